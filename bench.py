@@ -7,6 +7,13 @@ A "step" is one SparseOptimizer::optimize loop body = one LM outer iteration
 (computeActiveErrors, buildSystem, >=1 trial of setLambda/solve/update/
 restoreDiagonal/computeActiveErrors), all device-resident.  Inputs are resident
 in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline line
+(with the factorization's roofline figure, whose event timer sits inside the timed
+region).  `--dump-outputs DIR` also writes what the last timed step left.  `--full`
+adds everything that takes iterations or runs of its own: the per-stage breakdown
+and ms/linear-solve, the measured peaks, the secondary roofline lines, the C3 and
+C5 legs and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -33,8 +40,14 @@ def parse():
                          "WORLD_SIZE under torch.distributed.run, else 1)")
     ap.add_argument("--dry-run", action="store_true",
                     help="control plane only (rank spawn, gloo barrier, max over ranks, JSON shape): no GPU call")
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the stage breakdown (ms/linear-solve), the measured peaks, the secondary roofline "
+                         "lines, the C3 and C5 legs and the CPU baseline (the --no-* options below trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left (its statistics and every vertex "
+                         "estimate) as DIR/<name>.npy")
     ap.add_argument("--config", default="C4", help="C4 (default, BASELINE metric) or C5/C3/C2/C1; C4R (random covisibility), S2 (BlockSolver_3_2)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=6, help="timed oracle LM iterations (after iteration 0)")
@@ -42,7 +55,10 @@ def parse():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-posegraph", action="store_true", help="skip the C3 (100k-pose SE3) secondary leg")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 (4k x 1M x 10M BA) secondary leg")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_problem(cfg):
@@ -482,6 +498,44 @@ def stage_bytes(prob):
             "shared_records": {"information": shared_info, "intrinsics": shared_par}}
 
 
+DUMP_BUDGET_BYTES = 60 * 10**6  # of array data; the .npy headers come on top
+DUMP_SEED = 20261015
+
+
+DUMP_TRACE_STEPS = 65536
+
+
+def dump_outputs(outdir, prob, opt, timed, results):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 `outdir/<name>.npy`:
+    step_stats    [chi2, levenbergIterations, optimize_step's result (0 OK, 1 Terminate)] of the last timed step,
+    chi2_trace    chi2 after every timed step (the last DUMP_TRACE_STEPS of them),
+    estimates_<i> the estimates of the problem's i-th vertex set (insertion order), read back from the device.
+    Every value is finite in a sound run. The step's lambda is left out for that reason: once the problem has
+    converged the LM loop ends a step, as the reference's does, by raising lambda over rejected trials until it
+    overflows to +inf (the step's result is then Terminate and the state is the popped, unchanged one), so after enough
+    steps lambda says nothing that the result code does not.
+    The problem is seeded and every kernel sums in a fixed order, so two runs with the same arguments write the same
+    inputs' results. At most DUMP_BUDGET_BYTES in all: the budget left after the statistics is shared equally among
+    the vertex sets, and a set over its share is cut to a fixed, seeded sample of its rows (ascending row order)."""
+    os.makedirs(outdir, exist_ok=True)
+    last = timed[-1]
+    arrays = {"step_stats": np.array([last.chi2, float(last.levenbergIterations), float(results[-1])]),
+              "chi2_trace": np.array([s.chi2 for s in timed[-DUMP_TRACE_STEPS:]])}
+    share = (DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values())) // max(len(prob.vertices), 1)
+    rng = np.random.default_rng(DUMP_SEED)
+    for i, vs in enumerate(prob.vertices):
+        est = opt.estimates(vs.vtype)
+        rows = int(share // (est.shape[1] * est.itemsize))
+        if est.shape[0] > rows:
+            est = est[np.sort(rng.choice(est.shape[0], size=rows, replace=False))]
+        arrays[f"estimates_{i}"] = est
+    bad = [name for name, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"--dump-outputs: not finite: {bad}")
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
 METRIC = "LM iterations/sec + ms/linear-solve, synthetic BA 1k×100k at 1/2/4/8 GPUs"
 
 
@@ -552,23 +606,43 @@ def main():
     barrier(world)
     sync()
     t0 = time.perf_counter()
-    timed = []
+    timed, results = [], []
     for _ in range(args.steps):
         r, st = opt.optimize_step(it)
         timed.append(st)
+        results.append(r)
         it += 1
     sync()
     barrier(world)
     dt = time.perf_counter() - t0
     dt = allmax(dt, world)
-    value = args.steps / dt
-    trials = sum(s.levenbergIterations for s in timed)
     avg_ms = opt.kernel_ms(dom)
     launches = opt.kernel_count(dom)
+    if args.dump_outputs and rank == 0:  # before any further iteration: the state the last timed step left
+        dump_outputs(args.dump_outputs, prob, opt, timed, results)
+    kt = lin_ms = None
+    if args.full:
+        kt, lin_ms = stage_breakdown(args, opt, local, it)
+    finfo = opt.factor_info()
+    ranks = None
+    if world > 1:
+        ranks = allgather_obj(rank_record(opt, rank, local, {k: v["avg_ms"] for k, v in kt.items()} if kt else None),
+                              world)
+    report(args, prob, opt, rank, world, local, dt, timed, avg_ms, launches, kt, lin_ms, finfo, ranks, gen_s, warm_s)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
 
-    # stage breakdown: two more (untimed) iterations with every kernel class and stage timer on
-    names = ["linearize", "vreduce", "schur_dinv", "schur_diag", "schur_rows", "chol_factor", "chol_solve", "backsub",
-             "error", "oplus"]
+
+STAGE_NAMES = ["linearize", "vreduce", "schur_dinv", "schur_diag", "schur_rows", "chol_factor", "chol_solve", "backsub",
+               "error", "oplus"]
+
+
+def stage_breakdown(args, opt, local, it):
+    """--full: two more (untimed) iterations, from iteration `it`, with every kernel class and stage timer on, then
+    the measured peaks. Returns the per-class kernel times and the ms per linear solve of the two iterations."""
+    import g2o_amd
+    names = STAGE_NAMES
     if not args.no_kernel_timing:
         opt.enable_kernel_timing(True)
     opt.set_stats_level(2)
@@ -578,12 +652,20 @@ def main():
         it += 1
     lin_ms = [1e3 * s.timeLinearSolution / max(s.levenbergIterations, 1) for s in stage_st]
     kt = {k: {"avg_ms": opt.kernel_ms(k), "count": opt.kernel_count(k)} for k in names}
-    finfo = opt.factor_info()
-    ranks = allgather_obj(rank_record(opt, rank, local, {k: v["avg_ms"] for k, v in kt.items()}), world)
     try:  # after the timed region: ~1 s of streaming copy and MFMA / VALU issue loops
         PEAKS_MEASURED.update(g2o_amd.measure_peaks(local))
     except Exception as ex:  # reported, not fatal
         PEAKS_MEASURED["error"] = repr(ex)
+    return kt, lin_ms
+
+
+def report(args, prob, opt, rank, world, local, dt, timed, avg_ms, launches, kt, lin_ms, finfo, ranks, gen_s, warm_s):
+    """Build and print the JSON line (rank 0). `kt` / `lin_ms` are stage_breakdown's, None in a plain run; with
+    --full the secondary roofline lines and the other legs (C3, C5, CPU baseline) run here, after the headline's."""
+    import g2o_amd
+    dom = "chol_factor"
+    value = args.steps / dt
+    trials = sum(s.levenbergIterations for s in timed)
 
     # algorithmic flops of the factorization: sum_k c_k^2 under the REFERENCE ordering (cs_amd on the block
     # pattern, SURVEY.md §8d), from tools/chol_flops.py (oracle/_ref, committed JSON); the backend's own
@@ -613,7 +695,7 @@ def main():
         "launches_timed": launches,
     }
     secondary = []
-    if prob.landmark_dim:
+    if args.full and prob.landmark_dim:
         sb = stage_bytes(prob)
         rows_bytes = opt.kernel_bytes("schur_rows")
         ms_rows = kt["schur_rows"]["avg_ms"]
@@ -673,7 +755,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": 1e3 * dt / args.steps,
-        "ms_per_linear_solve": float(np.median(lin_ms)),
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -686,24 +767,36 @@ def main():
             "final_chi2": timed[-1].chi2 if timed else None,
             "parallelism": f"landmark-shard{world}" if world > 1 else "single",
         },
-        "stages_ms_avg": {k: v["avg_ms"] for k, v in kt.items()},  # 2 extra untimed iterations
-        "roofline": with_peaks(roofline),
-        "roofline_secondary": [with_peaks(d) for d in secondary],
-        "peaks": {"spec": {"hbm_GBps": PEAK_HBM_GBS, "fp64_TFps": PEAK_FP64_TFLOPS,
-                           "source": "MI355X_MICROARCH.md (spec)"},
-                  "measured": dict(PEAKS_MEASURED, source="g2ohip_measure_peaks on this GPU, this run")},
+        "roofline": with_peaks(roofline),  # against the measured peak too with --full
         "factor": finfo,
         "setup_s": {"generate": gen_s, "warmup_incl_structure": warm_s},
         "runtime": runtime,
     }
+    if world > 1:
+        out["ranks"] = ranks
+        out["comm"] = comm_record(ranks, world)
+    if args.full:
+        full_legs(args, prob, opt, rank, world, local, out, kt, lin_ms, secondary)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+
+
+def full_legs(args, prob, opt, rank, world, local, out, kt, lin_ms, secondary):
+    """--full: the figures of the stage iterations and the legs that are runs of their own (C3 pose graph, C5, CPU
+    baseline), added to the line `out`."""
+    out.update({
+        "ms_per_linear_solve": float(np.median(lin_ms)),
+        "stages_ms_avg": {k: v["avg_ms"] for k, v in kt.items()},  # 2 extra untimed iterations
+        "roofline_secondary": [with_peaks(d) for d in secondary],
+        "peaks": {"spec": {"hbm_GBps": PEAK_HBM_GBS, "fp64_TFps": PEAK_FP64_TFLOPS,
+                           "source": "AMD Instinct MI355X specification"},
+                  "measured": dict(PEAKS_MEASURED, source="g2ohip_measure_peaks on this GPU, this run")},
+    })
     if rank == 0 and world == 1 and not args.no_posegraph and args.config == "C4":
         try:
             out["pose_graph"] = posegraph_leg(local)
         except Exception as ex:  # reported, not fatal
             out["pose_graph"] = {"error": repr(ex)}
-    if world > 1:
-        out["ranks"] = ranks
-        out["comm"] = comm_record(ranks, world)
     if not args.no_c5 and args.config == "C4":
         # every rank: at N > 1 the C5 leg is the landmark-sharded multi-GPU configuration (its collectives need all)
         opt.close()
@@ -719,11 +812,6 @@ def main():
             out["cpu_baseline"] = cpu_baseline(prob, args.cpu_iters, args.cpu_threads)
         except Exception as ex:  # reported, not fatal
             out["cpu_baseline"] = {"error": repr(ex)}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -35,7 +35,7 @@ prof|prof5|prof3)
   # rocprofv3 kernel trace + stats of one config's bench run, then the PMC FETCH_SIZE / WRITE_SIZE passes -> traffic JSON
   case $STAGE in prof) CF=C4; ST=10;; prof5) CF=C5; ST=4;; prof3) CF=C3; ST=2;; esac
   CL=$(echo $CF | tr 'A-Z' 'a-z')
-  BA="--config $CF --no-cpu-baseline --no-posegraph --no-c5"
+  BA="--full --config $CF --no-cpu-baseline --no-posegraph --no-c5"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_$CL -o run -- python bench.py --steps $ST --warmup 2 $BA > $O/${TAG}_bench_prof_$CL.json 2> $O/${TAG}_bench_prof_$CL.err || { echo PROF_FAIL $CF; tail -20 $O/${TAG}_bench_prof_$CL.err; exit 1; }
   echo PROF_OK $CF
   RX='k_schur|k_linearize|k_backsub|k_vertex_reduce|k_cam_assemble|k_lm_fixup|k_zero_ranges|k_chol_scatter|k_vec_init|k_extend_add|k_step|k_syrk|k_permute'
@@ -47,7 +47,7 @@ prof|prof5|prof3)
 kstats)
   for CF in ${KSTATS_CONFIGS:-C4 C5 C3}; do
     D=$O/${TAG}_prof_$CF
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o run -- python bench.py --config $CF --no-cpu-baseline --no-posegraph --no-c5 > $D.json 2> $D.err || { echo PROF_FAIL $CF; tail -5 $D.err; exit 1; }
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o run -- python bench.py --full --config $CF --no-cpu-baseline --no-posegraph --no-c5 > $D.json 2> $D.err || { echo PROF_FAIL $CF; tail -5 $D.err; exit 1; }
     T=$(find $D -name '*kernel_trace.csv' | head -1)
     [ -n "$T" ] && python tools/factor_levels.py $T > $O/${TAG}_$(echo $CF | tr 'A-Z' 'a-z')_factor_levels.txt 2>&1
     echo KSTATS_OK $CF
@@ -59,14 +59,14 @@ bench)
     CU=$(echo $CL | tr 'a-z' 'A-Z')
     [ -f $O/${TAG}_traffic_$CL.json ] && export G2OHIP_TRAFFIC_JSON_$CU=$O/${TAG}_traffic_$CL.json
   done
-  timeout -k 10 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo BENCH_FAIL; tail -20 $O/${TAG}_bench.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo BENCH_FAIL; tail -20 $O/${TAG}_bench.err; exit 1; }
   echo BENCH_OK
   cat $O/${TAG}_bench.json
-  timeout -k 10 600 python bench.py --config C5 --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_c5.json 2> $O/${TAG}_bench_c5.err || { echo BENCH_C5_FAIL; tail -20 $O/${TAG}_bench_c5.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --config C5 --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_c5.json 2> $O/${TAG}_bench_c5.err || { echo BENCH_C5_FAIL; tail -20 $O/${TAG}_bench_c5.err; exit 1; }
   echo BENCH_C5_OK
   ;;
 line)
-  timeout -k 10 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo BENCH_FAIL; tail -20 $O/${TAG}_bench.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo BENCH_FAIL; tail -20 $O/${TAG}_bench.err; exit 1; }
   python -c "import json;d=json.load(open('$O/${TAG}_bench.json'));print('C4',d['value'],'factor',d['roofline']['avg_launch_ms'],'C5',d['c5']['value'],'C3',d['pose_graph']['value'])"
   ;;
 ab)

@@ -120,6 +120,56 @@ def test_bench_single_rank_dry_run():
     assert out["n_gpus"] == 1 and len(out["ranks"]) == 1
 
 
+def test_bench_full_option_dry_run():
+    """--full and --dump-outputs are accepted options; a dry run makes no GPU call and writes nothing."""
+    p, out = _run_bench(["--dry-run", "--full", "--steps", "2"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert out["dry_run"] is True and out["steps"] == 2
+    p, out = _run_bench(["--dry-run", "--steps", "0"])
+    assert p.returncode != 0 and out is None
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs writes the last timed step's statistics and every vertex set's estimates as float64 .npy, keeps
+    to its byte budget by a row sample that is the same from run to run, and leaves a set within its share whole."""
+    import types
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(5)
+    est = {3: rng.standard_normal((40, 7)), 9: rng.standard_normal((1000, 3))}
+    prob = types.SimpleNamespace(vertices=[types.SimpleNamespace(vtype=3), types.SimpleNamespace(vtype=9)])
+    opt = types.SimpleNamespace(estimates=lambda vtype: est[vtype].copy())
+    # the last step ended as a converged LM loop does: Terminate, lambda overflowed to +inf (never written out)
+    timed = [types.SimpleNamespace(chi2=4.0 - k, lambda_=0.5 ** k, levenbergIterations=1 + k) for k in range(3)]
+    timed[-1].lambda_ = float("inf")
+    results = [0, 0, 1]
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 6000 + 6 * 8)  # a 6000-byte share per vertex set
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), prob, opt, timed, results)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["chi2_trace.npy", "estimates_0.npy", "estimates_1.npy", "step_stats.npy"]
+        got.append({f: np.load(tmp_path / d / f) for f in files})
+    a, b = got
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert all(np.isfinite(v).all() for v in a.values())
+    assert np.array_equal(a["step_stats.npy"], [2.0, 3.0, 1.0])
+    assert np.array_equal(a["chi2_trace.npy"], [4.0, 3.0, 2.0])
+    assert np.array_equal(a["estimates_0.npy"], est[3])  # 2240 bytes: within its share
+    s = a["estimates_1.npy"]  # 24000 bytes: cut to 6000 // 24 rows, in ascending row order
+    assert s.shape == (250, 3)
+    rows = [int(np.flatnonzero((est[9] == r).all(axis=1))[0]) for r in s]
+    assert rows == sorted(set(rows))
+    assert sum(v.nbytes for v in a.values()) <= 2 * 6000 + 6 * 8
+    timed[-1].chi2 = float("nan")  # a broken run is an error, not a file of NaNs
+    with pytest.raises(RuntimeError, match="not finite"):
+        bench.dump_outputs(str(tmp_path / "c"), prob, opt, timed, results)
+    assert not os.path.exists(tmp_path / "c" / "step_stats.npy")
+
+
 def test_bench_refuses_world_mismatch():
     """Under a launcher whose WORLD_SIZE differs from --gpus the bench refuses instead of reporting the wrong N."""
     p, out = _run_bench(["--gpus", "2", "--dry-run"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

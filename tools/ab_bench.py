@@ -27,8 +27,8 @@ def main(argv):
             for kv in s.split(","):
                 k, v = kv.split("=", 1)
                 env[k] = v
-        cmd = [sys.executable, os.path.join(HERE, "bench.py"), "--config", cfg, "--no-cpu-baseline", "--no-posegraph",
-               "--no-c5"] + (extra or ["--steps", "6", "--warmup", "2"])
+        cmd = [sys.executable, os.path.join(HERE, "bench.py"), "--full", "--config", cfg, "--no-cpu-baseline",
+               "--no-posegraph", "--no-c5"] + (extra or ["--steps", "6", "--warmup", "2"])
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             print(f"{s}: FAILED rc={r.returncode}\n{r.stderr[-2000:]}", flush=True)
