@@ -481,7 +481,11 @@ class SparseOptimizer:
                         "distributed", "reduce_scatter", "rs_segment_doubles", "rs_tail_doubles", "model_input_s",
                         "model_input_allreduce_s", None,  # None: retired slots (always 0), kept for the ABI layout
                         "band_leaf", "aligned_shards", "local_block_doubles", "exchange_bytes_per_rank",
-                        "local_landmarks", "model_shard_s", "deferred_l21_fronts")
+                        "local_landmarks", "model_shard_s", "deferred_l21_fronts",
+                        # the Schur row pass on this rank: tasks and split row chunks of the G-block / Kt-record sets,
+                        # partial blocks staged by the parts; camera_list 0: all cameras, no list
+                        "schur_tasks", "schur_tasks_kx", "schur_part_groups", "schur_part_groups_kx",
+                        "schur_part_blocks", "camera_list")
 
     def factor_info(self) -> dict:
         out = np.zeros(len(self.FACTOR_INFO_KEYS))

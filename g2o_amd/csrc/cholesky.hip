@@ -756,8 +756,9 @@ __global__ void __launch_bounds__(256, 3) k_step(const StepTask* __restrict__ ta
     }
     __syncthreads();
     PH(2)
-    // L^-1 leaves from wave 0's registers; the block of X = L11^-1 it also is reaches xinv by k_xdiag after the
-    // factorization (the inverse tasks read it from linv meanwhile): no barrier and no LDS pass on the chain
+    // L^-1 leaves from wave 0's registers to linv: no barrier and no LDS pass on the chain. The block of X = L11^-1 it
+    // also is stays in linv (the inverse tasks and k_bwd_x read it there); xinv's diagonal blocks are valid only for
+    // the deferred-L21 fronts, whose level k_xdiag copies them in for k_l21, and zero for every other front
     if (tid < 64) factor_block(Dn, kbn, vn, col, tid, fail, ysol + t.c0 + r0, PH_REC, nullptr, linv + (size_t)(t.c0 + r0) * (NB * NB));
     PH(3)
     PH(4)

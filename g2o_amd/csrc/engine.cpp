@@ -3707,8 +3707,17 @@ int Engine::stage(double lambda, double* b, double* x, double* Hs, double* bs, l
   set_lambda(lambda, 1);
   const int ok = solve_sync();
   // the distributed factorization reduce-scatters S (dS keeps this rank's partial sums): the whole reduced system
-  // for the caller takes one more all-reduce (every rank calls stage, as it calls every other collective step)
-  if ((Hs || bs) && do_schur && chol.rs_on) allreduce_sum(dS.get(), (size_t)nS * pd * pd + size_poses);
+  // for the caller takes one more all-reduce (every rank calls stage, as it calls every other collective step), into a
+  // copy as in linear_residual: dS must keep the zeros of the blocks and rhs rows this rank's task lists never write
+  // (sch_skip), which the next reduce_input sums again
+  const double* sred = dS.get();
+  if ((Hs || bs) && do_schur && chol.rs_on) {
+    const size_t len = (size_t)nS * pd * pd + size_poses;
+    dsfull.resize(len);
+    HIP_CHECK(hipMemcpyAsync(dsfull.get(), dS.get(), len * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    allreduce_sum(dsfull.get(), len);
+    sred = dsfull.get();
+  }
   if (b) db.download(b, n, stream);
   if (x) dx.download(x, n, stream);
   if (Hs || bs) {
@@ -3717,10 +3726,10 @@ int Engine::stage(double lambda, double* b, double* x, double* Hs, double* bs, l
     const std::vector<int>& bi = do_schur ? s_bi : hpp_bi;
     const std::vector<int>& bj = do_schur ? s_bj : hpp_bj;
     blocks.resize(bi.size() * pd * pd);
-    if (do_schur) dS.download(blocks.data(), blocks.size(), stream);
+    if (do_schur) HIP_CHECK(hipMemcpyAsync(blocks.data(), sred, sizeof(double) * blocks.size(), hipMemcpyDeviceToHost, stream));
     else dH.download(blocks.data(), blocks.size(), stream);
     std::vector<double> bsv(np);
-    if (do_schur) HIP_CHECK(hipMemcpyAsync(bsv.data(), dS.get() + (size_t)nS * pd * pd, sizeof(double) * np, hipMemcpyDeviceToHost, stream));
+    if (do_schur) HIP_CHECK(hipMemcpyAsync(bsv.data(), sred + (size_t)nS * pd * pd, sizeof(double) * np, hipMemcpyDeviceToHost, stream));
     else db.download(bsv.data(), np, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
     if (Hs) {
@@ -3933,7 +3942,11 @@ int Engine::factor_info(double* out, int n) {
                       (double)chol.rs_seg, (double)chol.rs_tail_len, chol.rs_model[0], chol.rs_model[1],
                       0.0 /* retired: 64-column-step levels */, (double)S.band_leaf, dist_aligned ? 1.0 : 0.0,
                       (double)chol.rs_local, exchange_bytes(), (double)local_lm.size(), chol.shard_model,
-                      (double)chol.n_deferred_l21};
+                      (double)chol.n_deferred_l21,
+                      // the Schur row pass's task lists (G-block set, Kt-record set), their split row chunks and the
+                      // partial blocks those stage, the split camera pass's camera list (0: every camera, no list)
+                      (double)nsch_tasks, (double)nsch_tasks_kx, (double)nsch_groups, (double)nsch_groups_kx,
+                      (double)sch_part_blocks, (double)ncam_list};
   const int m = (int)(sizeof v / sizeof v[0]);
   for (int k = 0; k < std::min(n, m); ++k) out[k] = v[k];
   return m;

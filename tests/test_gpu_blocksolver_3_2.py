@@ -173,3 +173,140 @@ def test_slam2d_sharded(g2o_amd_mod, oracle):
     assert np.array_equal(states[1][:3 * N], states[0][:3 * N])
     xr = ref.minimal_state()
     assert np.linalg.norm(x - xr) <= RTOL * np.linalg.norm(xr)
+
+
+# ---- row chunks split into parts with 3x3 blocks: schur_row_store<3>'s partial-block store (odd PD: the second column
+# half holds one column only) and k_schur_part_sum<3> ----
+_DENSE = {}  # the dense problem, its oracle results and the single-GPU run: computed once, shared, left unchanged
+
+
+def _slam2d_dense():
+    """slam2d(60, landmarks_per_cell=2.0, sensor_range=4.0, max_obs_per_pose=64): 59 free poses, 538 landmarks, 3840
+    observations, up to 28 off-diagonal blocks per row. A row chunk is split only when it stages >= 512 blocks (its own
+    observations + their partners in the chunk): 14 of the 58 chunks do (the largest stages 792), so 14 part groups with
+    the target forced on one GPU; on 2 ranks with the default target 14 / 0, on 3 ranks 10 / 0 / 0. The pose count does
+    not matter for the density (30 poses: 11 such chunks); 48 observations per pose leave 2 chunks, sensor range 3
+    leaves 7; slam2d(300) with its defaults stages at most 143 blocks per chunk."""
+    if "prob" not in _DENSE:
+        _DENSE["prob"] = synth.slam2d(60, landmarks_per_cell=2.0, sensor_range=4.0, max_obs_per_pose=64)
+    return _DENSE["prob"]
+
+
+def _dense_oracle(oracle, iters):
+    key = ("oracle", iters)
+    if key not in _DENSE:
+        ref = oracle.OracleGraph(_slam2d_dense())
+        _, sr = ref.optimize(iters, oracle.make_config(threads=8))
+        _DENSE[key] = ([(s.chi2, s.levenbergIterations) for s in sr], ref.minimal_state())
+    return _DENSE[key]
+
+
+def _run_3_2(g2o_amd_mod, prob, iters):
+    opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+    opt.set_algorithm("lm_hip_fix3_2")
+    n, st = opt.optimize(iters)
+    return opt, n, [(s.chi2, s.levenbergIterations) for s in st], opt.minimal_state()
+
+
+def _check_against_oracle(traj, x, oracle_traj, xr):
+    assert len(traj) == len(oracle_traj)
+    for (chi, trials), (rchi, rtrials) in zip(traj, oracle_traj):
+        assert trials == rtrials
+        assert abs(chi - rchi) <= RTOL * abs(rchi), (chi, rchi)
+    assert np.linalg.norm(x - xr) <= RTOL * np.linalg.norm(xr)
+
+
+def test_slam2d_row_parts(g2o_amd_mod, oracle, monkeypatch):
+    """Split row chunks (G2OHIP_SCHUR_SPLIT_TASKS forced, one GPU) on a BlockSolver_3_2 graph dense enough for them
+    (_slam2d_dense: 14 part groups): the reduced system and solution against the oracle, every entry of Hschur and
+    bschur within 1e-13 of the matrix scale of the unsplit pass (a differently ordered f64 sum of O(100) terms of that
+    scale, as tests/test_gpu_schur_split.py), a 5-iteration trajectory against the unsplit pass and the oracle."""
+    prob = _slam2d_dense()
+    lam, iters = 1e-3, 5
+    r = oracle.OracleGraph(prob).stage(lam)
+    out, runs = {}, {}
+    for target in ("1000000", "0"):
+        monkeypatch.setenv("G2OHIP_SCHUR_SPLIT_TASKS", target)
+        opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+        opt.set_algorithm("lm_hip_fix3_2")
+        g = out[target] = opt.stage(lam)
+        info = opt.factor_info()
+        assert opt.block_dims()[:2] == [3, 2]
+        if target == "0":
+            assert info["schur_part_groups"] == 0 and info["schur_part_blocks"] == 0, info
+        else:
+            assert info["schur_part_groups"] > 0 and info["schur_part_blocks"] > 0, info
+        assert g["ok"] == r["ok"] == 1
+        for k in ("b", "bschur", "x"):
+            assert np.linalg.norm(g[k] - r[k]) <= 1e-9 * np.linalg.norm(r[k]), (target, k)
+        assert np.linalg.norm(g["Hschur"] - r["Hschur"]) <= 1e-11 * np.linalg.norm(r["Hschur"]), target
+        runs[target] = _run_3_2(g2o_amd_mod, prob, iters)
+    for k in ("Hschur", "bschur"):
+        x, y = np.asarray(out["1000000"][k]), np.asarray(out["0"][k])
+        scale = np.abs(y).max()
+        err = np.abs(x - y).max() / scale
+        print(f"{k}: split parts against the unsplit pass, max entry error / scale {err:.3e}")
+        assert err <= 1e-13, (k, err)
+    (_, n1, t1, x1), (_, n0, t0, x0) = runs["1000000"], runs["0"]
+    assert n1 == n0 == iters
+    assert [t for _, t in t1] == [t for _, t in t0]
+    assert np.allclose([c for c, _ in t1], [c for c, _ in t0], rtol=1e-10, atol=0)
+    assert np.linalg.norm(x1 - x0) <= 1e-10 * np.linalg.norm(x0)
+    _check_against_oracle(t1, x1, *_dense_oracle(oracle, iters))
+
+
+@pytest.mark.parametrize("nranks", [2, 3])
+def test_slam2d_dense_sharded(g2o_amd_mod, oracle, nranks):
+    """Landmark shards of the dense graph with the sharded path's default split target (2048 tasks; nothing forced):
+    some rank splits row chunks, and the run follows the single-GPU trajectory (state 1e-9) and the oracle (1e-6)."""
+    prob = _slam2d_dense()
+    iters = 4
+    key = uuid.uuid4().hex
+    opts = [g2o_amd_mod.SparseOptimizer(0).add_problem(prob) for _ in range(nranks)]
+    for r, o in enumerate(opts):
+        o.set_algorithm("lm_hip_fix3_2")
+        o.set_comm_local(key, r, nranks)
+    res, errs = [None] * nranks, []
+
+    def body(r):
+        try:
+            res[r] = opts[r].optimize(iters)
+        except Exception as ex:  # surfaced below
+            errs.append(ex)
+
+    th = [threading.Thread(target=body, args=(r,)) for r in range(nranks)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    assert not errs, errs
+    info = [o.factor_info() for o in opts]
+    groups = [int(i["schur_part_groups"]) for i in info]
+    print("schur_part_groups per rank:", groups, "schur_tasks:", [int(i["schur_tasks"]) for i in info])
+    assert any(g > 0 for g in groups), info
+    assert all(i["schur_part_blocks"] > 0 for i in info if i["schur_part_groups"] > 0), info
+    if "single" not in _DENSE:
+        _DENSE["single"] = _run_3_2(g2o_amd_mod, prob, iters)[1:]
+    n1, traj1, xs = _DENSE["single"]
+    oracle_traj, xr = _dense_oracle(oracle, iters)
+    # poses (ids first, 3 each) from rank 0; each landmark (2 each, id order) from the rank whose shard holds it
+    N, lm_ids = prob.vertices[0].ids.size, np.asarray(prob.vertices[1].ids)
+    states = [o.minimal_state() for o in opts]
+    x = states[0].copy()
+    held = np.zeros(lm_ids.size, np.int32)
+    for o, s in zip(opts, states):
+        assert np.array_equal(s[:3 * N], states[0][:3 * N])
+        lid = o.local_landmark_ids()
+        k = np.searchsorted(lm_ids, lid)
+        assert np.array_equal(lm_ids[k], lid)
+        held[k] += 1
+        rows = (3 * N + 2 * k[:, None] + np.arange(2)[None, :]).ravel()
+        x[rows] = s[rows]
+    assert np.all(held == 1)
+    for r in range(nranks):
+        n, st = res[r]
+        assert n == n1 == iters
+        traj = [(s.chi2, s.levenbergIterations) for s in st]
+        assert [t for _, t in traj] == [t for _, t in traj1]
+        _check_against_oracle(traj, x, oracle_traj, xr)
+    assert np.linalg.norm(x - xs) <= 1e-9 * np.linalg.norm(xs)

@@ -172,8 +172,70 @@ def test_split_row_parts(g2o_amd_mod, oracle, name, monkeypatch):
         monkeypatch.setenv("G2OHIP_SCHUR_SPLIT_TASKS", flag)
         opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
         n, st = opt.optimize(5)
+        info = opt.factor_info()  # of the structure the LM loop built and ran on
+        if flag == "0":
+            assert info["schur_part_groups"] == 0 and info["schur_part_groups_kx"] == 0, info
+            assert info["schur_part_blocks"] == 0, info
+        else:  # the LM loop's split walks the Kt-record set: its chunks must really be split (and the G-block set's)
+            assert info["schur_tasks_kx"] > 0 and info["schur_part_groups_kx"] > 0, info
+            assert info["schur_part_groups"] > 0 and info["schur_part_blocks"] > 0, info
         runs.append((n, [s.chi2 for s in st], [s.levenbergIterations for s in st], opt.minimal_state()))
     (n1, c1, t1, x1), (n0, c0, t0, x0) = runs
+    assert n1 == n0 and t1 == t0
+    assert np.allclose(c1, c0, rtol=1e-10, atol=0)
+    assert np.linalg.norm(x1 - x0) <= 1e-10 * np.linalg.norm(x0)
+
+
+_ORACLE_STAGE = {}  # per problem: computed once, shared by the cases below, left unchanged
+
+
+def _oracle_stage(oracle, name, prob, lam):
+    if (name, lam) not in _ORACLE_STAGE:
+        _ORACLE_STAGE[(name, lam)] = oracle.OracleGraph(prob).stage(lam)
+    return _ORACLE_STAGE[(name, lam)]
+
+
+@pytest.mark.parametrize("name", ["C4", "C5", "C4R"])
+@pytest.mark.parametrize("flags", [{"G2OHIP_SCHUR_KX": "0", "G2OHIP_CAM_KX": "0"}, {"G2OHIP_SCHUR_SPLIT": "0"}],
+                         ids=["g_blocks", "plain_passes"])
+def test_split_row_parts_g_blocks(g2o_amd_mod, oracle, name, flags, monkeypatch):
+    """Split row chunks outside the Kt-record pass: the generic row pass's partial-block store and k_schur_part_sum<6>
+    behind the split with G blocks (G2OHIP_SCHUR_KX=0) and behind the plain passes (G2OHIP_SCHUR_SPLIT=0). C5-small has
+    rows with more than 64 off-diagonal slots (a second chunk with noff < 64), C4R-small up to 117 (ragged second
+    chunks). Forced target, one GPU: schur_part_groups 35 (C4), 68 (C5), 136 (C4R) of 37 / 77 / 170 chunks.
+    Stage-level system and solution against the oracle; every entry of Hschur and bschur within 1e-13 of the matrix
+    scale of the unsplit pass (the bound test_split_kx_records_match_g_blocks derives for a differently ordered f64 sum
+    of O(100) terms of that scale); the LM trajectory against the unsplit pass."""
+    for k, v in flags.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("G2OHIP_STAGE_SPLIT", "1")
+    prob = synth.by_name(name, "small")
+    lam = 1e-3
+    r = _oracle_stage(oracle, name, prob, lam)
+    out, runs = {}, {}
+    for target in ("1000000", "0"):
+        monkeypatch.setenv("G2OHIP_SCHUR_SPLIT_TASKS", target)
+        opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+        g = out[target] = opt.stage(lam)
+        info = opt.factor_info()
+        if target == "0":
+            assert info["schur_part_groups"] == 0 and info["schur_part_blocks"] == 0, info
+        else:  # both configurations walk the G-block set
+            assert info["schur_part_groups"] > 0 and info["schur_part_blocks"] > 0, info
+        assert g["ok"] == r["ok"] == 1
+        for k in ("b", "bschur", "x"):
+            assert np.linalg.norm(g[k] - r[k]) <= 1e-9 * np.linalg.norm(r[k]), (target, k)
+        assert np.linalg.norm(g["Hschur"] - r["Hschur"]) <= 1e-11 * np.linalg.norm(r["Hschur"]), target
+        opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+        n, st = opt.optimize(5)
+        runs[target] = (n, [s.chi2 for s in st], [s.levenbergIterations for s in st], opt.minimal_state())
+    for k in ("Hschur", "bschur"):
+        x, y = np.asarray(out["1000000"][k]), np.asarray(out["0"][k])
+        scale = np.abs(y).max()
+        err = np.abs(x - y).max() / scale
+        print(f"{name} {k}: split parts against the unsplit pass, max entry error / scale {err:.3e}")
+        assert err <= 1e-13, (k, err)
+    (n1, c1, t1, x1), (n0, c0, t0, x0) = runs["1000000"], runs["0"]
     assert n1 == n0 and t1 == t0
     assert np.allclose(c1, c0, rtol=1e-10, atol=0)
     assert np.linalg.norm(x1 - x0) <= 1e-10 * np.linalg.norm(x0)

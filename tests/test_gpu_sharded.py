@@ -281,3 +281,245 @@ def test_distributed_linear_residual(g2o_amd_mod, monkeypatch):
     assert single.solve()
     r1 = single.linear_residual()
     assert r1 <= 1e-10 and abs(out[0] - r1) <= 1e-10, (out[0], r1)
+
+
+# ---- stage() and the low-level solver calls on ranks whose task lists skip work (aligned shards, distributed factor) ----
+# synth.ba(160, 3200) on 4 ranks under G2OHIP_DIST_FACTOR=1: the smallest of the banded problems tried (400 x 20000,
+# 200 x 10000, 200 x 4000, 160 x 3200, 120 x 2400, 100 x 2000 cameras x points) on which two ranks own subtrees with a
+# real shard each and both skip (at 120 x 2400 and below one rank holds nine tenths of the landmarks; at 100 x 2000 two
+# ranks hold none). 158 free cameras, one GPU: schur_tasks 157 = schur_tasks_kx. Observed per rank (0..3):
+#   local_landmarks 2003 / 886 / 156 / 155, camera_list 128 / 93 / 63 / 63 (of 158),
+#   schur_tasks 396 / 176 / 62 / 62 (split row chunks add part tasks: schur_part_groups 79 / 47 / 0 / 0),
+#   schur_tasks_kx 267 / 122 / 62 / 62 (schur_part_groups_kx 67 / 27 / 0 / 0).
+#
+# The staged lambdas are those of the LM run on this problem (its four iterations use 1387, 462, 154 and 51), rounded:
+# the 1e-9 bound on x only means something where the reference solve itself is that accurate. The reduced system's
+# largest eigenvalue is 3.7e8 (pixel units), so its condition number is 2.5e9 at lambda = 1e-3, where the oracle's own x
+# is 1.6e-9 from an iteratively refined extended-precision solve of its own [Hschur | bschur] — beyond the bound before
+# the device does anything. At lambda = 1e3 the condition number is 2.0e5 and the oracle's own error 2e-13, at
+# lambda = 50 they are 1.6e6 and 6.5e-12: two to three orders of room under 1e-9 for a backward-stable solve.
+SKIP_NRANKS = 4
+SKIP_LAM = 1e3
+SKIP_LAM_OTHER = 50.0
+
+
+@pytest.fixture(scope="module")
+def skip_case(g2o_amd_mod, oracle):
+    prob = synth.ba(160, 3200)
+    single = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+    single.initialize_optimization()
+    single.build_structure()
+    refs = {}
+
+    def oracle_stage(lam):  # computed once per lambda, shared and left unchanged
+        if lam not in refs:
+            refs[lam] = oracle.OracleGraph(prob).stage(lam)
+        return refs[lam]
+
+    return dict(prob=prob, single_info=single.factor_info(), oracle_stage=oracle_stage)
+
+
+@pytest.fixture(params=["0", "1"])
+def stage_split(request, monkeypatch):
+    """G2OHIP_STAGE_SPLIT: stage() through the plain passes (k_schur_diag writes every camera row; only the row pass
+    skips) or through the Schur split formed at assembly (the camera pass honours the rank's camera list too)."""
+    monkeypatch.setenv("G2OHIP_DIST_FACTOR", "1")
+    monkeypatch.setenv("G2OHIP_STAGE_SPLIT", request.param)
+    return request.param
+
+
+def _local_ranks(g2o_amd_mod, prob, nranks):
+    key = uuid.uuid4().hex
+    opts = [g2o_amd_mod.SparseOptimizer(0).add_problem(prob) for _ in range(nranks)]
+    for r, o in enumerate(opts):
+        o.set_comm_local(key, r, nranks)
+    return opts
+
+
+def _on_ranks(opts, fn):
+    """fn(optimizer) on every rank, one host thread each (every rank takes part in every collective)."""
+    out, errs = [None] * len(opts), []
+
+    def body(r):
+        try:
+            out[r] = fn(opts[r])
+        except Exception as ex:  # surfaced below
+            errs.append(ex)
+
+    th = [threading.Thread(target=body, args=(r,)) for r in range(len(opts))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    assert not errs, errs
+    assert not any(t.is_alive() for t in th), "a rank did not return"
+    return out
+
+
+def _assert_skips(case, opts, split):
+    """The ranks really run the distributed, aligned, reduce-scattered path, and really skip work."""
+    info = [o.factor_info() for o in opts]
+    brief = [{k: int(i[k]) for k in ("distributed", "aligned_shards", "reduce_scatter", "camera_list", "schur_tasks",
+                                     "schur_tasks_kx", "schur_part_groups", "schur_part_groups_kx", "local_landmarks")}
+             for i in info]
+    print("per-rank schedule:", brief)
+    assert all(i["distributed"] == 1 and i["aligned_shards"] == 1 and i["reduce_scatter"] == 1 for i in info), brief
+    num_poses = opts[0].block_dims()[2]
+    if split == "1":
+        assert any(0 < i["camera_list"] < num_poses for i in info), (num_poses, brief)
+    key = "schur_tasks_kx" if split == "1" else "schur_tasks"  # the set the staged build walks
+    assert case["single_info"][key] > 0
+    assert any(i[key] < case["single_info"][key] for i in info), (case["single_info"][key], brief)
+
+
+def _gather_x(prob, opts, xs, npose):
+    """Solver vectors of the ranks in the single-GPU layout: the pose part of rank 0, each landmark's entries from the
+    rank holding it. The ranks' shards are consecutive ranges of the (cut-aligned) landmark order, so rank r's entries
+    start after those of the ranks before it."""
+    ids = np.asarray(prob.vertices[1].ids)
+    assert np.all(np.diff(ids) > 0)
+    out = np.zeros_like(xs[0])
+    out[:npose] = xs[0][:npose]
+    off = 0
+    for o, x in zip(opts, xs):
+        lid = o.local_landmark_ids()
+        k = np.searchsorted(ids, lid)
+        assert np.array_equal(ids[k], lid)
+        rows = (npose + 3 * k[:, None] + np.arange(3)[None, :]).ravel()
+        out[rows] = x[npose + 3 * off: npose + 3 * (off + lid.size)]
+        off += lid.size
+    assert off == ids.size
+    return out
+
+
+def _check_stage_against(prob, opts, outs, ref, what):
+    for r, g in enumerate(outs):
+        assert g["ok"] == ref["ok"] == 1
+        eh = np.linalg.norm(g["Hschur"] - ref["Hschur"]) / np.linalg.norm(ref["Hschur"])
+        eb = np.linalg.norm(g["bschur"] - ref["bschur"]) / np.linalg.norm(ref["bschur"])
+        print(f"{what} rank {r}: Hschur rel {eh:.3e} bschur rel {eb:.3e}")
+        assert eh <= 1e-11, (what, r, eh)
+        assert eb <= 1e-9, (what, r, eb)
+    npose = ref["np"]
+    for g in outs[1:]:  # x meets in one all-reduce: the pose part is identical on every rank
+        assert np.array_equal(g["x"][:npose], outs[0]["x"][:npose])
+    x = _gather_x(prob, opts, [g["x"] for g in outs], npose)
+    ex = np.linalg.norm(x - ref["x"]) / np.linalg.norm(ref["x"])
+    print(f"{what}: x rel {ex:.3e}")
+    assert ex <= 1e-9, (what, ex)
+
+
+def test_distributed_stage_twice(g2o_amd_mod, skip_case, stage_split):
+    """stage() twice on the same ranks (ba(160, 3200), 4 ranks, counts above): the reduced system a rank hands out is
+    all-reduced, but its own dS must keep its partial sums and the zeros of what its task lists skip, or the second
+    call sums the first call's totals again. First call against the oracle, second call bitwise equal to the first
+    (every kernel sums in a fixed order, LocalComm reduces in rank order), a third call at another lambda against the
+    oracle at that lambda (a cached first result would not pass)."""
+    prob = skip_case["prob"]
+    opts = _local_ranks(g2o_amd_mod, prob, SKIP_NRANKS)
+    first = _on_ranks(opts, lambda o: o.stage(SKIP_LAM))
+    _assert_skips(skip_case, opts, stage_split)
+    _check_stage_against(prob, opts, first, skip_case["oracle_stage"](SKIP_LAM), "first stage")
+    second = _on_ranks(opts, lambda o: o.stage(SKIP_LAM))
+    for r, (a, b) in enumerate(zip(first, second)):
+        assert b["ok"] == 1
+        for k in ("Hschur", "bschur", "b", "x"):
+            d = np.abs(a[k] - b[k]).max()
+            assert np.array_equal(a[k], b[k]), f"rank {r}: second stage() differs from the first in {k}: max |diff| {d:.3e}" \
+                                               f" (max |{k}| {np.abs(a[k]).max():.3e})"
+    third = _on_ranks(opts, lambda o: o.stage(SKIP_LAM_OTHER))
+    _check_stage_against(prob, opts, third, skip_case["oracle_stage"](SKIP_LAM_OTHER), "third stage")
+
+
+def _low_level(o, lam):
+    o.build_system()
+    o.set_lambda(lam, True)
+    assert o.solve()
+    res = o.linear_residual()
+    x = o.x()
+    o.restore_diagonal()
+    return res, x
+
+
+def test_distributed_stage_then_low_level(g2o_amd_mod, skip_case, stage_split):
+    """buildSystem / setLambda / solve / linear_residual after a stage() on the same structure, against the same calls
+    on ranks that never staged: residual and solution bitwise equal (stage() leaves nothing behind in dS), the solution
+    within 1e-9 of the single-GPU solve, the residual <= 1e-10."""
+    prob = skip_case["prob"]
+
+    def staged_first(o):
+        g = o.stage(SKIP_LAM)
+        assert g["ok"] == 1
+        return _low_level(o, SKIP_LAM)
+
+    def fresh(o):
+        o.initialize_optimization()
+        o.build_structure()
+        return _low_level(o, SKIP_LAM)
+
+    opts = _local_ranks(g2o_amd_mod, prob, SKIP_NRANKS)
+    got = _on_ranks(opts, staged_first)
+    _assert_skips(skip_case, opts, stage_split)
+    fopts = _local_ranks(g2o_amd_mod, prob, SKIP_NRANKS)
+    want = _on_ranks(fopts, fresh)
+    _assert_skips(skip_case, fopts, stage_split)
+    for r, ((res, x), (fres, fx)) in enumerate(zip(got, want)):
+        print(f"rank {r}: residual after stage {res:.3e}, fresh {fres:.3e}, max |x - x_fresh| {np.abs(x - fx).max():.3e}")
+    for r, ((res, x), (fres, fx)) in enumerate(zip(got, want)):
+        assert res == fres, f"rank {r}: linear_residual {res:.6e} after stage(), {fres:.6e} on fresh ranks"
+        assert np.array_equal(x, fx), f"rank {r}: solution differs after stage(): max |diff| {np.abs(x - fx).max():.3e}"
+        assert res <= 1e-10, (r, res)
+    single = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+    single.initialize_optimization()
+    single.build_structure()
+    _, xs = _low_level(single, SKIP_LAM)
+    npose = 6 * single.block_dims()[2]
+    xg = _gather_x(prob, opts, [x for _, x in got], npose)
+    rel = np.linalg.norm(xg - xs) / np.linalg.norm(xs)
+    print(f"sharded solution against single GPU: rel {rel:.3e}")
+    assert rel <= 1e-9, rel
+
+
+def test_distributed_stage_then_optimize(g2o_amd_mod, oracle, skip_case, stage_split):
+    """optimize(4) after a stage(), and a stage() after optimize(4): the trajectories (chi2, trials, gathered state)
+    equal those of ranks that never staged, bitwise; the stage after the optimization matches the oracle's stage at the
+    oracle's optimized state."""
+    prob = skip_case["prob"]
+    iters = 4
+
+    def plain(o):
+        return o.optimize(iters), None
+
+    def stage_before(o):
+        g = o.stage(SKIP_LAM)
+        assert g["ok"] == 1
+        return o.optimize(iters), None
+
+    def stage_after(o):
+        res = o.optimize(iters)
+        return res, o.stage(SKIP_LAM)
+
+    runs = {}
+    for name, fn in (("plain", plain), ("stage_before", stage_before), ("stage_after", stage_after)):
+        opts = _local_ranks(g2o_amd_mod, prob, SKIP_NRANKS)
+        out = _on_ranks(opts, fn)
+        _assert_skips(skip_case, opts, stage_split)
+        x, _ = _gather_state(prob, opts)
+        runs[name] = (opts, out, x)
+    _, pout, px = runs["plain"]
+    for name in ("stage_before", "stage_after"):
+        _, out, x = runs[name]
+        for r in range(SKIP_NRANKS):
+            (n, st), (pn, pst) = out[r][0], pout[r][0]
+            assert n == pn == iters
+            assert [s.chi2 for s in st] == [s.chi2 for s in pst], (name, r)
+            assert [s.levenbergIterations for s in st] == [s.levenbergIterations for s in pst], (name, r)
+        assert np.array_equal(x, px), (name, np.abs(x - px).max())
+    ref = oracle.OracleGraph(prob)
+    nr, sr = ref.optimize(iters, oracle.make_config(threads=8))
+    assert nr == iters
+    for a, b in zip(pout[0][0][1], sr):
+        assert a.levenbergIterations == b.levenbergIterations
+        assert abs(a.chi2 - b.chi2) <= RTOL * b.chi2
+    opts, out, _ = runs["stage_after"]
+    _check_stage_against(prob, opts, [o[1] for o in out], ref.stage(SKIP_LAM), "stage after optimize")
