@@ -61,8 +61,9 @@ EXPORTS = [
     "g2ohip_solver_restore_diagonal", "g2ohip_solver_solve", "g2ohip_solver_vector_size", "g2ohip_solver_block_dims",
     "g2ohip_solver_get_x", "g2ohip_solver_get_b", "g2ohip_solver_multiply_hessian",
     "g2ohip_solver_linear_residual", "g2ohip_solver_factor_info", "g2ohip_solver_compute_marginals", "g2ohip_update", "g2ohip_push", "g2ohip_pop",
-    "g2ohip_discard_top", "g2ohip_stage", "g2ohip_linear_solve_ccs", "g2ohip_comm_unique_id",
-    "g2ohip_set_comm", "g2ohip_set_comm_local", "g2ohip_comm_selftest", "g2ohip_comm_selftest_rs", "g2ohip_symbolic_analyze", "g2ohip_dist_plan", "g2ohip_local_landmarks", "g2ohip_enable_kernel_timing",
+    "g2ohip_discard_top", "g2ohip_stage", "g2ohip_linear_solve_ccs", "g2ohip_linear_solve_ccs_ex",
+    "g2ohip_comm_unique_id",
+    "g2ohip_set_comm", "g2ohip_set_comm_local", "g2ohip_comm_selftest", "g2ohip_comm_selftest_rs", "g2ohip_symbolic_analyze", "g2ohip_symbolic_supernodes", "g2ohip_dist_plan", "g2ohip_local_landmarks", "g2ohip_enable_kernel_timing",
     "g2ohip_kernel_timing_only", "g2ohip_set_stats_level", "g2ohip_kernel_ms",
     "g2ohip_kernel_count", "g2ohip_kernel_bytes", "g2ohip_kernel_flops", "g2ohip_last_error",
     "g2ohip_version", "g2ohip_host_payload_len", "g2ohip_solver_save_hessian", "g2ohip_solver_set_write_debug",
@@ -130,6 +131,7 @@ def lib() -> C.CDLL:
         "g2ohip_discard_top": ([P], I),
         "g2ohip_stage": ([P, D, P, P, P, P, P], I),
         "g2ohip_linear_solve_ccs": ([I, I, P, P, P, P, P, I, P], I),
+        "g2ohip_linear_solve_ccs_ex": ([I, I, P, P, P, P, P, I, P, P, I], I),
         "g2ohip_comm_unique_id": ([P], I),
         "g2ohip_set_comm": ([P, P, I, I], I),
         "g2ohip_set_comm_local": ([P, C.c_char_p, I, I], I),
@@ -137,6 +139,7 @@ def lib() -> C.CDLL:
         "g2ohip_comm_selftest_rs": ([I, P, I, P, P, P], I),
         "g2ohip_debug_phases": ([P, I], I),
         "g2ohip_symbolic_analyze": ([I, I, I, P, P, P, P], I),
+        "g2ohip_symbolic_supernodes": ([I, I, I, P, P, P, P, P, I], I),
         "g2ohip_dist_plan": ([I, I, I, P, P, I, I, I, P, P, P, I], I),
         "g2ohip_local_landmarks": ([P, P, I], I),
         "g2ohip_enable_kernel_timing": ([P, I], None),
@@ -221,6 +224,17 @@ def symbolic_analyze(nblocks: int, bdim: int, bi, bj):
     return perm, dict(nnzL=st[0], flops=st[1], supernodes=int(st[2]), levels=int(st[3]), panel_steps=int(st[4]))
 
 
+def symbolic_supernodes(nblocks: int, bdim: int, bi, bj):
+    """Host-only: (ns, nr, level) arrays of the supernodes symbolic_analyze finds (scalar columns, scalar rows below
+    the diagonal block, level with leaves 0)."""
+    bi = np.ascontiguousarray(bi, np.int32)
+    bj = np.ascontiguousarray(bj, np.int32)
+    ns, nr, lv = (np.zeros(nblocks, np.int32) for _ in range(3))
+    m = lib().g2ohip_symbolic_supernodes(nblocks, bdim, len(bi), _p(bi), _p(bj), _p(ns), _p(nr), _p(lv), nblocks)
+    _check(m, "symbolic_supernodes")
+    return ns[:m], nr[:m], lv[:m]
+
+
 DIST_PLAN_KEYS = ("distributed", "rank_subtrees_s", "shared_s", "replicated_s", "exchange_s", "input_s",
                   "input_replicated_s", "max_rank_subtrees_s", "root_allgather_doubles", "rs_segment_doubles",
                   "rs_tail_doubles", "supernodes", "shard_s", "shard_replicated_s")
@@ -245,8 +259,14 @@ def dist_plan(nblocks: int, bdim: int, bi, bj, nranks: int, rank: int = 0, reduc
     return d, owner[:n]
 
 
-def linear_solve_ccs(n, Ap, Ai, Ax, b, block_dim=1, device=0):
-    """LinearSolver::solve on an upper-CCS matrix (LinearSolverCCS contract)."""
+# g2ohip_linear_solve_ccs_ex's info slots: the leading FACTOR_INFO_KEYS, then the deferred-L21 count
+CCS_INFO_KEYS = ("n", "nnzL", "flops", "supernodes", "levels", "max_front", "blocked_fronts", "inplace_levels",
+                 "prescatter_levels", "syrk_launches", "bwd_rounds", "deferred_l21_fronts")
+
+
+def linear_solve_ccs(n, Ap, Ai, Ax, b, block_dim=1, device=0, info=False):
+    """LinearSolver::solve on an upper-CCS matrix (LinearSolverCCS contract); info=True also returns the schedule
+    summary of the factorization (CCS_INFO_KEYS) as a dict: (ok, x, info)."""
     Ap = np.ascontiguousarray(Ap, np.int32)
     Ai = np.ascontiguousarray(Ai, np.int32)
     Ax = np.ascontiguousarray(Ax, np.float64)
@@ -254,9 +274,15 @@ def linear_solve_ccs(n, Ap, Ai, Ax, b, block_dim=1, device=0):
     x = np.zeros(n)
     nb = n // block_dim
     ends = np.arange(1, nb + 1, dtype=np.int32) * block_dim
-    r = lib().g2ohip_linear_solve_ccs(device, n, _p(Ap), _p(Ai), _p(Ax), _p(b), _p(x), nb, _p(ends))
+    if not info:
+        r = lib().g2ohip_linear_solve_ccs(device, n, _p(Ap), _p(Ai), _p(Ax), _p(b), _p(x), nb, _p(ends))
+        _check(r, "linear_solve_ccs")
+        return bool(r), x
+    out = np.zeros(len(CCS_INFO_KEYS))
+    r = lib().g2ohip_linear_solve_ccs_ex(device, n, _p(Ap), _p(Ai), _p(Ax), _p(b), _p(x), nb, _p(ends), _p(out),
+                                         len(out))
     _check(r, "linear_solve_ccs")
-    return bool(r), x
+    return bool(r), x, dict(zip(CCS_INFO_KEYS, out.tolist()))
 
 
 class SparseOptimizer:

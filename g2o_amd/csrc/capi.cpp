@@ -249,7 +249,12 @@ int g2ohip_stage(g2ohip_graph* g, double lambda, double* b, double* x, double* H
 
 int g2ohip_linear_solve_ccs(int device, int n, const int* Ap, const int* Ai, const double* Ax, const double* b,
                             double* x, int nblocks, const int* block_ends) {
-  if (n <= 0 || !Ap || !Ai || !Ax || !b || !x) return G2OHIP_ERR_ARG;
+  return g2ohip_linear_solve_ccs_ex(device, n, Ap, Ai, Ax, b, x, nblocks, block_ends, nullptr, 0);
+}
+
+int g2ohip_linear_solve_ccs_ex(int device, int n, const int* Ap, const int* Ai, const double* Ax, const double* b,
+                               double* x, int nblocks, const int* block_ends, double* info, int ninfo) {
+  if (n <= 0 || !Ap || !Ai || !Ax || !b || !x || ninfo < 0 || (ninfo > 0 && !info)) return G2OHIP_ERR_ARG;
   if (!gfx950_device(device)) return G2OHIP_ERR_DEVICE;
   return guarded([&]() -> int {
     // Uniform block partition required (BlockSolver<p,l> pose blocks); default 1x1 blocks.
@@ -292,6 +297,13 @@ int g2ohip_linear_solve_ccs(int device, int n, const int* Ap, const int* Ai, con
     {
       g2ohip::DeviceCholesky ch;
       ch.setup(nb, bd, bi, bj, s);
+      // the schedule setup chose, in the slot order of g2ohip_solver_factor_info's out[0..10], then its out[33]
+      const g2ohip::Symbolic& S = ch.sym;
+      const double v[] = {(double)S.n, (double)S.nnzL, S.flops, (double)S.sn.size(), (double)S.num_levels,
+                          (double)S.max_front, (double)ch.n_blocked, (double)ch.n_inplace_levels,
+                          (double)ch.n_pre_levels, (double)ch.n_syrk_ops, (double)ch.n_bwd_rounds,
+                          (double)ch.n_deferred_l21};
+      for (int k = 0; k < std::min(ninfo, (int)(sizeof v / sizeof v[0])); ++k) info[k] = v[k];
       g2ohip::DevBuf<double> dv, db, dx, dl;
       g2ohip::DevBuf<int> df;
       dv.upload(vals, s);
@@ -474,6 +486,27 @@ int g2ohip_symbolic_analyze(int nblocks, int bdim, int nblk, const int* bi, cons
       stats[4] = (double)lsteps;
     }
     return S.n;
+  } catch (const std::exception& ex) {
+    g_err = ex.what();
+    return G2OHIP_ERR_STATE;
+  }
+}
+
+int g2ohip_symbolic_supernodes(int nblocks, int bdim, int nblk, const int* bi, const int* bj, int* ns, int* nr,
+                               int* level, int cap) {
+  if (nblocks <= 0 || bdim <= 0 || nblk < 0 || (nblk > 0 && (!bi || !bj)) || cap < 0) return G2OHIP_ERR_ARG;
+  try {
+    for (int k = 0; k < nblk; ++k)
+      if (bi[k] < 0 || bj[k] < 0 || bi[k] >= nblocks || bj[k] >= nblocks) return G2OHIP_ERR_ARG;
+    g2ohip::Symbolic S = g2ohip::analyze(g2ohip::block_pattern(nblocks, bdim, std::vector<int>(bi, bi + nblk),
+                                                               std::vector<int>(bj, bj + nblk)));
+    const int m = (int)S.sn.size();
+    for (int k = 0; k < std::min(m, cap); ++k) {
+      if (ns) ns[k] = S.sn[k].ns;
+      if (nr) nr[k] = S.sn[k].nr;
+      if (level) level[k] = S.sn[k].level;
+    }
+    return m;
   } catch (const std::exception& ex) {
     g_err = ex.what();
     return G2OHIP_ERR_STATE;

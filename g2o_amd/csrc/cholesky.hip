@@ -150,7 +150,7 @@ __device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)
 // Returns false if a pivot was not positive (cs_chol's `d <= 0` test).
 // Latency-shaped for one wave, right-looking. The pivot chain runs on wave-uniform values only:
 // d_{j+1} = A(j+1,j+1) - (A(j+1,j) r_j)^2, both entries read by v_readlane one column early, so the
-// sequential chain per column is rsq -> Newton step -> r_j -> l_{j+1,j} -> d_{j+1}. Off the chain:
+// sequential chain per column is rsq -> third-order step -> r_j -> l_{j+1,j} -> d_{j+1}. Off the chain:
 // the scaled column l_j = row[j] r_j, its two-column look-ahead (l_{j+1,j}, l_{j+2,j} are chain
 // values, no broadcast), the rest of column j-1's rank-1 update (through LDS, one column late,
 // columns >= j+2), cut into chunks that sched_barriers pin between the chain's dependent steps.
@@ -181,20 +181,22 @@ __device__ __forceinline__ void c32_step(double (&row)[NB], int lane, double* co
   if constexpr (J < NB) {
     const double d = st.dn;
     st.ok &= d > 0.0;
-    const double r0 = __builtin_amdgcn_rsq(d);  // ~5e-8 relative; one Newton step -> ~4e-15
-    const double hd = 0.5 * d;
+    // ~5e-8 relative; one third-order step r = r0 (1 + h/2 + 3h^2/8), h = 1 - d r0^2, leaves h's own rounding
+    // (~1e-16). One Newton step (r0 (1.5 - d r0^2 / 2), one operation less) left -1.5e^2 ~ 4e-15, always low and
+    // different per column: forward errors up to 77 x LAPACK's (accuracy of the direct solver)
+    const double r0 = __builtin_amdgcn_rsq(d);
     CHOL_SB();
     c32_fill<J, 0>(row, st);
     CHOL_SB();
-    const double t1 = hd * r0;
+    const double t1 = d * r0;
     CHOL_SB();
     c32_fill<J, 1>(row, st);
     CHOL_SB();
-    const double t2 = __builtin_fma(-r0, t1, 1.5);
+    const double h = __builtin_fma(-r0, t1, 1.0);
     CHOL_SB();
     c32_fill<J, 2>(row, st);
     CHOL_SB();
-    const double r = r0 * t2;
+    const double r = __builtin_fma(r0 * h, __builtin_fma(0.375, h, 0.5), r0);
     const double l1 = st.b1 * r, l2 = st.c2 * r;  // l_{j+1,j}, l_{j+2,j}
     if constexpr (J + 1 < NB) st.dn = __builtin_fma(-l1, l1, st.a1);
     CHOL_SB();

@@ -7,6 +7,7 @@ CSparse reference path; the stage-level checks (reduced system, solution) use
 import numpy as np
 import pytest
 
+from chol_cases import upper_ccs
 from g2o_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -123,13 +124,7 @@ def _dense_spd_ccs(rng, n, density):
     mask = mask | mask.T
     A = rng.standard_normal((n, n)) * mask
     A = A @ A.T + n * np.eye(n)
-    Ap, Ai, Ax = [0], [], []
-    for j in range(n):
-        rows = np.nonzero(A[: j + 1, j])[0]
-        Ai += rows.tolist()
-        Ax += A[rows, j].tolist()
-        Ap.append(len(Ai))
-    return A, Ap, Ai, Ax
+    return (A, *upper_ccs(A))
 
 
 @pytest.mark.parametrize("pb,pre_max", [(64, "0"), (128, "1000000000000"), (256, "0")])

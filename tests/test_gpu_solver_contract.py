@@ -138,9 +138,13 @@ def test_write_debug_dump_on_not_pd(g2o_amd_mod, oracle, tmp_path, monkeypatch, 
         # Hll as packed 3x3 blocks: lambda just above -min eig keeps every Hll + lambda I PD, while the landmark with
         # the weakest direction inflates (Hll + lambda I)^-1 there and drives S + lambda I indefinite
         lam = -0.99 * float(np.linalg.eigvalsh(Hll.reshape(-1, 3, 3)).min())
+    # precondition, from the oracle on the CPU: the reduced system at this lambda is not positive definite by a margin
+    # no rounding can close (C1: every eigenvalue below -max diag; C4: lambda_min / lambda_max = -0.15)
+    ro = oracle.OracleGraph(prob).stage(lam)
+    ev = np.linalg.eigvalsh(ro["Hschur"])
+    assert ro["ok"] == 0 and ev[0] <= -1e-3 * abs(ev[-1]), (ev[0], ev[-1])
     r = opt.stage(lam)
-    if r["ok"]:
-        pytest.skip("lambda did not make the system indefinite")
+    assert r["ok"] == 0
     head, A, _ = _read_octave(str(tmp_path / "debug.txt"))
     assert head["name"] == "debug"
     S = r["Hschur"]
