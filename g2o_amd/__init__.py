@@ -39,6 +39,10 @@ class Config(C.Structure):
     _fields_ = [("max_trials_after_failure", C.c_int), ("user_lambda_init", C.c_double), ("verbose", C.c_int)]
 
 
+# EdgeStereoSE3ProjectXYZ (include/g2o_hip.h G2OHIP_E_STEREO_SE3_PROJECT_XYZ): meas u_l v u_r, params fx fy cx cy bf
+E_STEREO_SE3_PROJECT_XYZ = 6
+
+
 # edge types the device does not know: host-supplied error + Jacobians (include/g2o_hip.h G2OHIP_E_HOSTJ)
 def E_HOSTJ(D: int) -> int:
     return 32 + D

@@ -1,4 +1,5 @@
-// Fused bundle-adjustment assembly (graphs whose only edge type is EdgeSE3ProjectXYZ, BlockSolver_6_3 + Schur):
+// Fused bundle-adjustment assembly (graphs whose only edge type is EdgeSE3ProjectXYZ or EdgeStereoSE3ProjectXYZ,
+// BlockSolver_6_3 + Schur; the kernels are templates on the family, the Kt-record variants KX monocular only):
 // BlockSolver::buildSystem (block_solver.hpp:462-521) + BaseBinaryEdge::constructQuadraticForm
 // (base_binary_edge.hpp:61-137) without the per-edge slot round trip of the generic path.
 //
@@ -677,7 +678,7 @@ __global__ void __launch_bounds__(256)
                 const double* __restrict__ Ufac, const double* __restrict__ cl_all, int size_poses, int lm0,
                 double* __restrict__ x) {
   constexpr int D = F::D, DA = F::DA, DB = F::DB;
-  static_assert(DA == 3 && D == 2, "BA landmark blocks");
+  static_assert(DA == 3, "BA landmark blocks");
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int l = gid / LANES, q = gid % LANES;
   const bool active = l < nl;
@@ -742,13 +743,27 @@ __global__ void __launch_bounds__(256)
 }
 
 namespace launch {
-void linearize_fused(const EdgeArgs& a, const int4* chunks, int nchunks, const int* h0, const int* h1,
+void linearize_fused(int family, const EdgeArgs& a, const int4* chunks, int nchunks, const int* h0, const int* h1,
                      const long long* off_dst, const unsigned char* off_tr, double* off_base, double* off_slot,
                      double* Hll, double* b, int num_poses, int size_poses, int lm_begin, double* lpart,
                      const SchurSplit* sp, hipStream_t s) {
   if (nchunks <= 0) return;
   const EdgeData d{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, a.rk, a.rk_delta, a.ue};
   const SchurSplit z = sp ? *sp : SchurSplit{};
+  if (family == FAM_BA_STEREO) {  // G blocks only: the Kt record encodes the D = 2 geometry
+    if (sp && sp->kx) throw std::runtime_error("linearize_fused: Kt records are monocular only");
+    if (sp)
+      hipLaunchKernelGGL((k_linearize_fused<FamilyStereo, true, false>), grid_for(nchunks, 4), 256, 0, s, d, chunks,
+                         nchunks, h0, h1, off_dst, off_tr, off_base, off_slot, Hll, b, num_poses, size_poses, lm_begin,
+                         lpart, z);
+    else
+      hipLaunchKernelGGL((k_linearize_fused<FamilyStereo, false, false>), grid_for(nchunks, 4), 256, 0, s, d, chunks,
+                         nchunks, h0, h1, off_dst, off_tr, off_base, off_slot, Hll, b, num_poses, size_poses, lm_begin,
+                         lpart, z);
+    KERNEL_CHECK();
+    return;
+  }
+  if (family != FAM_BA) throw std::runtime_error("linearize_fused: not a bundle-adjustment edge family");
   if (sp && sp->kx)
     hipLaunchKernelGGL((k_linearize_fused<FamilyBA, true, true>), grid_for(nchunks, 4), 256, 0, s, d, chunks, nchunks, h0,
                        h1, off_dst, off_tr, off_base, off_slot, Hll, b, num_poses, size_poses, lm_begin, lpart, z);
@@ -775,26 +790,36 @@ void lm_fixup(int nfix, const int4* fix, const double* lpart, double* Hll, doubl
                        size_poses, lm_begin, z);
   KERNEL_CHECK();
 }
-void backsub_j(const EdgeArgs& a, int nl, const int2* erng, const int* hcam, const double* Ufac, const double* cl_all,
-               int size_poses, int lm0, double* x, hipStream_t s) {
+template <class F>
+static void backsub_j_lanes(int lanes, const EdgeData& d, int nl, const int2* erng, const int* hcam, const double* Ufac,
+                            const double* cl_all, int size_poses, int lm0, double* x, hipStream_t s) {
+  if (lanes == 2)
+    hipLaunchKernelGGL((k_backsub_j<F, 2>), grid_for((size_t)nl * 2, 256), 256, 0, s, d, nl, erng, hcam, Ufac, cl_all,
+                       size_poses, lm0, x);
+  else if (lanes == 4)
+    hipLaunchKernelGGL((k_backsub_j<F, 4>), grid_for((size_t)nl * 4, 256), 256, 0, s, d, nl, erng, hcam, Ufac, cl_all,
+                       size_poses, lm0, x);
+  else if (lanes == 16)
+    hipLaunchKernelGGL((k_backsub_j<F, 16>), grid_for((size_t)nl * 16, 256), 256, 0, s, d, nl, erng, hcam, Ufac, cl_all,
+                       size_poses, lm0, x);
+  else
+    hipLaunchKernelGGL((k_backsub_j<F, 8>), grid_for((size_t)nl * 8, 256), 256, 0, s, d, nl, erng, hcam, Ufac, cl_all,
+                       size_poses, lm0, x);
+}
+void backsub_j(int family, const EdgeArgs& a, int nl, const int2* erng, const int* hcam, const double* Ufac,
+               const double* cl_all, int size_poses, int lm0, double* x, hipStream_t s) {
   if (nl <= 0) return;
   const EdgeData d{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, a.rk, a.rk_delta, a.ue};
   // lanes per landmark (dev A/B G2OHIP_BACKSUB_J_LANES; profiles/r04_ab_backsub_lanes.log): 4 against 8 / 16, C5
   // 224.7-225.3 -> 227.5-227.6 / 222.6 LM it/s; 2 against 4, C5 225.0-225.1 -> 226.0-226.3, C4 907.5 -> 912.4
   static EnvKnob lanes_k{"G2OHIP_BACKSUB_J_LANES", 2};
   const int lanes = lanes_k.get();
-  if (lanes == 2)
-    hipLaunchKernelGGL((k_backsub_j<FamilyBA, 2>), grid_for((size_t)nl * 2, 256), 256, 0, s, d, nl, erng, hcam, Ufac,
-                       cl_all, size_poses, lm0, x);
-  else if (lanes == 4)
-    hipLaunchKernelGGL((k_backsub_j<FamilyBA, 4>), grid_for((size_t)nl * 4, 256), 256, 0, s, d, nl, erng, hcam, Ufac,
-                       cl_all, size_poses, lm0, x);
-  else if (lanes == 16)
-    hipLaunchKernelGGL((k_backsub_j<FamilyBA, 16>), grid_for((size_t)nl * 16, 256), 256, 0, s, d, nl, erng, hcam, Ufac,
-                       cl_all, size_poses, lm0, x);
+  if (family == FAM_BA_STEREO)
+    backsub_j_lanes<FamilyStereo>(lanes, d, nl, erng, hcam, Ufac, cl_all, size_poses, lm0, x, s);
+  else if (family == FAM_BA)
+    backsub_j_lanes<FamilyBA>(lanes, d, nl, erng, hcam, Ufac, cl_all, size_poses, lm0, x, s);
   else
-    hipLaunchKernelGGL((k_backsub_j<FamilyBA, 8>), grid_for((size_t)nl * 8, 256), 256, 0, s, d, nl, erng, hcam, Ufac,
-                       cl_all, size_poses, lm0, x);
+    throw std::runtime_error("backsub_j: not a bundle-adjustment edge family");
   KERNEL_CHECK();
 }
 
@@ -805,11 +830,26 @@ static bool cam_nt() {
   static EnvKnob k{"G2OHIP_CAM_NT", 1};
   return k.get() != 0;
 }
-void cam_assemble(const EdgeArgs& a, const int* cm_ptr, int npose, double* Hpp, double* b, int num_poses, int lm_begin,
-                  const SchurSplit* sp, hipStream_t s, const int* cams) {
+void cam_assemble(int family, const EdgeArgs& a, const int* cm_ptr, int npose, double* Hpp, double* b, int num_poses,
+                  int lm_begin, const SchurSplit* sp, hipStream_t s, const int* cams) {
   if (npose <= 0) return;
   const EdgeData d{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, a.rk, a.rk_delta, a.ue};
   const SchurSplit z = sp ? *sp : SchurSplit{};
+  if (family == FAM_BA_STEREO) {  // always the recomputing pass (no Kt records)
+    if (sp && sp->kx) throw std::runtime_error("cam_assemble: Kt records are monocular only");
+    if (sp && cam_nt())
+      hipLaunchKernelGGL((k_cam_assemble<FamilyStereo, true, false, true>), npose, 256, 0, s, d, cm_ptr, cams, npose,
+                         Hpp, b, num_poses, lm_begin, z);
+    else if (sp)
+      hipLaunchKernelGGL((k_cam_assemble<FamilyStereo, true, false, false>), npose, 256, 0, s, d, cm_ptr, cams, npose,
+                         Hpp, b, num_poses, lm_begin, z);
+    else
+      hipLaunchKernelGGL((k_cam_assemble<FamilyStereo, false, false, false>), npose, 256, 0, s, d, cm_ptr, cams, npose,
+                         Hpp, b, num_poses, lm_begin, z);
+    KERNEL_CHECK();
+    return;
+  }
+  if (family != FAM_BA) throw std::runtime_error("cam_assemble: not a bundle-adjustment edge family");
   if (sp && sp->kx && sp->cm_hpl)
     hipLaunchKernelGGL((k_cam_assemble<FamilyBA, true, true>), npose, 256, 0, s, d, cm_ptr, cams, npose, Hpp, b, num_poses,
                        lm_begin, z);

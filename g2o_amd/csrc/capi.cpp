@@ -100,6 +100,14 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
   if (!g || !path) return G2OHIP_ERR_ARG;
+  // the reference's EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP reader / writer is unusable (types_six_dof_expmap.cpp:469-493:
+  // four measurement values through a 3-vector, no intrinsics): a file without these edges would not be the graph
+  if (const auto* es = g->e->hg.set_of(G2OHIP_E_STEREO_SE3_PROJECT_XYZ); es && !es->ev0.empty()) {
+    g_err = "g2ohip_save_g2o: the graph holds " + std::to_string(es->ev0.size()) +
+            " EdgeStereoSE3ProjectXYZ edges, which the .g2o format cannot carry (the reference's reader and writer "
+            "for the tag drop the intrinsics and misread the measurement)";
+    return G2OHIP_ERR_UNSUPPORTED;
+  }
   return guarded([&] { return g->e->save(path); });
 }
 int g2ohip_num_vertices(g2ohip_graph* g) { return g ? (int)g->e->hg.verts.size() : G2OHIP_ERR_ARG; }

@@ -1,6 +1,7 @@
 // Device-side vertex/edge math for the three edge families on the BlockSolver path.
 //
 //   EdgeSE3ProjectXYZ  types/sba/types_six_dof_expmap.h:201-229, .cpp:395-455
+//   EdgeStereoSE3ProjectXYZ  types/sba/types_six_dof_expmap.h:262-290, .cpp:457-464, 495-541
 //   EdgeSE3 (QUAT)     types/slam3d/edge_se3.cpp:77-103, isometry3d_gradients.h:194-260
 //   EdgeSE2            types/slam2d/edge_se2.h:46-52, edge_se2.cpp:77-103
 //   EdgeSE2PointXY     types/slam2d/edge_se2_pointxy.h:41-75, edge_se2_pointxy.cpp:63-87
@@ -237,7 +238,7 @@ struct EdgeData {
   const int* v1;
   const double* meas;       // per-edge measurement payload (family-specific stride; host-J: e | Ji | Jj)
   const double* info;       // packed upper information (family-specific stride)
-  const double* params;     // BA intrinsics [4] or nullptr
+  const double* params;     // BA intrinsics [4] (stereo: [5], + bf) or nullptr
   const double* s0;         // state array of vertex-0 type
   const double* s1;         // state array of vertex-1 type
   int rk;                   // robust kernel of the edge set (G2OHIP_RK_*), 0 none
@@ -399,6 +400,90 @@ struct FamilyBA {
     B[9] = 0;
     B[10] = -1. / z * fy;
     B[11] = y / z2 * fy;
+  }
+};
+
+// ---- EdgeStereoSE3ProjectXYZ: v0 = point (3), v1 = camera SE3Quat (6); meas u_l v u_r, info packed upper 6,
+// intrinsics fx fy cx cy bf (stride 5) ----
+struct FamilyStereo {
+  static constexpr int D = 3, DA = 3, DB = 6, MEAS = 3, INFO = 6, PAR = 5;
+  static constexpr int S0 = 3, S1 = 8;  // state strides
+  // the point in the camera frame (SE3Quat::map)
+  DI static void to_camera(const EdgeData& d, int v0, int v1, double* q, double* pc) {
+    const double* c = d.s1 + (size_t)v1 * 8;
+    const double* p = d.s0 + (size_t)v0 * 3;
+    q[0] = c[3]; q[1] = c[4]; q[2] = c[5]; q[3] = c[6];
+    const double pv[3] = {p[0], p[1], p[2]};
+    qrot(q, pv, pc);
+    pc[0] += c[0]; pc[1] += c[1]; pc[2] += c[2];
+  }
+  // obs - cam_project (types_six_dof_expmap.cpp:457-464), in its operation order. cam_project takes bf as
+  // `const float&` (types_six_dof_expmap.h:287): the error sees bf rounded to float, the Jacobians the double.
+  // No contraction here: the projection rounds as the reference's does, operation by operation.
+  DI static void residual(const double* K, const double* pc, double m0, double m1, double m2, double* err) {
+#pragma clang fp contract(off)
+    const double invz = 1.0 / pc[2];
+    const double bf_f = (double)(float)K[4];
+    const double u = pc[0] * invz * K[0] + K[2];
+    const double v = pc[1] * invz * K[1] + K[3];
+    const double ur = u - bf_f * invz;
+    err[0] = m0 - u;
+    err[1] = m1 - v;
+    err[2] = m2 - ur;
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double q[4], pc[3];
+    to_camera(d, d.v0[e], d.v1[e], q, pc);
+    const double* m = d.meas + (size_t)e * 3;
+    residual(param_rec(d, e, PAR), pc, m[0], m[1], m[2], err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A, double* B) {
+    double pc[3];
+    linearize(d, e, err, A, B, pc);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A, double* B, double* pc) {
+    linearize_at(d, e, d.v0[e], d.v1[e], err, A, B, pc);
+  }
+  // the edge's vertex indices given; NT: the measurement is read nontemporally (as FamilyBA::linearize_at)
+  template <bool NT = false>
+  DI static void linearize_at(const EdgeData& d, int e, int v0, int v1, double* err, double* A, double* B, double* pc) {
+    double q[4];
+    to_camera(d, v0, v1, q, pc);
+    const double* K = param_rec(d, e, PAR);
+    const double* mp = d.meas + (size_t)e * 3;
+    const double m0 = NT ? __builtin_nontemporal_load(mp) : mp[0];
+    const double m1 = NT ? __builtin_nontemporal_load(mp + 1) : mp[1];
+    const double m2 = NT ? __builtin_nontemporal_load(mp + 2) : mp[2];
+    residual(K, pc, m0, m1, m2, err);
+    const double fx = K[0], fy = K[1], bf = K[4];
+    const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z;
+    double R[9];
+    quat_to_R(q[0], q[1], q[2], q[3], R);
+    // linearizeOplus, types_six_dof_expmap.cpp:509-540, in its expression forms
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) {
+      A[cc] = -fx * R[cc] / z + fx * x * R[6 + cc] / z_2;
+      A[3 + cc] = -fy * R[3 + cc] / z + fy * y * R[6 + cc] / z_2;
+      A[6 + cc] = A[cc] - bf * R[6 + cc] / z_2;
+    }
+    B[0] = x * y / z_2 * fx;
+    B[1] = -(1 + (x * x / z_2)) * fx;
+    B[2] = y / z * fx;
+    B[3] = -1. / z * fx;
+    B[4] = 0;
+    B[5] = x / z_2 * fx;
+    B[6] = (1 + y * y / z_2) * fy;
+    B[7] = -x * y / z_2 * fy;
+    B[8] = -x / z * fy;
+    B[9] = 0;
+    B[10] = -1. / z * fy;
+    B[11] = y / z_2 * fy;
+    B[12] = B[0] - bf * y / z_2;
+    B[13] = B[1] + bf * x / z_2;
+    B[14] = B[2];
+    B[15] = B[3];
+    B[16] = 0;
+    B[17] = B[5] - bf / z_2;
   }
 };
 

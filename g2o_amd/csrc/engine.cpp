@@ -48,11 +48,16 @@ int vertex_state_stride(int t) {
 static bool is_hostj(int e) { return e > G2OHIP_E_HOSTJ(0) && e <= G2OHIP_E_HOSTJ(6); }
 int edge_dim(int e) {
   if (is_hostj(e)) return e - G2OHIP_E_HOSTJ(0);
+  if (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ) return 3;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 6 : (e == G2OHIP_E_SE2 ? 3 : -1));
 }
 int edge_meas_dim(int e) {
   if (is_hostj(e)) return 0;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
+}
+// doubles of an edge type's per-edge parameter record (camera intrinsics): fx fy cx cy, stereo + bf
+int edge_param_dim(int e) {
+  return e == G2OHIP_E_SE3_PROJECT_XYZ ? 4 : (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ ? 5 : 0);
 }
 
 // ------------------------------------------------------------------ host-side math for I/O
@@ -1160,7 +1165,8 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
                       const double* params) {
   const int D = edge_dim(type);
   if (D < 0 || n < 0) return G2OHIP_ERR_ARG;
-  if (type == G2OHIP_E_SE3_PROJECT_XYZ && !params) return G2OHIP_ERR_ARG;
+  const int np = edge_param_dim(type);
+  if (np > 0 && !params) return G2OHIP_ERR_ARG;
   const int nm = edge_meas_dim(type);
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
@@ -1179,7 +1185,7 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   }
   if (nm > 0) es->meas.insert(es->meas.end(), meas, meas + (size_t)n * nm);
   es->info.insert(es->info.end(), info, info + (size_t)n * D * D);
-  if (type == G2OHIP_E_SE3_PROJECT_XYZ) es->params.insert(es->params.end(), params, params + (size_t)n * 4);
+  if (np > 0) es->params.insert(es->params.end(), params, params + (size_t)n * np);
   es->payload.clear();
   initialized = false;
   return G2OHIP_OK;
@@ -1659,9 +1665,11 @@ int Engine::minimal_state(double* out) {
 
 // ------------------------------------------------------------------ Engine: structure
 // device family of an edge type (host-J types: any endpoint vertex types)
+static bool is_ba_family(int fam) { return fam == FAM_BA || fam == FAM_BA_STEREO; }
 static int family_of(int etype, int& vtA, int& vtB) {
   switch (etype) {
     case G2OHIP_E_SE3_PROJECT_XYZ: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA;
+    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA_STEREO;
     case G2OHIP_E_SE3_QUAT: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3;
     case G2OHIP_E_SE2: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2;
     case G2OHIP_E_SE2_XY: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY;
@@ -1887,11 +1895,11 @@ void Engine::setup_edges_device() {
       ne += g.ne;
     }
   }
-  // fused BA assembly: the only edge group is BA and the Schur complement is formed (G2OHIP_ASM_FUSED=0 keeps the
-  // generic slot path, for A/B checks)
+  // fused BA assembly: the only edge group is BA (monocular or stereo) and the Schur complement is formed
+  // (G2OHIP_ASM_FUSED=0 keeps the generic slot path, for A/B checks)
   {
     const char* fz = getenv("G2OHIP_ASM_FUSED");
-    ba_fused = do_schur && groups.size() == 1 && groups[0].family == FAM_BA && !(fz && atoi(fz) == 0);
+    ba_fused = do_schur && groups.size() == 1 && is_ba_family(groups[0].family) && !(fz && atoi(fz) == 0);
   }
   if (ba_fused) {  // landmark-major edge order (stable: per landmark, the given order)
     EGroup& g = groups[0];
@@ -1903,18 +1911,21 @@ void Engine::setup_edges_device() {
     const int D = g.D, nm = es.nm, gne = g.ne;
     std::vector<int> v0(std::max(gne, 1), 0), v1(std::max(gne, 1), 0);
     const int minfo = D * (D + 1) / 2;
-    const int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY ? 2 : (g.family == FAM_SE3 ? 12 : (g.family == FAM_SE2 ? 3 : 0));
+    const int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY
+                          ? 2
+                          : (g.family == FAM_SE3 ? 12 : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO ? 3 : 0));
+    const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type) : 0;
     std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
-        params(g.family == FAM_BA ? (size_t)gne * 4 : 1);
+        params(mpar ? (size_t)gne * mpar : 1);
     for (int k = 0; k < gne; ++k) {
       const int e = g.edges[k];
       v0[k] = hg.verts[es.ev0[e]].local;
       v1[k] = hg.verts[es.ev1[e]].local;
       const double* m = es.meas.data() + (size_t)e * nm;
       double* mo = meas.data() + (size_t)k * mmeas;
-      if (g.family == FAM_BA) {
-        mo[0] = m[0]; mo[1] = m[1];
-        for (int j = 0; j < 4; ++j) params[(size_t)k * 4 + j] = es.params[(size_t)e * 4 + j];
+      if (is_ba_family(g.family)) {
+        for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+        for (int j = 0; j < mpar; ++j) params[(size_t)k * mpar + j] = es.params[(size_t)e * mpar + j];
       } else if (g.family == FAM_SE3) {  // edge_se3.cpp:42-50: normalise q, Z = fromVectorQT, store Z^-1
         double q[4] = {m[3], m[4], m[5], m[6]};
         const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
@@ -1945,14 +1956,14 @@ void Engine::setup_edges_device() {
        // record instead of 24 + 32 bytes per edge (G2OHIP_UNIFORM_RECORDS=0 keeps per-edge records, A/B)
       const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
       g.ue = 0;
-      if (g.family == FAM_BA && gne > 1 && !(ev && atoi(ev) == 0)) {
+      if (is_ba_family(g.family) && gne > 1 && !(ev && atoi(ev) == 0)) {
         auto uniform = [&](const std::vector<double>& v, int st) {
           for (int k = 1; k < gne; ++k)
             if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
           return true;
         };
         if (uniform(info, minfo)) { g.ue |= 1; info.resize(minfo); }
-        if (uniform(params, 4)) { g.ue |= 2; params.resize(4); }
+        if (uniform(params, mpar)) { g.ue |= 2; params.resize(mpar); }
       }
     }
     g.info.upload(info, stream);
@@ -2030,6 +2041,8 @@ void Engine::setup_edges_device() {
     }
     std::vector<int> ptr(num_poses + 1, 0), cv0, cv1;
     std::vector<double> cmeas, cinfo, cpar;
+    // per observation: D measurement doubles (2, stereo 3), the packed information, the intrinsics (4, stereo 5)
+    const int cD = g.D, cI = cD * (cD + 1) / 2, cP = edge_param_dim(es.type);
     cm_e_h.clear();
     for (int i = 0; i < num_poses; ++i) {
       ptr[i + 1] = ptr[i] + (int)lists[i].size();
@@ -2038,17 +2051,15 @@ void Engine::setup_edges_device() {
         const int e = g.edges[k];
         cv0.push_back(hg.verts[es.ev0[e]].local);
         cv1.push_back(hg.verts[es.ev1[e]].local);
-        cmeas.push_back(es.meas[(size_t)e * 2]);
-        cmeas.push_back(es.meas[(size_t)e * 2 + 1]);
-        const double* I = es.info.data() + (size_t)e * 4;
-        cinfo.push_back(I[0]);  // packed upper, column-major: (0,0) (0,1) (1,1)
-        cinfo.push_back(I[1]);
-        cinfo.push_back(I[3]);
-        for (int j = 0; j < 4; ++j) cpar.push_back(es.params[(size_t)e * 4 + j]);
+        for (int j = 0; j < cD; ++j) cmeas.push_back(es.meas[(size_t)e * cD + j]);
+        const double* I = es.info.data() + (size_t)e * cD * cD;
+        for (int c = 0; c < cD; ++c)  // packed upper, column-major: (0,0) (0,1) (1,1) ...
+          for (int r = 0; r <= c; ++r) cinfo.push_back(I[r * cD + c]);
+        for (int j = 0; j < cP; ++j) cpar.push_back(es.params[(size_t)e * cP + j]);
       }
     }
     auto nz_i = [](std::vector<int>& v) -> std::vector<int>& { if (v.empty()) v.push_back(0); return v; };
-    auto nz_d = [](std::vector<double>& v) -> std::vector<double>& { if (v.empty()) v.assign(4, 0.0); return v; };
+    auto nz_d = [](std::vector<double>& v) -> std::vector<double>& { if (v.empty()) v.assign(6, 0.0); return v; };
     cm_ptr_h = ptr;
     {  // per local landmark its edge range in the (landmark-major) group order
       const int lm_b = local_lm.empty() ? 0 : local_lm.front();
@@ -2070,8 +2081,8 @@ void Engine::setup_edges_device() {
     cm_v0.upload(nz_i(cv0), stream);
     cm_v1.upload(nz_i(cv1), stream);
     cm_meas.upload(nz_d(cmeas), stream);
-    if ((g.ue & 1) && cinfo.size() > 3) cinfo.resize(3);  // the shared record (see the group's upload)
-    if ((g.ue & 2) && cpar.size() > 4) cpar.resize(4);
+    if ((g.ue & 1) && (int)cinfo.size() > cI) cinfo.resize(cI);  // the shared record (see the group's upload)
+    if ((g.ue & 2) && (int)cpar.size() > cP) cpar.resize(cP);
     cm_info.upload(nz_d(cinfo), stream);
     cm_params.upload(nz_d(cpar), stream);
   }
@@ -2881,7 +2892,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
       // the Kt-record set (BA split; decided with the split below): another block size needs its own batches
       kx_sb = kx_batch_size();
       nsch_tasks_kx = nsch_groups_kx = 0;
-      if (kx_sb != SB && ba_fused && pd == 6 && ld == 3) {
+      if (kx_sb != SB && ba_fused && groups[0].family == FAM_BA && pd == 6 && ld == 3) {
         BatchSet bs;
         build_batches(kx_sb, bs, true);
         nsch_tasks_kx = (int)bs.tasks.size();
@@ -2925,11 +2936,13 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
       // (G2OHIP_BACKSUB_RECOMPUTE=0) needs G.
       const char* kx = getenv("G2OHIP_SCHUR_KX");
       const char* bsr = getenv("G2OHIP_BACKSUB_RECOMPUTE");
-      fz_kx = fz_split_ok && !(kx && atoi(kx) == 0) && !(bsr && atoi(bsr) == 0);
+      // (the record encodes the monocular D = 2 geometry: stereo graphs store G and take the G-block row pass)
+      fz_kx = fz_split_ok && groups[0].family == FAM_BA && !(kx && atoi(kx) == 0) && !(bsr && atoi(bsr) == 0);
       fz_lambda = std::numeric_limits<double>::quiet_NaN();
     }
     if (use_cgls()) {  // the fork's JacobiSolver_6_3: CGLS on J, no reduced system to factor
-      if (!ba_fused || nranks > 1) throw DeviceError("lm_pcg6_3_eigen needs a single-GPU graph of BA edges only");
+      if (!ba_fused || groups[0].family != FAM_BA || nranks > 1)
+        throw DeviceError("lm_pcg6_3_eigen needs a single-GPU graph of BA edges only");
       const EGroup& g = groups[0];
       const HEdgeSet& es = hg.esets[g.set];
       std::vector<int> ecam(g.ne), ept(g.ne);
@@ -3124,9 +3137,9 @@ int Engine::build_system_split(double lambda, const double* lamp) {  // block_so
       fz_lambda = lamp ? std::numeric_limits<double>::infinity() : lambda;
     }
     timer.begin("linearize", stream);
-    launch::linearize_fused(group_args(g), fz_chunks.get(), fz_nchunks, d_hidx[g.vtA].get(), d_hidx[g.vtB].get(),
-                            g.off_dst.get(), g.off_tr.get(), dH.get(), doffslot.get(), dHll.get(), db.get(), num_poses,
-                            size_poses, lm_begin, fz_lpart.get(), split ? &sp : nullptr, stream);
+    launch::linearize_fused(g.family, group_args(g), fz_chunks.get(), fz_nchunks, d_hidx[g.vtA].get(),
+                            d_hidx[g.vtB].get(), g.off_dst.get(), g.off_tr.get(), dH.get(), doffslot.get(), dHll.get(),
+                            db.get(), num_poses, size_poses, lm_begin, fz_lpart.get(), split ? &sp : nullptr, stream);
     timer.end(stream);
     for (const OffRed& R : offred)
       launch::offblock_reduce(R.nb, R.bsz, R.ptr.get(), R.soff.get(), doffslot.get(), dH.get(), R.dst.get(), stream);
@@ -3141,11 +3154,11 @@ int Engine::build_system_split(double lambda, const double* lamp) {  // block_so
     ca.info = cm_info.get();
     ca.params = cm_params.get();
     if (split && ncam_list > 0)  // a sharded rank's split pass: only the cameras it needs (the rest stay zero)
-      launch::cam_assemble(ca, cm_ptr.get(), ncam_list, dH.get(), db.get(), num_poses, lm_begin, &sp, stream,
-                           d_cam_list.get());
+      launch::cam_assemble(g.family, ca, cm_ptr.get(), ncam_list, dH.get(), db.get(), num_poses, lm_begin, &sp,
+                           stream, d_cam_list.get());
     else
-      launch::cam_assemble(ca, cm_ptr.get(), num_poses, dH.get(), db.get(), num_poses, lm_begin, split ? &sp : nullptr,
-                           stream);
+      launch::cam_assemble(g.family, ca, cm_ptr.get(), num_poses, dH.get(), db.get(), num_poses, lm_begin,
+                           split ? &sp : nullptr, stream);
     timer.end(stream);
     if (use_cgls()) {  // JacobiSolver::buildSystem's J (jacobi_solver.hpp:479-700)
       timer.begin("cgls_jacobian", stream);
@@ -3288,8 +3301,8 @@ void Engine::solve_async(bool reset_fail) {  // block_solver.hpp:314-447
   const char* bsr = getenv("G2OHIP_BACKSUB_RECOMPUTE");
   const bool bs_recompute = !(bsr && atoi(bsr) == 0) || fz_kx;  // Kt records: no G to read
   if (split && bs_recompute && ld == 3 && pd == 6)
-    launch::backsub_j(group_args(groups[0]), nLloc, d_bs_erng.get(), d_hidx[groups[0].vtB].get(), dUfac.get(),
-                      dCl.get(), size_poses, lm_begin, dx.get(), stream);
+    launch::backsub_j(groups[0].family, group_args(groups[0]), nLloc, d_bs_erng.get(), d_hidx[groups[0].vtB].get(),
+                      dUfac.get(), dCl.get(), size_poses, lm_begin, dx.get(), stream);
   else if (split)
     launch::backsub_g(pd, ld, nLloc, d_lm_ptr.get(), d_blk_pose.get(), dG.get(), dUfac.get(), dCl.get(), size_poses,
                       lm_begin, dx.get(), stream);
@@ -3988,9 +4001,12 @@ double Engine::kernel_bytes(const std::string& name) const {
   if (name == "linearize") {  // BA groups: edge data read, the Hpl block written (+ both slots, generic path)
     double by = 0;
     for (const EGroup& g : groups)
-      if (g.family == FAM_BA)
-        by += g.ne * ((2 + 3 + 4) * 8.0 + 8 + (ba_fused ? 0.0 : 9.0 + 27.0) * 8 + ob) +
+      // measurement + packed information + intrinsics streamed per edge: 2 + 3 + 4 doubles, stereo 3 + 6 + 5
+      if (is_ba_family(g.family)) {
+        const int D = g.D, np = g.family == FAM_BA ? 4 : 5;
+        by += g.ne * ((D + D * (D + 1) / 2 + np) * 8.0 + 8 + (ba_fused ? 0.0 : 9.0 + 27.0) * 8 + ob) +
               (ba_fused ? local_lm.size() * 12 * 8.0 : 0.0);
+      }
     return by;
   }
   if (name == "backsub") return local_lm.size() * (3 * 8.0 * 2 + 72) + npl * (pb + 4) + size_poses * 8.0;

@@ -1513,6 +1513,7 @@ template <class Fn>
 static void family_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
   switch (family) {
     case FAM_BA: fn(FamilyBA{}); break;
+    case FAM_BA_STEREO: fn(FamilyStereo{}); break;
     case FAM_SE3: fn(FamilySE3{}); break;
     case FAM_SE2: fn(FamilySE2{}); break;
     case FAM_SE2XY: fn(FamilySE2XY{}); break;

@@ -7,7 +7,7 @@
 
 namespace g2ohip {
 
-enum Family { FAM_NONE = 0, FAM_BA = 1, FAM_SE3 = 2, FAM_SE2 = 3, FAM_HOSTJ = 4, FAM_SE2XY = 5 };
+enum Family { FAM_NONE = 0, FAM_BA = 1, FAM_SE3 = 2, FAM_SE2 = 3, FAM_HOSTJ = 4, FAM_SE2XY = 5, FAM_BA_STEREO = 6 };
 
 struct EdgeArgs {
   const int* v0;
@@ -60,18 +60,19 @@ struct SchurSplit {
   double* bschur;
   int* fail;             // landmark block not positive definite (informational, as k_schur_prep)
 };
-void linearize_fused(const EdgeArgs& a, const int4* chunks, int nchunks, const int* h0, const int* h1,
+// family: FAM_BA or FAM_BA_STEREO (the Kt-record variants, sp->kx, are FAM_BA only)
+void linearize_fused(int family, const EdgeArgs& a, const int4* chunks, int nchunks, const int* h0, const int* h1,
                      const long long* off_dst, const unsigned char* off_tr, double* off_base, double* off_slot,
                      double* Hll, double* b, int num_poses, int size_poses, int lm_begin, double* lpart,
                      const SchurSplit* sp, hipStream_t s);
 void lm_fixup(int nfix, const int4* fix, const double* lpart, double* Hll, double* b, int num_poses, int size_poses,
               int lm_begin, const SchurSplit* sp, hipStream_t s);
-void cam_assemble(const EdgeArgs& a, const int* cm_ptr, int npose, double* Hpp, double* b, int num_poses, int lm_begin,
-                  const SchurSplit* sp, hipStream_t s, const int* cams = nullptr);
+void cam_assemble(int family, const EdgeArgs& a, const int* cm_ptr, int npose, double* Hpp, double* b, int num_poses,
+                  int lm_begin, const SchurSplit* sp, hipStream_t s, const int* cams = nullptr);
 // back-substitution of the Schur split recomputing each observation's Jacobians (no G blocks read): per local landmark
 // its edge range erng (landmark-major group order), hcam = camera vertex -> hessian index (-1 fixed)
-void backsub_j(const EdgeArgs& a, int nl, const int2* erng, const int* hcam, const double* Ufac, const double* cl_all,
-               int size_poses, int lm0, double* x, hipStream_t s);
+void backsub_j(int family, const EdgeArgs& a, int nl, const int2* erng, const int* hcam, const double* Ufac,
+               const double* cl_all, int size_poses, int lm0, double* x, hipStream_t s);
 // Schur kernels for (pd, ld) = (6, 3) (BlockSolver_6_3) and (3, 2) (BlockSolver_3_2)
 void schur_prep(int ld, int nl, int lm0, const double* Hll, const double* bl_all, const double* lam, double* Dinv,
                 double* Ufac, double* cl_all, int* fail, hipStream_t s);

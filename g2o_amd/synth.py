@@ -15,6 +15,8 @@ Recipes:
   * ``ba``      - BAL-style bundle adjustment after ``g2o/examples/ba/ba_demo.cpp:86-300``
     (VERTEX_SE3:EXPMAP cameras, VERTEX_XYZ points, EDGE_SE3_PROJECT_XYZ:EXPMAP),
     each point observed by exactly k cameras of a window of W consecutive ones.
+  * ``ba_stereo`` - the same scene observed by a stereo rig (EdgeStereoSE3ProjectXYZ: u_l v u_r),
+    all observations or a fraction of them (a mixed monocular + stereo graph).
 """
 from __future__ import annotations
 
@@ -29,9 +31,10 @@ SEED = 20261015
 # vertex / edge type codes (include/g2o_hip.h)
 V_SE3_EXPMAP, V_XYZ, V_SE3_QUAT, V_SE2, V_XY = 1, 2, 3, 4, 5
 E_SE3_PROJECT_XYZ, E_SE3_QUAT, E_SE2, E_SE2_XY = 1, 2, 3, 5
+E_STEREO_SE3_PROJECT_XYZ = 6
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2}
-MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2}
-ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2}
+MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3}
+ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3}
 
 
 @dataclasses.dataclass
@@ -50,7 +53,7 @@ class EdgeSet:
     v1: np.ndarray      # int32 [n]
     meas: np.ndarray    # float64 [n, MEAS_DIM]
     info: np.ndarray    # float64 [n, D, D]
-    params: np.ndarray | None = None  # float64 [n, 4] (fx fy cx cy) for projection edges
+    params: np.ndarray | None = None  # float64 [n, 4] (fx fy cx cy) for projection edges, [n, 5] (+ bf) for stereo
 
 
 @dataclasses.dataclass
@@ -386,15 +389,10 @@ def _small_rot(rng, n, sigma):
     return _axis_angle(axis, ang)
 
 
-def ba(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point: int = 10, window: int = 64,
-       pixel_noise: float = 1.0, cam_rot_noise: float = 0.002, cam_trans_noise: float = 0.01,
-       point_noise: float = 0.05, fixed_cameras: int = 2, seed: int = SEED) -> Problem:
-    """BAL-style synthetic BA (config C4/C5).  Camera i sits at x = 0.04 i on a line
-    (ba_demo.cpp:216-231) with a small random attitude; every point is seen by
-    exactly ``obs_per_point`` distinct cameras drawn from a window of ``window``
-    consecutive cameras.  fx = fy = 1000, cx = 320, cy = 240, Omega = I2.
-    The first ``fixed_cameras`` cameras are fixed: one fixed camera leaves the
-    monocular scale unobservable (rank-deficient Schur system), two fix it."""
+def _ba_scene(num_cameras, num_points, obs_per_point, window, pixel_noise, cam_rot_noise, cam_trans_noise,
+              point_noise, fixed_cameras, seed):
+    """The scene of :func:`ba`: the problem and, per observation, the true point in its camera's frame and the true
+    (noise-free) projection.  Every random draw is ba()'s, in ba()'s order."""
     rng = _rng(seed, 3)
     C, P, k = num_cameras, num_points, obs_per_point
     W = min(window, C)
@@ -415,6 +413,7 @@ def ba(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point: int = 
     pflat = np.repeat(np.arange(P), k)
     pc = np.einsum("nij,nj->ni", Rw[cflat], pts[pflat]) + tw[cflat]
     uv = np.stack([pc[:, 0] / pc[:, 2] * fx + cx, pc[:, 1] / pc[:, 2] * fy + cy], axis=1)
+    uv_true = uv.copy()
     uv += rng.standard_normal(uv.shape) * pixel_noise
     # initial estimates
     dR = _small_rot(rng, C, cam_rot_noise)
@@ -434,7 +433,51 @@ def ba(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point: int = 
     info = np.broadcast_to(np.eye(2), (m, 2, 2)).copy()
     params = np.broadcast_to(np.array([fx, fy, cx, cy]), (m, 4)).copy()
     edges = EdgeSet(E_SE3_PROJECT_XYZ, pt_ids[pflat], cam_ids[cflat], uv, info, params)
-    return Problem(f"ba{C}x{P}k{k}w{W}", [cams_v, pts_v], [edges], 6, 3)
+    return Problem(f"ba{C}x{P}k{k}w{W}", [cams_v, pts_v], [edges], 6, 3), pc, uv_true
+
+
+def ba(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point: int = 10, window: int = 64,
+       pixel_noise: float = 1.0, cam_rot_noise: float = 0.002, cam_trans_noise: float = 0.01,
+       point_noise: float = 0.05, fixed_cameras: int = 2, seed: int = SEED) -> Problem:
+    """BAL-style synthetic BA (config C4/C5).  Camera i sits at x = 0.04 i on a line
+    (ba_demo.cpp:216-231) with a small random attitude; every point is seen by
+    exactly ``obs_per_point`` distinct cameras drawn from a window of ``window``
+    consecutive cameras.  fx = fy = 1000, cx = 320, cy = 240, Omega = I2.
+    The first ``fixed_cameras`` cameras are fixed: one fixed camera leaves the
+    monocular scale unobservable (rank-deficient Schur system), two fix it."""
+    return _ba_scene(num_cameras, num_points, obs_per_point, window, pixel_noise, cam_rot_noise, cam_trans_noise,
+                     point_noise, fixed_cameras, seed)[0]
+
+
+def ba_stereo(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point: int = 10, window: int = 64,
+              pixel_noise: float = 1.0, cam_rot_noise: float = 0.002, cam_trans_noise: float = 0.01,
+              point_noise: float = 0.05, fixed_cameras: int = 2, seed: int = SEED, bf: float = 100.3,
+              stereo_fraction: float = 1.0, disparity_noise: float = 1.0, info: np.ndarray | None = None) -> Problem:
+    """The scene of :func:`ba` (same arguments, same cameras, points, estimates and left-image measurements) seen by a
+    stereo rig: EdgeStereoSE3ProjectXYZ observations (u_l, v, u_r) with u_r = u_true - bf / z_true + noise, the noise
+    (sigma ``disparity_noise``) from an rng stream of its own.  params are fx fy cx cy bf; ``info`` is the 3x3
+    information of every stereo edge (default I3).  With ``stereo_fraction`` < 1 that fraction of the observations
+    (chosen at random, again from a stream of its own) is stereo and the rest stay monocular in a second EdgeSet: the
+    mixed graph of a stereo SLAM system's local BA.  A stereo rig observes the scale, so one fixed camera is enough."""
+    prob, pc, uv_true = _ba_scene(num_cameras, num_points, obs_per_point, window, pixel_noise, cam_rot_noise,
+                                  cam_trans_noise, point_noise, fixed_cameras, seed)
+    mono = prob.edges[0]
+    m = len(mono.v0)
+    ur = uv_true[:, 0] - bf / pc[:, 2] + _rng(seed, 5).standard_normal(m) * disparity_noise
+    if stereo_fraction >= 1.0:
+        st = np.ones(m, bool)
+    else:
+        st = _rng(seed, 6).random(m) < stereo_fraction
+    ns = int(st.sum())
+    meas = np.stack([mono.meas[st, 0], mono.meas[st, 1], ur[st]], axis=1)
+    om = np.eye(3) if info is None else np.asarray(info, np.float64).reshape(3, 3)
+    params = np.concatenate([mono.params[st], np.full((ns, 1), float(bf))], axis=1)
+    edges = [EdgeSet(E_STEREO_SE3_PROJECT_XYZ, mono.v0[st].copy(), mono.v1[st].copy(), meas,
+                     np.broadcast_to(om, (ns, 3, 3)).copy(), params)]
+    if ns < m:
+        edges.append(EdgeSet(E_SE3_PROJECT_XYZ, mono.v0[~st].copy(), mono.v1[~st].copy(), mono.meas[~st].copy(),
+                             mono.info[~st].copy(), mono.params[~st].copy()))
+    return Problem(prob.name + f"_stereo{stereo_fraction:g}", prob.vertices, edges, 6, 3)
 
 
 def by_name(name: str, scale: str = "full") -> Problem:

@@ -41,6 +41,13 @@ extern "C" {
 #define G2OHIP_E_SE2 3             /* EdgeSE2, edge_se2.h:46-52: meas x y theta; info 3x3 */
 #define G2OHIP_E_SE2_XY 5          /* EdgeSE2PointXY, edge_se2_pointxy.h:41-75: v0 SE2 pose, v1 XY point; meas x y;
                                       info 2x2 */
+#define G2OHIP_E_STEREO_SE3_PROJECT_XYZ 6 /* EdgeStereoSE3ProjectXYZ, types_six_dof_expmap.h:262-290: v0 point
+                                      (G2OHIP_V_XYZ), v1 camera (G2OHIP_V_SE3_EXPMAP); meas u_l v u_r; info 3x3; params
+                                      fx fy cx cy bf (n*5). As the reference's cam_project takes bf as a float
+                                      (:287), the error uses bf rounded to float, the Jacobians the double. A graph
+                                      whose only edge type this is takes the fused assembly, as a monocular one does;
+                                      with other types beside it (monocular edges, say) the generic one. Not carried by
+                                      .g2o files: see g2ohip_load_g2o / g2ohip_save_g2o */
 /* An edge type the device does not know (any BaseBinaryEdge<D, E, Vi, Vj> between registered vertices of
  * dimension 2, 3 or 6): the host's own linearizeOplus (the type's analytic one, or BaseBinaryEdge's numeric
  * central differences, base_binary_edge.hpp:198-266) supplies the error and both Jacobians, see
@@ -105,7 +112,12 @@ void g2ohip_graph_destroy(g2ohip_graph* g);
 int g2ohip_add_vertices(g2ohip_graph* g, int type, int n, const int* ids, const double* est, const int* fixed,
                         const int* marginalized);
 int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int* v1, const double* meas,
-                     const double* info /* n * D*D row-major */, const double* params /* n*4 or NULL */);
+                     const double* info /* n * D*D row-major */, const double* params /* n*4, stereo n*5, or NULL */);
+/* params: the intrinsics of the projection types (G2OHIP_ERR_ARG when one of them gets NULL), NULL for the others. */
+/* .g2o files do not carry G2OHIP_E_STEREO_SE3_PROJECT_XYZ: the reference's reader and writer for its tag
+ * (EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP, types_six_dof_expmap.cpp:469-493) move four measurement values through a
+ * 3-vector and no intrinsics. The loader skips the tag like any unknown one; g2ohip_save_g2o on a graph that holds
+ * such edges writes nothing and returns G2OHIP_ERR_UNSUPPORTED (g2ohip_last_error says why). */
 int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
