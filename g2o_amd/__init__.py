@@ -48,6 +48,18 @@ def E_HOSTJ(D: int) -> int:
     return 32 + D
 
 
+# unary edge types (BaseUnaryEdge; include/g2o_hip.h G2OHIP_E_*_PRIOR): EdgeSet.v1 is None
+E_SE2_PRIOR, E_SE2_XY_PRIOR, E_XY_PRIOR, E_SE3_PRIOR, E_XYZ_PRIOR = 16, 17, 18, 19, 20
+
+
+# any other BaseUnaryEdge: host-supplied error + Jacobian, payload [e | Ji] per edge (G2OHIP_E_HOSTJ_UNARY)
+def E_HOSTJ_UNARY(D: int) -> int:
+    return 48 + D
+
+
+# g2ohip_load_g2o_ex flags
+LOAD_UNARY = 1
+
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
       "Saturated": 8, "DCS": 9}
@@ -56,7 +68,7 @@ HOST_EDGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_
 
 EXPORTS = [
     "g2ohip_graph_create", "g2ohip_graph_destroy", "g2ohip_add_vertices", "g2ohip_add_edges",
-    "g2ohip_load_g2o", "g2ohip_save_g2o", "g2ohip_num_vertices", "g2ohip_num_edges",
+    "g2ohip_load_g2o", "g2ohip_load_g2o_ex", "g2ohip_save_g2o", "g2ohip_num_vertices", "g2ohip_num_edges",
     "g2ohip_set_robust_kernel", "g2ohip_set_host_jacobians", "g2ohip_set_host_edge_callback",
     "g2ohip_solver_diag_absmax", "g2ohip_solver_set_eta", "g2ohip_solver_linear_iterations",
     "g2ohip_get_estimates", "g2ohip_set_estimates", "g2ohip_minimal_state", "g2ohip_set_algorithm",
@@ -98,6 +110,7 @@ def lib() -> C.CDLL:
         "g2ohip_add_vertices": ([P, I, I, P, P, P, P], I),
         "g2ohip_add_edges": ([P, I, I, P, P, P, P, P], I),
         "g2ohip_load_g2o": ([P, C.c_char_p, I], I),
+        "g2ohip_load_g2o_ex": ([P, C.c_char_p, I, C.c_uint], I),
         "g2ohip_save_g2o": ([P, C.c_char_p], I),
         "g2ohip_num_vertices": ([P], I),
         "g2ohip_num_edges": ([P], I),
@@ -317,7 +330,7 @@ class SparseOptimizer:
 
     def add_edges(self, es):
         v0 = np.ascontiguousarray(es.v0, np.int32)
-        v1 = np.ascontiguousarray(es.v1, np.int32)
+        v1 = None if es.v1 is None else np.ascontiguousarray(es.v1, np.int32)  # None: a unary edge type
         meas = None if es.meas is None else np.ascontiguousarray(es.meas, np.float64)
         info = np.ascontiguousarray(es.info, np.float64)
         par = None if es.params is None else np.ascontiguousarray(es.params, np.float64)
@@ -354,7 +367,8 @@ class SparseOptimizer:
                 want = lib().g2ohip_host_payload_len(self.h, etype)
                 if want < 0 or pay.size != want:  # never write past the engine's payload buffer
                     raise G2OHipError(f"host edge callback returned {pay.size} doubles for edge type {etype}, "
-                                      f"expected {want} (D * (1 + dim(v0) + dim(v1)) per edge)")
+                                      f"expected {want} (D * (1 + dim(v0) + dim(v1)) per edge, unary: "
+                                      f"D * (1 + dim(v0)))")
                 C.memmove(out, pay.ctypes.data, pay.nbytes)
                 return 0
             except Exception:  # reported as a failed callback by the engine
@@ -370,8 +384,11 @@ class SparseOptimizer:
         est = np.ascontiguousarray(est, np.float64)
         _check(lib().g2ohip_set_estimates(self.h, vtype, _p(est)), "set_estimates")
 
-    def load(self, path: str, marginalize_xyz: bool = True):
-        _check(lib().g2ohip_load_g2o(self.h, path.encode(), int(marginalize_xyz)), "load")
+    def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False):
+        """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
+        EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), which are skipped otherwise."""
+        _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), LOAD_UNARY if unary else 0),
+               "load")
 
     def num_vertices(self) -> int:
         return int(lib().g2ohip_num_vertices(self.h))

@@ -24,6 +24,9 @@ template <class F>
 int guarded(F&& f) {
   try {
     return f();
+  } catch (const g2ohip::StatusError& ex) {
+    g_err = ex.what();
+    return ex.code;
   } catch (const std::exception& ex) {
     g_err = ex.what();
     return G2OHIP_ERR_DEVICE;
@@ -91,12 +94,16 @@ int g2ohip_add_vertices(g2ohip_graph* g, int type, int n, const int* ids, const 
 }
 int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int* v1, const double* meas,
                      const double* info, const double* params) {
-  if (!g || (n > 0 && (!v0 || !v1 || !info))) return G2OHIP_ERR_ARG;
+  if (!g || (n > 0 && (!v0 || !info))) return G2OHIP_ERR_ARG;  // v1: NULL for the unary types only (Engine::add_edges)
   return guarded([&] { return g->e->add_edges(type, n, v0, v1, meas, info, params); });
 }
 int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
   if (!g || !path) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz); });
+}
+int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
+  if (!g || !path || (flags & ~G2OHIP_LOAD_UNARY)) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
   if (!g || !path) return G2OHIP_ERR_ARG;

@@ -16,6 +16,12 @@ namespace g2ohip {
 struct DeviceError : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
+// a refusal with a reason: the C entry point returns `code` (G2OHIP_ERR_ARG, G2OHIP_ERR_UNSUPPORTED) and
+// g2ohip_last_error the message
+struct StatusError : std::runtime_error {
+  int code;
+  StatusError(int c, const std::string& what) : std::runtime_error(what), code(c) {}
+};
 
 #define HIP_CHECK(expr)                                                                                  \
   do {                                                                                                   \

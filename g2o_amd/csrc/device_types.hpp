@@ -5,7 +5,9 @@
 //   EdgeSE3 (QUAT)     types/slam3d/edge_se3.cpp:77-103, isometry3d_gradients.h:194-260
 //   EdgeSE2            types/slam2d/edge_se2.h:46-52, edge_se2.cpp:77-103
 //   EdgeSE2PointXY     types/slam2d/edge_se2_pointxy.h:41-75, edge_se2_pointxy.cpp:63-87
-//   oplus              types_six_dof_expmap.h:97-100 (SE3Quat::exp * T, se3quat.h:217-257),
+//   unary priors       types/slam2d/edge_se2_prior.h:39-77, edge_se2_xyprior.h:39-71, edge_xy_prior.h,
+//                      types/slam3d/edge_se3_prior.cpp:89-102 (isometry3d_gradients.h:265-325), edge_xyz_prior.cpp:63-70
+//   oplus             types_six_dof_expmap.h:97-100 (SE3Quat::exp * T, se3quat.h:217-257),
 //                      types_sba.h:149-153, vertex_se3.h:105-113, vertex_se2.h:51-58
 //
 // State layouts in HBM (fp64):
@@ -690,6 +692,161 @@ struct FamilyHostJ {
     for (int i = 0; i < D * DA; ++i) A[i] = p[D + i];
 #pragma unroll
     for (int i = 0; i < D * DB; ++i) B[i] = p[D + D * DA + i];
+  }
+};
+
+// ================================================================ unary edge families (BaseUnaryEdge, v0 only)
+// Each family: D, DA, MEAS (payload doubles per edge), INFO, error(d, e, err), linearize(d, e, err, A) with A the
+// Jacobian row-major (D x DA). v1 / s1 are not read.
+
+// ---- EdgeSE2Prior (edge_se2_prior.h:39-77): meas payload = inverse measurement (x y theta), info packed 6.
+// error = (Z^-1 * x).toVector(); J = [R(Z^-1) 0; 0 1] ----
+struct FamilyUnarySE2 {
+  static constexpr int D = 3, DA = 3, MEAS = 3, INFO = 6;
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* xi = d.s0 + (size_t)d.v0[e] * 3;
+    const double* mi = d.meas + (size_t)e * 3;
+    const double a[3] = {xi[0], xi[1], xi[2]}, m[3] = {mi[0], mi[1], mi[2]};
+    FamilySE2::compose(m, a, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
+    error(d, e, err);
+    const double th = d.meas[(size_t)e * 3 + 2];
+    const double rc = cos(th), rs = sin(th);
+    A[0] = rc; A[1] = -rs; A[2] = 0;
+    A[3] = rs; A[4] = rc;  A[5] = 0;
+    A[6] = 0;  A[7] = 0;   A[8] = 1.;
+  }
+};
+
+// ---- EdgeSE2XYPrior (edge_se2_xyprior.h:39-71, .cpp:60-63): error = translation - z, J = [I 0] ----
+struct FamilyUnarySE2XY {
+  static constexpr int D = 2, DA = 3, MEAS = 2, INFO = 3;
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* xi = d.s0 + (size_t)d.v0[e] * 3;
+    const double* m = d.meas + (size_t)e * 2;
+    err[0] = xi[0] - m[0];
+    err[1] = xi[1] - m[1];
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
+    error(d, e, err);
+    A[0] = 1; A[1] = 0; A[2] = 0;
+    A[3] = 0; A[4] = 1; A[5] = 0;
+  }
+};
+
+// ---- EdgeXYPrior (edge_xy_prior.h, .cpp) on a VertexPointXY, EdgeXYZPrior (edge_xyz_prior.cpp:63-70) on a point:
+// error = estimate - z, J = I ----
+template <int N>
+struct FamilyUnaryPoint {
+  static constexpr int D = N, DA = N, MEAS = N, INFO = N * (N + 1) / 2;
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* p = d.s0 + (size_t)d.v0[e] * N;
+    const double* m = d.meas + (size_t)e * N;
+#pragma unroll
+    for (int i = 0; i < N; ++i) err[i] = p[i] - m[i];
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
+    error(d, e, err);
+#pragma unroll
+    for (int i = 0; i < N * N; ++i) A[i] = (i % (N + 1) == 0) ? 1.0 : 0.0;
+  }
+};
+using FamilyUnaryXY = FamilyUnaryPoint<2>;
+using FamilyUnaryXYZ = FamilyUnaryPoint<3>;
+
+// ---- EdgeSE3Prior (edge_se3_prior.cpp:89-102): meas payload = [Z^-1 (12) | offset P (12)], info packed 21.
+// error = toVectorMQT(Z^-1 * (X * P)) (the cache's n2w = X * P); Jacobian computeEdgeSE3PriorGradient
+// (isometry3d_gradients.h:265-325, the gcc branch): A = Z^-1 X, B = P, E = A B ----
+struct FamilyUnarySE3 {
+  static constexpr int D = 6, DA = 6, MEAS = 24, INFO = 21;
+  DI static void load(const EdgeData& d, int e, double* X, double* Zi, double* P) {
+    const double* x = d.s0 + (size_t)d.v0[e] * 12;
+    const double* m = d.meas + (size_t)e * 24;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { X[k] = x[k]; Zi[k] = m[k]; P[k] = m[12 + k]; }
+  }
+  DI static void error_of(const double* X, const double* Zi, const double* P, double* err) {
+    double T[12], E[12];
+    iso_mul(X, P, T);
+    iso_mul(Zi, T, E);
+    err[0] = E[9]; err[1] = E[10]; err[2] = E[11];
+    compact_quat(E, err + 3);
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double X[12], Zi[12], P[12];
+    load(d, e, X, Zi, P);
+    error_of(X, Zi, P, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* J) {
+    double X[12], Zi[12], P[12], A[12], E[12];
+    load(d, e, X, Zi, P);
+    error_of(X, Zi, P, err);
+    iso_mul(Zi, X, A);
+    iso_mul(A, P, E);
+    const double* Ra = A;
+    const double* Rb = P;
+    double dq[27];
+    dq_dR(E, dq);
+#pragma unroll
+    for (int k = 0; k < 36; ++k) J[k] = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) J[r * 6 + c] = Ra[r * 3 + c];
+    {  // dte/dq = Ra * skew(tb)
+      const double x = 2 * P[9], y = 2 * P[10], z = 2 * P[11];
+      const double S[9] = {0, z, -y, -z, 0, x, y, -x, 0};
+      double M[9];
+      mat3mul(Ra, S, M);
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) J[r * 6 + 3 + c] = M[r * 3 + c];
+    }
+    {  // dre/dq = dq * [vec(Ra*Sx) vec(Ra*Sy) vec(Ra*Sz)], skew of Rb
+      const double r11 = 2 * Rb[0], r12 = 2 * Rb[1], r13 = 2 * Rb[2];
+      const double r21 = 2 * Rb[3], r22 = 2 * Rb[4], r23 = 2 * Rb[5];
+      const double r31 = 2 * Rb[6], r32 = 2 * Rb[7], r33 = 2 * Rb[8];
+      const double Sx[9] = {0, 0, 0, -r31, -r32, -r33, r21, r22, r23};
+      const double Sy[9] = {r31, r32, r33, 0, 0, 0, -r11, -r12, -r13};
+      const double Sz[9] = {-r21, -r22, -r23, r11, r12, r13, 0, 0, 0};
+      double Mx[9], My[9], Mz[9];
+      mat3mul(Ra, Sx, Mx);
+      mat3mul(Ra, Sy, My);
+      mat3mul(Ra, Sz, Mz);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        double s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {  // k: column-major index of the 3x3 -> (k%3, k/3)
+          const int rr = k % 3, cc = k / 3;
+          s0 += dq[r * 9 + k] * Mx[rr * 3 + cc];
+          s1 += dq[r * 9 + k] * My[rr * 3 + cc];
+          s2 += dq[r * 9 + k] * Mz[rr * 3 + cc];
+        }
+        J[(3 + r) * 6 + 3] = s0; J[(3 + r) * 6 + 4] = s1; J[(3 + r) * 6 + 5] = s2;
+      }
+    }
+  }
+};
+
+// ---- host-Jacobian unary edges (any other BaseUnaryEdge<D, E, V>): per edge [e (D) | Ji (D x DA)] row-major in the
+// meas payload, from the host's linearizeOplus (base_unary_edge.hpp:87-129 numeric, or the type's own) ----
+template <int D_, int DA_>
+struct FamilyHostJUnary {
+  static constexpr int D = D_, DA = DA_, INFO = D * (D + 1) / 2, P = D + D * DA, MEAS = P;
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* p = d.meas + (size_t)e * P;
+#pragma unroll
+    for (int i = 0; i < D; ++i) err[i] = p[i];
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
+    const double* p = d.meas + (size_t)e * P;
+#pragma unroll
+    for (int i = 0; i < D; ++i) err[i] = p[i];
+#pragma unroll
+    for (int i = 0; i < D * DA; ++i) A[i] = p[D + i];
   }
 };
 

@@ -45,19 +45,38 @@ int vertex_state_stride(int t) {
   }
   return 0;
 }
-static bool is_hostj(int e) { return e > G2OHIP_E_HOSTJ(0) && e <= G2OHIP_E_HOSTJ(6); }
+static bool is_hostj_binary(int e) { return e > G2OHIP_E_HOSTJ(0) && e <= G2OHIP_E_HOSTJ(6); }
+static bool is_hostj_unary(int e) { return e > G2OHIP_E_HOSTJ_UNARY(0) && e <= G2OHIP_E_HOSTJ_UNARY(6); }
+// host-Jacobian edge types of either arity
+static bool is_hostj(int e) { return is_hostj_binary(e) || is_hostj_unary(e); }
+// BaseUnaryEdge types: the five priors and the unary host-J escape
+static bool is_unary_type(int e) { return (e >= G2OHIP_E_SE2_PRIOR && e <= G2OHIP_E_XYZ_PRIOR) || is_hostj_unary(e); }
 int edge_dim(int e) {
-  if (is_hostj(e)) return e - G2OHIP_E_HOSTJ(0);
-  if (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ) return 3;
+  if (is_hostj_binary(e)) return e - G2OHIP_E_HOSTJ(0);
+  if (is_hostj_unary(e)) return e - G2OHIP_E_HOSTJ_UNARY(0);
+  switch (e) {
+    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: case G2OHIP_E_SE2_PRIOR: case G2OHIP_E_XYZ_PRIOR: return 3;
+    case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: return 2;
+    case G2OHIP_E_SE3_PRIOR: return 6;
+  }
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 6 : (e == G2OHIP_E_SE2 ? 3 : -1));
 }
 int edge_meas_dim(int e) {
   if (is_hostj(e)) return 0;
+  if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR) return 2;
+  if (e == G2OHIP_E_SE3_PRIOR) return 7;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
 }
-// doubles of an edge type's per-edge parameter record (camera intrinsics): fx fy cx cy, stereo + bf
+// doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
+// sensor offset x y z qx qy qz qw (optional: NULL = identity)
 int edge_param_dim(int e) {
+  if (e == G2OHIP_E_SE3_PRIOR) return 7;
   return e == G2OHIP_E_SE3_PROJECT_XYZ ? 4 : (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ ? 5 : 0);
+}
+static int family_of(int etype, int& vtA, int& vtB);
+// doubles of one host-J edge's payload: [e | Ji | Jj], a unary edge's [e | Ji]
+static size_t hostj_edge_len(const HostGraph& hg, const HEdgeSet& es, size_t k) {
+  return (size_t)es.D * (1 + hg.verts[es.ev0[k]].dim + (es.unary ? 0 : hg.verts[es.ev1[k]].dim));
 }
 
 // ------------------------------------------------------------------ host-side math for I/O
@@ -1165,12 +1184,14 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
                       const double* params) {
   const int D = edge_dim(type);
   if (D < 0 || n < 0) return G2OHIP_ERR_ARG;
+  const bool unary = is_unary_type(type);
+  if (unary != (v1 == nullptr) && (n > 0 || v1)) return G2OHIP_ERR_ARG;  // v1 is NULL for the unary types, only for them
   const int np = edge_param_dim(type);
-  if (np > 0 && !params) return G2OHIP_ERR_ARG;
+  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR) return G2OHIP_ERR_ARG;
   const int nm = edge_meas_dim(type);
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
-    if (!hg.idmap.count(v0[k]) || !hg.idmap.count(v1[k])) return G2OHIP_ERR_ARG;
+    if (!hg.idmap.count(v0[k]) || (!unary && !hg.idmap.count(v1[k]))) return G2OHIP_ERR_ARG;
   HEdgeSet* es = hg.set_of(type);
   if (!es) {
     hg.esets.emplace_back();
@@ -1178,14 +1199,19 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
     es->type = type;
     es->D = D;
     es->nm = nm;
+    es->unary = unary;
   }
   for (int k = 0; k < n; ++k) {
     es->ev0.push_back(hg.idmap[v0[k]]);
-    es->ev1.push_back(hg.idmap[v1[k]]);
+    if (!unary) es->ev1.push_back(hg.idmap[v1[k]]);
   }
   if (nm > 0) es->meas.insert(es->meas.end(), meas, meas + (size_t)n * nm);
   es->info.insert(es->info.end(), info, info + (size_t)n * D * D);
-  if (np > 0) es->params.insert(es->params.end(), params, params + (size_t)n * np);
+  if (np > 0 && params) es->params.insert(es->params.end(), params, params + (size_t)n * np);
+  if (np > 0 && !params) {  // EdgeSE3Prior without an offset parameter: the identity
+    const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
+    for (int k = 0; k < n; ++k) es->params.insert(es->params.end(), ident, ident + 7);
+  }
   es->payload.clear();
   initialized = false;
   return G2OHIP_OK;
@@ -1203,10 +1229,8 @@ int Engine::set_robust_kernel(int type, int kind, double delta) {
 int Engine::set_host_payload(int type, const double* payload) {
   HEdgeSet* es = hg.set_of(type);
   if (!es || !is_hostj(type) || !payload) return G2OHIP_ERR_ARG;
-  std::vector<int> dims(es->ev0.size() * 2);
   size_t len = 0;
-  for (size_t k = 0; k < es->ev0.size(); ++k)
-    len += (size_t)es->D * (1 + hg.verts[es->ev0[k]].dim + hg.verts[es->ev1[k]].dim);
+  for (size_t k = 0; k < es->ev0.size(); ++k) len += hostj_edge_len(hg, *es, k);
   es->payload.assign(payload, payload + len);
   es->payload_ver = 0;  // caller-provided: used as is
   if (initialized && edges_ready) {
@@ -1215,8 +1239,7 @@ int Engine::set_host_payload(int type, const double* payload) {
         // gather the group's edges (the host payload has per-edge strides of the edge's own dims; a group has
         // one (DA, DB), so offsets come from a prefix over the set)
         std::vector<size_t> off(es->ev0.size() + 1, 0);
-        for (size_t k = 0; k < es->ev0.size(); ++k)
-          off[k + 1] = off[k] + (size_t)es->D * (1 + hg.verts[es->ev0[k]].dim + hg.verts[es->ev1[k]].dim);
+        for (size_t k = 0; k < es->ev0.size(); ++k) off[k + 1] = off[k] + hostj_edge_len(hg, *es, k);
         const int P = g.payload_stride();
         std::vector<double> buf((size_t)std::max(g.ne, 1) * P);
         for (int k = 0; k < g.ne; ++k)
@@ -1240,13 +1263,16 @@ int Engine::set_host_callback(g2ohip_host_edge_fn fn, void* user) {
 // are skipped with one warning per tag (:455-460); FIX lines fix vertices after loading (:409-417).
 namespace {
 struct ParsedVertex { int type, id; double est[7]; };
-struct ParsedEdge { int type, a, b; double m[7], info[36], p[4]; };
+struct ParsedEdge { int type, a, b; double m[7], info[36], p[7]; };  // unary: b = -1, or the SE3 prior's parameter id
+struct ParsedParam { int id; double v[7]; };                        // PARAMS_SE3OFFSET id x y z qx qy qz qw
 struct ParsedChunk {
   std::vector<ParsedVertex> verts;
   std::vector<ParsedEdge> edges;
+  std::vector<ParsedParam> params;
   std::vector<int> fix;
   std::vector<std::string> unknown;
   bool bad = false;
+  std::string bad_tag;  // the tag of the line that came up short
 };
 struct Cursor {
   const char* p;
@@ -1271,7 +1297,8 @@ struct Cursor {
   }
   bool more() { ws(); return p < e; }
 };
-void parse_chunk(const char* b, const char* e, ParsedChunk& out) {
+// unary: the unary edge tags and PARAMS_SE3OFFSET are parsed (G2OHIP_LOAD_UNARY), else skipped as unknown tags
+void parse_chunk(const char* b, const char* e, bool unary, ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1311,7 +1338,7 @@ void parse_chunk(const char* b, const char* e, ParsedChunk& out) {
       ed.m[0] = c.d(); ed.m[1] = c.d();
       const double o0 = c.d(), o1 = c.d(), o2 = c.d();
       ed.info[0] = o0; ed.info[1] = o1; ed.info[2] = o1; ed.info[3] = o2;
-      for (double& x : ed.p) x = c.d();
+      for (int k = 0; k < 4; ++k) ed.p[k] = c.d();  // fx fy cx cy
       out.edges.push_back(ed);
     } else if (tag == "EDGE_SE2_XY") {  // edge_se2_pointxy.cpp:46-52
       ParsedEdge ed{G2OHIP_E_SE2_XY, c.i(), c.i(), {}, {}, {}};
@@ -1327,16 +1354,38 @@ void parse_chunk(const char* b, const char* e, ParsedChunk& out) {
       for (int r = 0; r < D; ++r)
         for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
       out.edges.push_back(ed);
+    } else if (unary && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
+      ParsedParam pp{c.i(), {}};
+      for (double& x : pp.v) x = c.d();
+      out.params.push_back(pp);
+    } else if (unary && (tag == "EDGE_PRIOR_SE2" || tag == "EDGE_PRIOR_SE2_XY" || tag == "EDGE_PRIOR_XY" ||
+                         tag == "EDGE_POINTXYZ_PRIOR" || tag == "EDGE_SE3_PRIOR")) {
+      // edge_se2_prior.cpp:43-55, edge_se2_xyprior.cpp:36-48, edge_xy_prior.cpp:45-57, edge_xyz_prior.cpp:37-52,
+      // edge_se3_prior.cpp:55-75 (the parameter id ahead of the measurement): measurement, upper triangle of the
+      // information row-wise
+      const int type = tag == "EDGE_PRIOR_SE2"        ? G2OHIP_E_SE2_PRIOR
+                       : tag == "EDGE_PRIOR_SE2_XY"   ? G2OHIP_E_SE2_XY_PRIOR
+                       : tag == "EDGE_PRIOR_XY"       ? G2OHIP_E_XY_PRIOR
+                       : tag == "EDGE_POINTXYZ_PRIOR" ? G2OHIP_E_XYZ_PRIOR
+                                                      : G2OHIP_E_SE3_PRIOR;
+      ParsedEdge ed{type, c.i(), -1, {}, {}, {}};
+      if (type == G2OHIP_E_SE3_PRIOR) ed.b = c.i();
+      const int D = edge_dim(type), nm = edge_meas_dim(type);
+      for (int k = 0; k < nm; ++k) ed.m[k] = c.d();
+      for (int r = 0; r < D; ++r)
+        for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
+      out.edges.push_back(ed);
     } else {
       if (std::find(out.unknown.begin(), out.unknown.end(), tag) == out.unknown.end()) out.unknown.push_back(tag);
       continue;
     }
-    if (!c.ok) { out.bad = true; return; }
+    if (!c.ok) { out.bad = true; out.bad_tag = tag; return; }
   }
 }
 }  // namespace
 
-int Engine::load(const char* path, int marginalize_xyz) {
+int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
+  const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1364,12 +1413,12 @@ int Engine::load(const char* path, int marginalize_xyz) {
   {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
-      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], chunks[t]); });
+      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
   for (auto& c : chunks) {
-    if (c.bad) return G2OHIP_ERR_ARG;
+    if (c.bad) throw StatusError(G2OHIP_ERR_ARG, std::string("g2o_hip load: short or malformed ") + c.bad_tag + " line in " + path);
     for (auto& u : c.unknown)
       if (std::find(warned.begin(), warned.end(), u) == warned.end()) {
         warned.push_back(u);
@@ -1403,11 +1452,15 @@ int Engine::load(const char* path, int marginalize_xyz) {
   std::vector<double> em, ei, ep;
   auto flush_e = [&](int type) -> int {
     if (ea.empty()) return G2OHIP_OK;
-    const int r = add_edges(type, (int)ea.size(), ea.data(), eb.data(), em.data(), ei.data(),
-                            type == G2OHIP_E_SE3_PROJECT_XYZ ? ep.data() : nullptr);
+    const int r = add_edges(type, (int)ea.size(), ea.data(), is_unary_type(type) ? nullptr : eb.data(), em.data(),
+                            ei.data(), edge_param_dim(type) ? ep.data() : nullptr);
     ea.clear(); eb.clear(); em.clear(); ei.clear(); ep.clear();
     return r;
   };
+  // PARAMS_SE3OFFSET records by id (the parameters of the file's EDGE_SE3_PRIOR lines)
+  std::unordered_map<int, const ParsedParam*> offsets;
+  for (auto& c : chunks)
+    for (auto& pp : c.params) offsets[pp.id] = &pp;
   cur = 0;
   for (auto& c : chunks)
     for (auto& ed : c.edges) {
@@ -1416,11 +1469,27 @@ int Engine::load(const char* path, int marginalize_xyz) {
         cur = ed.type;
       }
       const int D = edge_dim(ed.type), nm = edge_meas_dim(ed.type);
+      if (is_unary_type(ed.type)) {  // the vertex type is checked here: a message names the line's vertex
+        int vtA, vtB;
+        family_of(ed.type, vtA, vtB);
+        auto it = hg.idmap.find(ed.a);
+        if (it == hg.idmap.end() || hg.verts[it->second].type != vtA)
+          throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: unary edge (type " + std::to_string(ed.type) + ") on vertex " +
+                                                std::to_string(ed.a) + ", which is missing or of the wrong type");
+        if (ed.type == G2OHIP_E_SE3_PRIOR) {
+          auto po = offsets.find(ed.b);
+          if (po == offsets.end())
+            throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: EDGE_SE3_PRIOR on vertex " + std::to_string(ed.a) +
+                                                  " names parameter id " + std::to_string(ed.b) +
+                                                  ", which no PARAMS_SE3OFFSET line defines");
+          std::memcpy(ed.p, po->second->v, sizeof(double) * 7);
+        }
+      }
       ea.push_back(ed.a);
       eb.push_back(ed.b);
       em.insert(em.end(), ed.m, ed.m + nm);
       ei.insert(ei.end(), ed.info, ed.info + D * D);
-      if (ed.type == G2OHIP_E_SE3_PROJECT_XYZ) ep.insert(ep.end(), ed.p, ed.p + 4);
+      ep.insert(ep.end(), ed.p, ed.p + edge_param_dim(ed.type));
     }
   if (int r = flush_e(cur)) return r;
   for (auto& c : chunks)
@@ -1473,6 +1542,27 @@ int Engine::save(const char* path) {
       o.s.clear();
     }
   };
+  // parameters first (optimizable_graph.cpp:663-667): one PARAMS_SE3OFFSET line per distinct offset of the SE3 priors,
+  // ids in first-seen order; prior_pid[k] = the id edge k's line names
+  std::vector<int> prior_pid;
+  if (const HEdgeSet* ps = hg.set_of(G2OHIP_E_SE3_PRIOR)) {
+    std::vector<const double*> distinct;
+    prior_pid.resize(ps->ev0.size());
+    for (size_t k = 0; k < ps->ev0.size(); ++k) {
+      const double* p = ps->params.data() + k * 7;
+      size_t j = 0;
+      while (j < distinct.size() && std::memcmp(distinct[j], p, sizeof(double) * 7) != 0) ++j;
+      if (j == distinct.size()) {
+        distinct.push_back(p);
+        LineBuf& L = out[0];
+        L.tag("PARAMS_SE3OFFSET"); L.i((int)j);
+        for (int q = 0; q < 7; ++q) L.d(p[q]);
+        L.nl();
+      }
+      prior_pid[k] = (int)j;
+    }
+    flush();
+  }
   parallel_ranges(hg.verts.size(), nt, [&](int t, size_t lo, size_t hi) {
     LineBuf& L = out[t];
     L.s.reserve((hi - lo) * 96);
@@ -1506,10 +1596,21 @@ int Engine::save(const char* path) {
       LineBuf& L = out[t];
       L.s.reserve((hi - lo) * 200);
       for (size_t k = lo; k < hi; ++k) {
-        const int a = hg.verts[es.ev0[k]].id, b = hg.verts[es.ev1[k]].id;
+        const int a = hg.verts[es.ev0[k]].id, b = es.unary ? -1 : hg.verts[es.ev1[k]].id;
         const double* m = es.meas.data() + k * nm;
         const double* I = es.info.data() + k * D * D;
-        if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
+        if (es.unary) {  // edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58, edge_xy_prior.cpp:59-67,
+                         // edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86 (the parameter id first)
+          L.tag(es.type == G2OHIP_E_SE2_PRIOR      ? "EDGE_PRIOR_SE2"
+                : es.type == G2OHIP_E_SE2_XY_PRIOR ? "EDGE_PRIOR_SE2_XY"
+                : es.type == G2OHIP_E_XY_PRIOR     ? "EDGE_PRIOR_XY"
+                : es.type == G2OHIP_E_XYZ_PRIOR    ? "EDGE_POINTXYZ_PRIOR"
+                                                   : "EDGE_SE3_PRIOR");
+          L.i(a);
+          if (es.type == G2OHIP_E_SE3_PRIOR) L.i(prior_pid[k]);
+          for (int q = 0; q < nm; ++q) L.d(m[q]);
+          for (int r = 0; r < D; ++r) for (int q = r; q < D; ++q) L.d(I[r * D + q]);
+        } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
           L.tag("EDGE_SE2_XY"); L.i(a); L.i(b);
           L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
         } else if (es.type == G2OHIP_E_SE3_PROJECT_XYZ) {  // types_six_dof_expmap.cpp:380-393
@@ -1535,8 +1636,7 @@ long long Engine::host_payload_len(int type) {
   HEdgeSet* es = hg.set_of(type);
   if (!es || !is_hostj(type)) return G2OHIP_ERR_ARG;
   long long len = 0;
-  for (size_t k = 0; k < es->ev0.size(); ++k)
-    len += (long long)es->D * (1 + hg.verts[es->ev0[k]].dim + hg.verts[es->ev1[k]].dim);
+  for (size_t k = 0; k < es->ev0.size(); ++k) len += (long long)hostj_edge_len(hg, *es, k);
   return len;
 }
 
@@ -1673,26 +1773,47 @@ static int family_of(int etype, int& vtA, int& vtB) {
     case G2OHIP_E_SE3_QUAT: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3;
     case G2OHIP_E_SE2: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2;
     case G2OHIP_E_SE2_XY: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY;
+    // unary types: vtB = 0 (no second vertex)
+    case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
+    case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
+    case G2OHIP_E_XY_PRIOR: vtA = G2OHIP_V_XY; vtB = 0; return FAM_U_XY;
+    case G2OHIP_E_SE3_PRIOR: vtA = G2OHIP_V_SE3_QUAT; vtB = 0; return FAM_U_SE3;
+    case G2OHIP_E_XYZ_PRIOR: vtA = G2OHIP_V_XYZ; vtB = 0; return FAM_U_XYZ;
   }
   vtA = vtB = 0;
-  return is_hostj(etype) ? FAM_HOSTJ : FAM_NONE;
+  return is_hostj_binary(etype) ? FAM_HOSTJ : (is_hostj_unary(etype) ? FAM_U_HOSTJ : FAM_NONE);
 }
 
-int Engine::initialize() {  // sparse_optimizer.cpp:201-279 + buildIndexMapping :168-192
-  if (hg.num_edges() == 0) return G2OHIP_ERR_STATE;
-  has_hostj = false;
-  std::vector<char> has(hg.verts.size(), 0);
+// type checks and the vertices that have edges (initialize / update_initialization); a unary set checks one vertex
+static int mark_edge_vertices(const HostGraph& hg, std::vector<char>& has, bool& hostj, bool& unary) {
+  hostj = unary = false;
   for (const HEdgeSet& es : hg.esets) {
     int vtA, vtB;
     const int fam = family_of(es.type, vtA, vtB);
     if (fam == FAM_NONE) return G2OHIP_ERR_UNSUPPORTED;
-    has_hostj |= fam == FAM_HOSTJ;
+    hostj |= is_hostj_family(fam);
+    unary |= es.unary && !es.ev0.empty();
     for (size_t k = 0; k < es.ev0.size(); ++k) {
-      const HVertex &a = hg.verts[es.ev0[k]], &b = hg.verts[es.ev1[k]];
-      if (fam != FAM_HOSTJ && (a.type != vtA || b.type != vtB)) return G2OHIP_ERR_UNSUPPORTED;
-      has[es.ev0[k]] = has[es.ev1[k]] = 1;
+      const HVertex& a = hg.verts[es.ev0[k]];
+      if (!is_hostj_family(fam) && a.type != vtA)
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED, "edge type " + std::to_string(es.type) + " on vertex " +
+                                                      std::to_string(a.id) + " of vertex type " + std::to_string(a.type));
+      has[es.ev0[k]] = 1;
+      if (es.unary) continue;
+      const HVertex& b = hg.verts[es.ev1[k]];
+      if (!is_hostj_family(fam) && b.type != vtB)
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED, "edge type " + std::to_string(es.type) + " on vertex " +
+                                                      std::to_string(b.id) + " of vertex type " + std::to_string(b.type));
+      has[es.ev1[k]] = 1;
     }
   }
+  return G2OHIP_OK;
+}
+
+int Engine::initialize() {  // sparse_optimizer.cpp:201-279 + buildIndexMapping :168-192
+  if (hg.num_edges() == 0) return G2OHIP_ERR_STATE;
+  std::vector<char> has(hg.verts.size(), 0);
+  if (int r = mark_edge_vertices(hg, has, has_hostj, has_unary_)) return r;
   active.clear();
   for (size_t k = 0; k < hg.verts.size(); ++k)
     if (has[k]) active.push_back((int)k);
@@ -1727,9 +1848,10 @@ int Engine::initialize() {  // sparse_optimizer.cpp:201-279 + buildIndexMapping 
   do_schur = num_landmarks > 0;  // optimization_algorithm_with_hessian.cpp:48-73
   // the Schur kernels are instantiated for BlockSolver_6_3 and BlockSolver_3_2 (block_solver.h:188-201)
   if (do_schur && !((pd == 6 && ld == 3) || (pd == 3 && ld == 2))) return G2OHIP_ERR_UNSUPPORTED;
-  // landmark-landmark edges have no place in BlockSolver's Schur layout here
+  // landmark-landmark edges have no place in BlockSolver's Schur layout here (a prior on a landmark is no such edge:
+  // it lands in the landmark's own Hll block)
   for (const HEdgeSet& es : hg.esets)
-    for (size_t k = 0; k < es.ev0.size(); ++k) {
+    for (size_t k = 0; k < es.ev0.size() && !es.unary; ++k) {
       const int a = hidx[es.ev0[k]], b = hidx[es.ev1[k]];
       if (a >= num_poses && b >= num_poses) return G2OHIP_ERR_UNSUPPORTED;
     }
@@ -1752,18 +1874,8 @@ int Engine::update_initialization() {
   if (do_schur) return G2OHIP_ERR_UNSUPPORTED;
   std::vector<char> was(hg.verts.size(), 0), has(hg.verts.size(), 0);
   for (int vi : active) was[vi] = 1;
-  bool hj = false;
-  for (const HEdgeSet& es : hg.esets) {
-    int vtA, vtB;
-    const int fam = family_of(es.type, vtA, vtB);
-    if (fam == FAM_NONE) return G2OHIP_ERR_UNSUPPORTED;
-    hj |= fam == FAM_HOSTJ;
-    for (size_t k = 0; k < es.ev0.size(); ++k) {
-      const HVertex &a = hg.verts[es.ev0[k]], &b = hg.verts[es.ev1[k]];
-      if (fam != FAM_HOSTJ && (a.type != vtA || b.type != vtB)) return G2OHIP_ERR_UNSUPPORTED;
-      has[es.ev0[k]] = has[es.ev1[k]] = 1;
-    }
-  }
+  bool hj = false, un = false;
+  if (int r = mark_edge_vertices(hg, has, hj, un)) return r;
   std::vector<int> fresh;
   for (size_t k = 0; k < hg.verts.size(); ++k)
     if (has[k] && !was[k]) fresh.push_back((int)k);
@@ -1782,6 +1894,7 @@ int Engine::update_initialization() {
   }
   size_poses = num_poses * pd;
   has_hostj = hj;
+  has_unary_ = un;
   initialized = true;
   structure_built = false;
   edges_ready = false;
@@ -1807,8 +1920,7 @@ static void upload_group_payload(const HostGraph& hg, EGroup& g, hipStream_t s) 
   std::vector<double> buf((size_t)std::max(g.ne, 1) * P, 0.0);
   if (!es.payload.empty()) {
     std::vector<size_t> off(es.ev0.size() + 1, 0);
-    for (size_t k = 0; k < es.ev0.size(); ++k)
-      off[k + 1] = off[k] + (size_t)es.D * (1 + hg.verts[es.ev0[k]].dim + hg.verts[es.ev1[k]].dim);
+    for (size_t k = 0; k < es.ev0.size(); ++k) off[k + 1] = off[k] + hostj_edge_len(hg, es, k);
     if (off.back() != es.payload.size()) throw std::runtime_error("host-J payload size does not match the edges");
     for (int k = 0; k < g.ne; ++k)
       std::memcpy(buf.data() + (size_t)k * P, es.payload.data() + off[g.edges[k]], sizeof(double) * P);
@@ -1825,8 +1937,7 @@ void Engine::refresh_host_payload(bool jacobians) {
       if (!jacobians && es.payload_ver == state_ver) continue;  // errors of this state already there
       sync_host_state();  // the callback reads the estimates the device holds
       size_t len = 0;
-      for (size_t k = 0; k < es.ev0.size(); ++k)
-        len += (size_t)es.D * (1 + hg.verts[es.ev0[k]].dim + hg.verts[es.ev1[k]].dim);
+      for (size_t k = 0; k < es.ev0.size(); ++k) len += hostj_edge_len(hg, es, k);
       es.payload.assign(len, 0.0);
       if (host_fn(host_user, es.type, jacobians ? 1 : 0, es.payload.data()) != 0)
         throw std::runtime_error("host edge callback failed for edge type " + std::to_string(es.type));
@@ -1857,9 +1968,10 @@ void Engine::setup_edges_device() {
   for (int l = lm_begin; l < lm_end; ++l) local_lm.push_back(l);
   // an edge belongs to the rank owning its landmark endpoint; edges without a (free) landmark are assembled by rank 0
   // once. Pose graphs run replicas: every rank assembles every edge.
+  // (a prior on a free landmark goes to that landmark's rank, one on a pose to rank 0: vb = -1 has no hessian index)
   auto owner_of = [&](int va, int vb) {
     if (!(do_schur && nranks > 1)) return rank;
-    const int h = hidx[va] >= num_poses ? hidx[va] : (hidx[vb] >= num_poses ? hidx[vb] : -1);
+    const int h = hidx[va] >= num_poses ? hidx[va] : (hx(vb) >= num_poses ? hx(vb) : -1);
     if (h < 0) return 0;
     return (int)(std::upper_bound(bnd.begin(), bnd.end(), h - num_poses) - bnd.begin()) - 1;
   };
@@ -1873,9 +1985,11 @@ void Engine::setup_edges_device() {
     std::vector<std::pair<int, int>> keys;
     std::vector<std::vector<int>> lists;
     for (size_t k = 0; k < es.ev0.size(); ++k) {
-      const int va = es.ev0[k], vb = es.ev1[k];
+      const int va = es.ev0[k], vb = es.v1(k);
+      // a unary edge on a fixed vertex is inactive (sparse_optimizer.cpp:241, allVerticesFixed): no chi2, no H, no b
+      if (es.unary && hidx[va] < 0) continue;
       if (owner_of(va, vb) != rank) continue;
-      const std::pair<int, int> key{hg.verts[va].type, hg.verts[vb].type};
+      const std::pair<int, int> key{hg.verts[va].type, vb < 0 ? 0 : hg.verts[vb].type};
       size_t gi = std::find(keys.begin(), keys.end(), key) - keys.begin();
       if (gi == keys.size()) { keys.push_back(key); lists.emplace_back(); }
       lists[gi].push_back((int)k);
@@ -1889,7 +2003,7 @@ void Engine::setup_edges_device() {
       g.vtB = keys[gi].second;
       g.D = es.D;
       g.DA = vertex_dim(g.vtA);
-      g.DB = vertex_dim(g.vtB);
+      g.DB = g.vtB ? vertex_dim(g.vtB) : 0;
       g.edges = std::move(lists[gi]);
       g.ne = (int)g.edges.size();
       ne += g.ne;
@@ -1911,22 +2025,25 @@ void Engine::setup_edges_device() {
     const int D = g.D, nm = es.nm, gne = g.ne;
     std::vector<int> v0(std::max(gne, 1), 0), v1(std::max(gne, 1), 0);
     const int minfo = D * (D + 1) / 2;
-    const int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY
-                          ? 2
-                          : (g.family == FAM_SE3 ? 12 : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO ? 3 : 0));
+    int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY
+                    ? 2
+                    : (g.family == FAM_SE3 ? 12 : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO ? 3 : 0));
+    switch (g.family) {  // unary families: the payload k_linearize_unary's family reads (device_types.hpp)
+      case FAM_U_SE2: case FAM_U_XYZ: mmeas = 3; break;
+      case FAM_U_SE2XY: case FAM_U_XY: mmeas = 2; break;
+      case FAM_U_SE3: mmeas = 24; break;
+    }
     const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type) : 0;
     std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
         params(mpar ? (size_t)gne * mpar : 1);
     for (int k = 0; k < gne; ++k) {
       const int e = g.edges[k];
       v0[k] = hg.verts[es.ev0[e]].local;
-      v1[k] = hg.verts[es.ev1[e]].local;
+      if (!es.unary) v1[k] = hg.verts[es.ev1[e]].local;
       const double* m = es.meas.data() + (size_t)e * nm;
       double* mo = meas.data() + (size_t)k * mmeas;
-      if (is_ba_family(g.family)) {
-        for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
-        for (int j = 0; j < mpar; ++j) params[(size_t)k * mpar + j] = es.params[(size_t)e * mpar + j];
-      } else if (g.family == FAM_SE3) {  // edge_se3.cpp:42-50: normalise q, Z = fromVectorQT, store Z^-1
+      // x y z qx qy qz qw -> Z^-1 as [R^T (row-major) | -R^T t]: normalise q, Z = fromVectorQT (edge_se3.cpp:42-50)
+      auto iso_inverse_of = [](const double* m, double* mo) {
         double q[4] = {m[3], m[4], m[5], m[6]};
         const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
         for (double& x : q) x /= n;
@@ -1935,7 +2052,23 @@ void Engine::setup_edges_device() {
         double Rt[9] = {Z[0], Z[3], Z[6], Z[1], Z[4], Z[7], Z[2], Z[5], Z[8]};
         for (int j = 0; j < 9; ++j) mo[j] = Rt[j];
         for (int i = 0; i < 3; ++i) mo[9 + i] = -(Rt[i * 3] * m[0] + Rt[i * 3 + 1] * m[1] + Rt[i * 3 + 2] * m[2]);
-      } else if (g.family == FAM_SE2) {  // edge_se2.cpp:41-47: inverse measurement
+      };
+      if (is_ba_family(g.family)) {
+        for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+        for (int j = 0; j < mpar; ++j) params[(size_t)k * mpar + j] = es.params[(size_t)e * mpar + j];
+      } else if (g.family == FAM_SE3) {
+        iso_inverse_of(m, mo);
+      } else if (g.family == FAM_U_SE3) {  // edge_se3_prior.cpp:55-63: Z^-1, then the offset P = fromVectorQT(params)
+        iso_inverse_of(m, mo);
+        const double* p = es.params.data() + (size_t)e * 7;
+        double q[4] = {p[3], p[4], p[5], p[6]};
+        const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        for (double& x : q) x /= n;
+        q2R(q[0], q[1], q[2], q[3], mo + 12);
+        for (int i = 0; i < 3; ++i) mo[21 + i] = p[i];
+      } else if (g.family == FAM_U_SE2XY || g.family == FAM_U_XY || g.family == FAM_U_XYZ) {
+        for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+      } else if (g.family == FAM_SE2 || g.family == FAM_U_SE2) {  // edge_se2.cpp:41-47, edge_se2_prior.cpp:67-71: inverse measurement
         const double th = norm_theta(-m[2]);
         const double c = std::cos(th), s = std::sin(th);
         mo[0] = c * (-m[0]) - s * (-m[1]);
@@ -1968,7 +2101,7 @@ void Engine::setup_edges_device() {
     }
     g.info.upload(info, stream);
     g.params.upload(params, stream);
-    if (g.family == FAM_HOSTJ) upload_group_payload(hg, g, stream);
+    if (is_hostj_family(g.family)) upload_group_payload(hg, g, stream);
     else g.meas.upload(meas, stream);
   }
   if (ba_fused) {
@@ -2103,7 +2236,7 @@ void Engine::schur_pattern(std::vector<int>& sbi, std::vector<int>& sbj, std::ve
   for (int i = 0; i < num_poses; ++i) rowcols[i].push_back(i);
   for (const HEdgeSet& es : hg.esets)
     for (size_t e = 0; e < es.ev0.size(); ++e) {
-      const int i1 = hidx[es.ev0[e]], i2 = hidx[es.ev1[e]];
+      const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
       if (i1 < 0 || i2 < 0) continue;
       if (i1 >= num_poses && i2 < num_poses) lmposes[i1 - num_poses].push_back(i2);
       else if (i2 >= num_poses && i1 < num_poses) lmposes[i2 - num_poses].push_back(i1);
@@ -2132,7 +2265,7 @@ std::vector<double> Engine::pose_work() const {
   std::vector<double> w(num_poses, 0.0);
   for (const HEdgeSet& es : hg.esets)
     for (size_t e = 0; e < es.ev0.size(); ++e) {
-      const int i1 = hidx[es.ev0[e]], i2 = hidx[es.ev1[e]];
+      const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
       if (i1 >= num_poses && i2 >= 0 && i2 < num_poses) w[i2] += dist_cost::OBS_S;
       else if (i2 >= num_poses && i1 >= 0 && i1 < num_poses) w[i1] += dist_cost::OBS_S;
     }
@@ -2187,7 +2320,7 @@ void Engine::align_shards() {
   std::vector<std::vector<int>> lp(num_landmarks);
   for (const HEdgeSet& es : hg.esets)
     for (size_t e = 0; e < es.ev0.size(); ++e) {
-      const int i1 = hidx[es.ev0[e]], i2 = hidx[es.ev1[e]];
+      const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
       if (i1 >= num_poses && i2 >= 0 && i2 < num_poses) lp[i1 - num_poses].push_back(i2);
       else if (i2 >= num_poses && i1 >= 0 && i1 < num_poses) lp[i2 - num_poses].push_back(i1);
     }
@@ -2318,6 +2451,10 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     int r = initialize();
     if (r) return r;
   }
+  if (use_cgls() && has_unary_)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                      "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take unary edges: the "
+                      "graph holds priors; use lm_pcg6_3 or lm_hip_fix6_3");
   ensure_device_state();
   if (comm) comm->rearm();  // a new collective sequence: RCCL's call-sequence check covers its first calls again
   align_shards();
@@ -2346,7 +2483,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     const HEdgeSet& es = hg.esets[groups[gi].set];
     const int e = groups[gi].edges[k];
     va = es.ev0[e];
-    vb = es.ev1[e];
+    vb = es.v1(e);  // -1: a unary edge
   };
   std::map<std::pair<int, int>, int> hppmap;  // (i<j) -> block id
   hpp_bi.assign(num_poses, 0);
@@ -2360,8 +2497,8 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
       int va, vb;
       verts_of(gi, k, va, vb);
       const long long f = gfirst[gi] + k;
-      int i1 = hidx[va], i2 = hidx[vb];
-      if (i1 < 0 || i2 < 0) continue;
+      int i1 = hidx[va], i2 = hx(vb);
+      if (i1 < 0 || i2 < 0) continue;  // (a unary edge has no off-diagonal block: no offref, no Hpp / Hpl block)
       const bool m1 = i1 >= num_poses, m2 = i2 >= num_poses;
       if (!m1 && !m2) {
         bool tr = i1 > i2;
@@ -2448,6 +2585,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     long long& ca = nslot[g.DA];
     g.slotA = ca;
     ca += g.ne;
+    if (!g.DB) continue;  // a unary group: ne slots in the arena of DA only
     long long& cb = nslot[g.DB];
     g.slotB = cb;
     cb += g.ne;
@@ -2500,7 +2638,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
       for (int k = 0; k < g.ne; ++k) {
         int va, vb;
         verts_of(gi, k, va, vb);
-        const int hs[2] = {hidx[va], hidx[vb]};
+        const int hs[2] = {hidx[va], hx(vb)};
         const long long code[2] = {g.slotA + k, g.slotB + k};
         for (int sd = 0; sd < 2; ++sd) {
           const int h = hs[sd];
@@ -3008,7 +3146,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
         };
         for (const HEdgeSet& es : hg.esets)
           for (size_t e = 0; e < es.ev0.size(); ++e) {
-            const int i1 = hidx[es.ev0[e]], i2 = hidx[es.ev1[e]];
+            const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
             if (i1 >= num_poses || i2 >= num_poses) continue;  // a free landmark endpoint: its owner's
             for (int h : {i1, i2})
               if (h >= 0) { const int t = blk(h, h); if (t >= 0) by0[t] = 1; }
@@ -3169,11 +3307,20 @@ int Engine::build_system_split(double lambda, const double* lamp) {  // block_so
   }
   timer.begin("linearize", stream);
   for (const EGroup& g : groups)
-    launch::linearize(g.family, group_args(g), g.ne, d_hidx[g.vtA].get(), d_hidx[g.vtB].get(),
-                      slot_arena(g.DA) + g.slotA * (g.DA * (g.DA + 1) / 2 + g.DA),
-                      slot_arena(g.DB) + g.slotB * (g.DB * (g.DB + 1) / 2 + g.DB), g.off_dst.get(), g.off_tr.get(),
-                      dH.get(), doffslot.get(), stream);
+    if (!is_unary_family(g.family))
+      launch::linearize(g.family, group_args(g), g.ne, d_hidx[g.vtA].get(), d_hidx[g.vtB].get(),
+                        slot_arena(g.DA) + g.slotA * (g.DA * (g.DA + 1) / 2 + g.DA),
+                        slot_arena(g.DB) + g.slotB * (g.DB * (g.DB + 1) / 2 + g.DB), g.off_dst.get(), g.off_tr.get(),
+                        dH.get(), doffslot.get(), stream);
   timer.end(stream);
+  if (has_unary_) {  // the unary groups: one slot per edge (k_linearize_unary), timed as a class of their own
+    timer.begin("linearize_unary", stream);
+    for (const EGroup& g : groups)
+      if (is_unary_family(g.family))
+        launch::linearize_unary(g.family, group_args(g), g.ne, d_hidx[g.vtA].get(),
+                                slot_arena(g.DA) + g.slotA * (g.DA * (g.DA + 1) / 2 + g.DA), stream);
+    timer.end(stream);
+  }
   for (const OffRed& R : offred)
     launch::offblock_reduce(R.nb, R.bsz, R.ptr.get(), R.soff.get(), doffslot.get(), dH.get(), R.dst.get(), stream);
   timer.begin("vreduce", stream);
@@ -3498,9 +3645,9 @@ int Engine::lm_solve(int iteration, const g2ohip_config& cfg, g2ohip_batch_stats
     // computeScale (:177-184) on the device, sum x (lambda x + b), while lambda is still set; the
     // restoreDiagonal that follows (:113) is the next setLambda (lambda is virtual, never in H)
     // one rank, device decision: the finals and k_lm_decide in one launch (no all-reduce between them)
-    const bool decide_fused = spec && nranks <= 1 && groups.size() == 1 && groups[0].family != FAM_HOSTJ;
+    const bool decide_fused = spec && nranks <= 1 && groups.size() == 1 && !is_hostj_family(groups[0].family);
     last_decide_fused = decide_fused;
-    if (groups.size() == 1 && groups[0].family != FAM_HOSTJ) {  // chi2 and the scale sum in one pass + one final
+    if (groups.size() == 1 && !is_hostj_family(groups[0].family)) {  // chi2 and the scale sum in one pass + one final
       timer.begin("error", stream);
       const EGroup& g = groups[0];
       const launch::LmDecide dec{currentChi, (double)ni, rank == 0, hdec_dev_};
@@ -4011,9 +4158,26 @@ double Engine::kernel_bytes(const std::string& name) const {
   }
   if (name == "backsub") return local_lm.size() * (3 * 8.0 * 2 + 72) + npl * (pb + 4) + size_poses * 8.0;
   if (name == "chol_factor") return (double)chol.sym.front_pool * 8 * 2;
+  if (name == "linearize_unary") {  // per edge: vertex index + hessian index, edge data (payload + packed information),
+                                    // the vertex state read, the slot written
+    double by = 0;
+    for (const EGroup& g : groups)
+      if (is_unary_family(g.family)) {
+        const int mm = g.family == FAM_U_SE3 ? 24 : (g.family == FAM_U_HOSTJ ? g.payload_stride() : hg.esets[g.set].nm);
+        by += g.ne * (8.0 + (mm + g.D * (g.D + 1) / 2 + vertex_state_stride(g.vtA) + g.DA * (g.DA + 1) / 2 + g.DA) * 8.0);
+      }
+    return by;
+  }
   return 0;
 }
 double Engine::kernel_flops(const std::string& name) const {
+  if (name == "linearize_unary") {  // A^T Omega (2 D^2 DA), its product with A (upper: D DA (DA + 1)), Omega e and A^T w
+    double fl = 0;
+    for (const EGroup& g : groups)
+      if (is_unary_family(g.family))
+        fl += (double)g.ne * (2.0 * g.D * g.D * g.DA + (double)g.D * g.DA * (g.DA + 1) + 2.0 * g.D * g.D + 2.0 * g.D * g.DA);
+    return fl;
+  }
   if (name == "chol_factor") return chol.sym.flops;
   if (name == "schur_rows") return (double)npairs * (108 * 2);
   return 0;

@@ -38,8 +38,11 @@ struct HVertex {
 // one edge type of the graph (edges kept in insertion order)
 struct HEdgeSet {
   int type = 0, D = 0, nm = 0;          // G2OHIP_E_*, error dimension, measurement doubles per edge
-  std::vector<int> ev0, ev1;            // vertex indices
-  std::vector<double> meas, info, params;  // raw: meas (as given), info D*D row-major, params 4
+  std::vector<int> ev0, ev1;            // vertex indices (a unary set stores one endpoint: ev1 stays empty)
+  bool unary = false;                   // BaseUnaryEdge types (G2OHIP_E_*_PRIOR, G2OHIP_E_HOSTJ_UNARY)
+  int v1(size_t k) const { return unary ? -1 : ev1[k]; }  // -1: no second vertex
+  std::vector<double> meas, info, params;  // raw: meas (as given), info D*D row-major, params 4 (stereo 5; SE3 prior:
+                                           // the offset, 7)
   int rk = 0;                           // robust kernel (G2OHIP_RK_*), delta
   double rk_delta = 1.0;
   std::vector<double> payload;          // host-J edges: latest [e | Ji | Jj] per edge from the host
@@ -65,7 +68,8 @@ struct HostGraph {
 };
 
 // A device edge group: the local-shard edges of one edge set with one pair of endpoint vertex types,
-// linearized by one kernel instantiation (family, D, DA, DB)
+// linearized by one kernel instantiation (family, D, DA, DB). Unary sets: one group per vertex type, vtB = 0, DB = 0,
+// slots in the arena of DA only (k_linearize_unary); edges on fixed vertices are inactive and stay out of the group
 struct EGroup {
   int set = 0, family = 0, vtA = 0, vtB = 0, D = 0, DA = 0, DB = 0;
   std::vector<int> edges;               // indices into the edge set
@@ -248,7 +252,7 @@ class Engine {
   int set_host_callback(g2ohip_host_edge_fn fn, void* user);
   // computeLambdaInit (optimization_algorithm_levenberg.cpp:152-175): max |diagonal| of Hpp and Hll
   int diag_absmax(double* out);
-  int load(const char* path, int marginalize_xyz);
+  int load(const char* path, int marginalize_xyz, unsigned flags = 0);  // flags: G2OHIP_LOAD_*
   int save(const char* path);
   // doubles of the host payload of a host-J edge type ([e | Ji | Jj] per edge, insertion order)
   long long host_payload_len(int type);
@@ -332,6 +336,8 @@ class Engine {
   int ne = 0;                    // local edges over all groups
   std::vector<EGroup> groups;
   bool has_hostj = false;
+  bool has_unary_ = false;  // some edge set is unary (lm_pcg6_3_eigen refuses, the fused BA assembly does not apply)
+  int hx(int v) const { return v < 0 ? -1 : hidx[v]; }  // hessian index of a vertex, -1: fixed or no vertex
   g2ohip_host_edge_fn host_fn = nullptr;
   void* host_user = nullptr;
   // sharding
@@ -371,7 +377,9 @@ class Engine {
   DevBuf<double> doffslot;
   struct OffRed { int nb = 0, bsz = 0; DevBuf<int> ptr; DevBuf<long long> soff, dst; };
   OffRed offred[2];  // [Hpp off-diagonal blocks (pd x pd), Hpl blocks (pd x ld)]
-  // fused BA assembly (assembly.hip): graphs whose only edge group is BA in Schur mode; edges landmark-major,
+  // fused BA assembly (assembly.hip): graphs whose only edge group is BA in Schur mode (a BA graph that also holds
+  // active unary edges, priors on cameras or landmarks, has more groups and takes the generic slot path, as a mixed
+  // monocular + stereo graph does; fusing priors into the camera pass is not done); edges landmark-major,
   // wave chunks of whole landmarks, camera-major copies of the edge data for the camera-side pass
   bool ba_fused = false;
   DevBuf<int4> fz_chunks, fz_fix;
@@ -460,7 +468,8 @@ class Engine {
   // the kernel timer records events in the assembly (all classes, or one of the assembly's): the speculative next
   // assembly is off then (a timer on chol_factor alone, bench.py's, leaves it on)
   bool timer_times_build() const {
-    return timer.enabled && (timer.only.empty() || timer.only == "linearize" || timer.only == "vreduce" ||
+    return timer.enabled && (timer.only.empty() || timer.only == "linearize" || timer.only == "linearize_unary" ||
+                             timer.only == "vreduce" ||
                              timer.only == "schur_rows");
   }
   double* hscal_ = nullptr;      // pinned host copy of dscal (one readback per LM trial)

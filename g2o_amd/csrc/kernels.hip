@@ -4,6 +4,8 @@
 //                 BaseBinaryEdge::constructQuadraticForm (base_binary_edge.hpp:61-100):
 //                 one lane per edge, J and J^T Omega J in registers, contributions streamed
 //                 to per-edge slots (no atomics, no locks).
+//   k_linearize_unary  the same for BaseUnaryEdge types (base_unary_edge.hpp:48-78): one vertex, one slot
+//                 per edge, no off-diagonal block.
 //   k_vertex_reduce  deterministic segmented reduction of the slots into Hpp/Hll diagonal
 //                 blocks and b (replaces the per-vertex omp locks + copyB, :467-517).
 //   k_schur_prep  landmark pass of BlockSolver::solve (:342-360): Dinv = (Hll+lambda I)^-1,
@@ -231,6 +233,80 @@ __global__ void __launch_bounds__(256)
   }
   wave_sync();
   wave_copy_out(slot1 + (size_t)ebase * SB, sw, nw * SB, lane);
+}
+
+// BaseUnaryEdge::constructQuadraticForm (base_unary_edge.hpp:48-78) for the unary families: one lane per edge, the
+// single packed-upper A^T Omega A | A^T (-Omega e) slot (Omega scaled by rho' under a robust kernel) staged in the
+// wave's LDS image and streamed out with wave_copy_out. No second slot, no off-diagonal block. A lane whose vertex is
+// fixed writes nothing to the image (its slot is never read).
+template <class F>
+__global__ void __launch_bounds__(256)
+    k_linearize_unary(EdgeData d, int ne, const int* __restrict__ h0, double* __restrict__ slot0) {
+  constexpr int D = F::D, DA = F::DA;
+  constexpr int SA = DA * (DA + 1) / 2 + DA;
+  __shared__ __attribute__((aligned(16))) double stage[4][64 * SA];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int e = blockIdx.x * blockDim.x + tid;
+  const int ebase = e - lane, nw = min(64, ne - ebase);  // the wave's edges [ebase, ebase + nw)
+  if (nw <= 0) return;                                  // wave-uniform
+  double* sw = stage[tid >> 6];
+  if (e < ne && h0[d.v0[e]] >= 0) {
+    double err[D], A[D * DA], Om[D * D];
+    F::linearize(d, e, err, A);
+    load_info<D>(info_rec(d, e, F::INFO), Om);
+    if (d.rk) {  // base_unary_edge.hpp:62-69: weightedOmega = rho' Omega, b -= rho' A^T Omega e
+      double chi = 0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        double r = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) r += Om[i * D + j] * err[j];
+        chi += err[i] * r;
+      }
+      double r0, r1;
+      robustify(d.rk, d.rk_delta, chi, r0, r1);
+#pragma unroll
+      for (int i = 0; i < D * D; ++i) Om[i] *= r1;
+    }
+    double wr[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      double s = 0;
+#pragma unroll
+      for (int c = 0; c < D; ++c) s += Om[r * D + c] * err[c];
+      wr[r] = -s;
+    }
+    double AtO[DA * D];  // A^T Omega
+#pragma unroll
+    for (int i = 0; i < DA; ++i)
+#pragma unroll
+      for (int c = 0; c < D; ++c) {
+        double s = 0;
+#pragma unroll
+        for (int r = 0; r < D; ++r) s += A[r * DA + i] * Om[r * D + c];
+        AtO[i * D + c] = s;
+      }
+    double* o = sw + lane * SA;
+    int k = 0;
+#pragma unroll
+    for (int c = 0; c < DA; ++c)
+#pragma unroll
+      for (int r = 0; r <= c; ++r) {
+        double s = 0;
+#pragma unroll
+        for (int t = 0; t < D; ++t) s += AtO[r * D + t] * A[t * DA + c];
+        o[k++] = s;
+      }
+#pragma unroll
+    for (int i = 0; i < DA; ++i) {
+      double s = 0;
+#pragma unroll
+      for (int r = 0; r < D; ++r) s += A[r * DA + i] * wr[r];
+      o[k++] = s;
+    }
+  }
+  wave_sync();
+  wave_copy_out(slot0 + (size_t)ebase * SA, sw, nw * SA, lane);
 }
 
 // ------------------------------------------------------------------------------ vertex reduction
@@ -1509,8 +1585,46 @@ static void hj_a(int DA, int DB, Fn& fn) {
   else if (DA == 6) hj_b<D, 6>(DB, fn);
   else throw std::runtime_error("host-Jacobian edge: vertex dimension must be 2, 3 or 6");
 }
+// unary families; host-Jacobian ones: runtime (D, DA) -> FamilyHostJUnary<D, DA>
+template <int D, class Fn>
+static void hju_a(int DA, Fn& fn) {
+  if (DA == 2) fn(FamilyHostJUnary<D, 2>{});
+  else if (DA == 3) fn(FamilyHostJUnary<D, 3>{});
+  else if (DA == 6) fn(FamilyHostJUnary<D, 6>{});
+  else throw std::runtime_error("host-Jacobian unary edge: vertex dimension must be 2, 3 or 6");
+}
+template <class Fn>
+static void unary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
+  switch (family) {
+    case FAM_U_SE2: fn(FamilyUnarySE2{}); break;
+    case FAM_U_SE2XY: fn(FamilyUnarySE2XY{}); break;
+    case FAM_U_XY: fn(FamilyUnaryXY{}); break;
+    case FAM_U_SE3: fn(FamilyUnarySE3{}); break;
+    case FAM_U_XYZ: fn(FamilyUnaryXYZ{}); break;
+    case FAM_U_HOSTJ:
+      switch (a.D) {
+        case 1: hju_a<1>(a.DA, fn); break;
+        case 2: hju_a<2>(a.DA, fn); break;
+        case 3: hju_a<3>(a.DA, fn); break;
+        case 4: hju_a<4>(a.DA, fn); break;
+        case 5: hju_a<5>(a.DA, fn); break;
+        case 6: hju_a<6>(a.DA, fn); break;
+        default: throw std::runtime_error("host-Jacobian unary edge: error dimension must be 1..6");
+      }
+      break;
+    default: throw std::runtime_error("unknown unary edge family");
+  }
+}
+template <class Fn>
+static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn);
+// every family, for the kernels that only need F::error (chi2): binary or unary
 template <class Fn>
 static void family_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
+  if (is_unary_family(family)) unary_dispatch(family, a, fn);
+  else binary_dispatch(family, a, fn);
+}
+template <class Fn>
+static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
   switch (family) {
     case FAM_BA: fn(FamilyBA{}); break;
     case FAM_BA_STEREO: fn(FamilyStereo{}); break;
@@ -1546,10 +1660,20 @@ void linearize(int family, const EdgeArgs& a, int ne, const int* h0, const int* 
                const long long* off_dst, const unsigned char* off_tr, double* off_base, double* off_slot, hipStream_t s) {
   if (ne <= 0) return;
   const unsigned g = grid_for(ne, 256);
-  family_dispatch(family, a, [&](auto fam) {
+  binary_dispatch(family, a, [&](auto fam) {
     using F = decltype(fam);
     hipLaunchKernelGGL(k_linearize<F>, g, 256, 0, s, mk(a), ne, h0, h1, slot0, slot1, off_dst, off_tr, off_base,
                        off_slot);
+  });
+  KERNEL_CHECK();
+}
+
+void linearize_unary(int family, const EdgeArgs& a, int ne, const int* h0, double* slot0, hipStream_t s) {
+  if (ne <= 0) return;
+  const unsigned g = grid_for(ne, 256);
+  unary_dispatch(family, a, [&](auto fam) {
+    using F = decltype(fam);
+    hipLaunchKernelGGL(k_linearize_unary<F>, g, 256, 0, s, mk(a), ne, h0, slot0);
   });
   KERNEL_CHECK();
 }

@@ -7,7 +7,13 @@
 
 namespace g2ohip {
 
-enum Family { FAM_NONE = 0, FAM_BA = 1, FAM_SE3 = 2, FAM_SE2 = 3, FAM_HOSTJ = 4, FAM_SE2XY = 5, FAM_BA_STEREO = 6 };
+enum Family {
+  FAM_NONE = 0, FAM_BA = 1, FAM_SE3 = 2, FAM_SE2 = 3, FAM_HOSTJ = 4, FAM_SE2XY = 5, FAM_BA_STEREO = 6,
+  // unary families (BaseUnaryEdge: one vertex, EdgeArgs::v1 / s1 null, DB = 0)
+  FAM_U_SE2 = 16, FAM_U_SE2XY = 17, FAM_U_XY = 18, FAM_U_SE3 = 19, FAM_U_XYZ = 20, FAM_U_HOSTJ = 21
+};
+inline bool is_unary_family(int f) { return f >= FAM_U_SE2 && f <= FAM_U_HOSTJ; }
+inline bool is_hostj_family(int f) { return f == FAM_HOSTJ || f == FAM_U_HOSTJ; }
 
 struct EdgeArgs {
   const int* v0;
@@ -29,6 +35,8 @@ void error(int family, const EdgeArgs& a, int ne, double* chi, hipStream_t s);
 // set, into off_slot (per-edge slots of blocks several edges share)
 void linearize(int family, const EdgeArgs& a, int ne, const int* h0, const int* h1, double* slot0, double* slot1,
                const long long* off_dst, const unsigned char* off_tr, double* off_base, double* off_slot, hipStream_t s);
+// unary edge groups (k_linearize_unary): one slot per edge in the arena of the vertex's dimension, nothing else
+void linearize_unary(int family, const EdgeArgs& a, int ne, const int* h0, double* slot0, hipStream_t s);
 // code[p] = slot index in `slots` (stride dim(dim+1)/2 + dim)
 void vertex_reduce(int dim, int nv, int lanes, const int* ptr, const int* code, const double* slots, double* H,
                    double* b, const int* boff, hipStream_t s);

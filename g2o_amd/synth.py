@@ -32,9 +32,15 @@ SEED = 20261015
 V_SE3_EXPMAP, V_XYZ, V_SE3_QUAT, V_SE2, V_XY = 1, 2, 3, 4, 5
 E_SE3_PROJECT_XYZ, E_SE3_QUAT, E_SE2, E_SE2_XY = 1, 2, 3, 5
 E_STEREO_SE3_PROJECT_XYZ = 6
+# unary edge types (priors): EdgeSet.v1 is None
+E_SE2_PRIOR, E_SE2_XY_PRIOR, E_XY_PRIOR, E_SE3_PRIOR, E_XYZ_PRIOR = 16, 17, 18, 19, 20
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2}
-MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3}
-ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3}
+MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
+            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3}
+ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
+           E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3}
+# the vertex type a unary edge type attaches to
+PRIOR_VERTEX = {E_SE2_PRIOR: V_SE2, E_SE2_XY_PRIOR: V_SE2, E_XY_PRIOR: V_XY, E_SE3_PRIOR: V_SE3_QUAT, E_XYZ_PRIOR: V_XYZ}
 
 
 @dataclasses.dataclass
@@ -50,10 +56,12 @@ class VertexSet:
 class EdgeSet:
     etype: int
     v0: np.ndarray      # int32 [n] vertex ids
-    v1: np.ndarray      # int32 [n]
+    v1: np.ndarray | None  # int32 [n]; None for a unary edge type (a prior)
     meas: np.ndarray    # float64 [n, MEAS_DIM]
     info: np.ndarray    # float64 [n, D, D]
-    params: np.ndarray | None = None  # float64 [n, 4] (fx fy cx cy) for projection edges, [n, 5] (+ bf) for stereo
+    # float64 [n, 4] (fx fy cx cy) for projection edges, [n, 5] (+ bf) for stereo, [n, 7] (offset x y z qx qy qz qw)
+    # or None (identity) for SE3 priors
+    params: np.ndarray | None = None
 
 
 @dataclasses.dataclass
@@ -529,3 +537,85 @@ def landmark_subset(prob: Problem, ids, name: str = "subset") -> Problem:
     ev = EdgeSet(e.etype, e.v0[m].copy(), e.v1[m].copy(), e.meas[m].copy(), e.info[m].copy(),
                  None if e.params is None else e.params[m].copy())
     return Problem(f"{prob.name}/{name}", [cams, pv], [ev], prob.pose_dim, prob.landmark_dim)
+
+
+# ---------------------------------------------------------------- unary edges (priors)
+def with_priors(prob: Problem, etype: int, every: int = 10, sigma=0.1, seed: int = SEED, drop_fixed: bool = False,
+                offset=None, start: int = 0, count: int | None = None) -> Problem:
+    """A copy of ``prob`` with priors of one unary type (E_SE2_PRIOR, E_SE2_XY_PRIOR, E_XY_PRIOR, E_SE3_PRIOR,
+    E_XYZ_PRIOR) on every ``every``-th vertex of the type it attaches to (from vertex ``start`` of that type's first
+    vertex set, at most ``count`` of them).  The measurement is the vertex's estimate (for E_SE3_PRIOR composed with
+    ``offset``, x y z qx qy qz qw, None = identity) plus Gaussian noise of ``sigma`` (a scalar or one value per error
+    component); the information is sigma^-1 (I + A)(I + A)^T sigma^-1 with A random per edge: SPD, not diagonal.
+    ``drop_fixed`` un-fixes every fixed vertex, so the priors alone hold the gauge.  ``prob`` itself is left
+    unchanged; the existing edge sets are shared, the vertex sets copied."""
+    vt = PRIOR_VERTEX[etype]
+    D, nm = ERR_DIM[etype], MEAS_DIM[etype]
+    rng = _rng(seed, 16 + etype)
+    verts = [VertexSet(v.vtype, v.ids.copy(), v.est.copy(),
+                       np.zeros_like(v.fixed) if drop_fixed else v.fixed.copy(), v.marginalized.copy())
+             for v in prob.vertices]
+    vs = next(v for v in verts if v.vtype == vt)
+    sel = np.arange(start, len(vs.ids), every)
+    if count is not None:
+        sel = sel[:count]
+    n = len(sel)
+    est = vs.est[sel]
+    sg = np.broadcast_to(np.asarray(sigma, np.float64), (D,))
+    noise = rng.standard_normal((n, D)) * sg
+    params = None
+    if etype == E_SE2_PRIOR:
+        meas = est + noise
+        meas[:, 2] = np.mod(meas[:, 2] + np.pi, 2 * np.pi) - np.pi
+    elif etype == E_SE2_XY_PRIOR:
+        meas = est[:, :2] + noise
+    elif etype in (E_XY_PRIOR, E_XYZ_PRIOR):
+        meas = est + noise
+    else:  # E_SE3_PRIOR: z = X * P * exp(noise)
+        R, t = quat_to_rot(est[:, 3:7]), est[:, 0:3]
+        if offset is not None:
+            off = np.asarray(offset, np.float64).reshape(7)
+            qo = off[3:7] / np.linalg.norm(off[3:7])
+            Ro = quat_to_rot(qo[None])[0]
+            t = t + R @ off[0:3]
+            R = R @ Ro
+            params = np.broadcast_to(np.concatenate([off[0:3], qo]), (n, 7)).copy()
+        ang = np.linalg.norm(noise[:, 3:6], axis=1)
+        dR = _axis_angle(np.where(ang[:, None] > 0, noise[:, 3:6], [1.0, 0.0, 0.0]), 2 * ang)
+        meas = np.concatenate([t + np.einsum("nij,nj->ni", R, noise[:, 0:3]), rot_to_quat(R @ dR)], axis=1)
+    A = np.eye(D) + 0.3 * rng.standard_normal((n, D, D))
+    info = np.einsum("nij,nkj->nik", A, A) / (sg[:, None] * sg[None, :])
+    info = 0.5 * (info + np.transpose(info, (0, 2, 1)))
+    es = EdgeSet(etype, vs.ids[sel].copy(), None, meas, info, params)
+    return Problem(prob.name + f"+prior{etype}x{n}", verts, list(prob.edges) + [es], prob.pose_dim, prob.landmark_dim)
+
+
+def twin_of(prob: Problem) -> Problem:
+    """The binary-only twin of a graph with priors: one fixed identity vertex I per needed type (an unused id each) and
+    every E_SE2_PRIOR(v; z) as E_SE2(I, v; z), every E_SE3_PRIOR(v; z) with the identity offset as E_SE3_QUAT(I, v; z),
+    every E_XY_PRIOR(l; z) as E_SE2_XY(I, l; z).  With I the identity the reference's binary edges give the prior's
+    error and its free-side Jacobian exactly, so H, b, chi2, lambda_0 and the hessian order are those of the prior
+    graph.  The other unary types have no twin (KeyError)."""
+    twin = {E_SE2_PRIOR: (E_SE2, V_SE2), E_SE3_PRIOR: (E_SE3_QUAT, V_SE3_QUAT), E_XY_PRIOR: (E_SE2_XY, V_SE2)}
+    next_id = max(int(v.ids.max()) for v in prob.vertices if len(v.ids)) + 1
+    ident: dict = {}
+    verts = list(prob.vertices)
+    edges = []
+    for es in prob.edges:
+        if es.v1 is not None:
+            edges.append(es)
+            continue
+        bt, ivt = twin[es.etype]
+        if es.etype == E_SE3_PRIOR and es.params is not None and not np.array_equal(
+                es.params, np.broadcast_to([0, 0, 0, 0, 0, 0, 1.0], es.params.shape)):
+            raise KeyError("an SE3 prior with an offset has no binary twin")
+        if ivt not in ident:
+            e0 = np.zeros((1, EST_DIM[ivt]))
+            if ivt == V_SE3_QUAT:
+                e0[0, 6] = 1.0
+            ident[ivt] = next_id
+            verts.append(VertexSet(ivt, np.array([next_id], np.int32), e0, np.ones(1, np.int32), np.zeros(1, np.int32)))
+            next_id += 1
+        iv = np.full(len(es.v0), ident[ivt], np.int32)
+        edges.append(EdgeSet(bt, iv, es.v0.copy(), es.meas.copy(), es.info.copy(), None))
+    return Problem(prob.name + "/twin", verts, edges, prob.pose_dim, prob.landmark_dim)

@@ -54,6 +54,22 @@ extern "C" {
  * g2ohip_set_host_jacobians; the device assembles, marginalises and solves. meas unused (may be NULL);
  * info D*D. Several host-J types (different D) may coexist with the device types in one graph. */
 #define G2OHIP_E_HOSTJ(D) (32 + (D)) /* D = error dimension, 1..6 */
+/* ---- unary edge types (BaseUnaryEdge, core/base_unary_edge.hpp:49-78): one vertex, v0; g2ohip_add_edges takes them
+ * with v1 == NULL (a non-NULL v1 is G2OHIP_ERR_ARG, as a NULL v1 is for the binary types). A unary edge on a fixed
+ * vertex is inactive (sparse_optimizer.cpp:241, allVerticesFixed): it adds nothing to chi2, H or b. A vertex whose
+ * only edges are unary is an active vertex like any other. A BA graph that also holds unary edges is assembled on the
+ * generic slot path, not the fused one (as a mixed monocular + stereo graph is). ---- */
+#define G2OHIP_E_SE2_PRIOR 16    /* EdgeSE2Prior, edge_se2_prior.h:39-77: v0 G2OHIP_V_SE2; meas x y theta; info 3x3 */
+#define G2OHIP_E_SE2_XY_PRIOR 17 /* EdgeSE2XYPrior, edge_se2_xyprior.h:39-71: v0 G2OHIP_V_SE2; meas x y; info 2x2 */
+#define G2OHIP_E_XY_PRIOR 18     /* EdgeXYPrior, edge_xy_prior.h: v0 G2OHIP_V_XY; meas x y; info 2x2 */
+#define G2OHIP_E_SE3_PRIOR 19    /* EdgeSE3Prior, edge_se3_prior.cpp:89-102: v0 G2OHIP_V_SE3_QUAT; meas x y z qx qy qz qw;
+                                    info 6x6; params: the sensor offset x y z qx qy qz qw per edge (n*7,
+                                    ParameterSE3Offset), NULL = identity */
+#define G2OHIP_E_XYZ_PRIOR 20    /* EdgeXYZPrior, edge_xyz_prior.cpp:63-70: v0 G2OHIP_V_XYZ; meas x y z; info 3x3 */
+/* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3 or 6 (pose-only reprojection, say): the
+ * host supplies the error and the Jacobian as for G2OHIP_E_HOSTJ, payload [e (D) | Ji (D x dim(v0))] row-major per
+ * edge. meas unused (may be NULL); info D*D. */
+#define G2OHIP_E_HOSTJ_UNARY(D) (48 + (D)) /* D = error dimension, 1..6 */
 
 /* robust kernels (robust_kernel_impl.cpp; RobustKernelFactory names) */
 #define G2OHIP_RK_NONE 0
@@ -113,12 +129,24 @@ int g2ohip_add_vertices(g2ohip_graph* g, int type, int n, const int* ids, const 
                         const int* marginalized);
 int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int* v1, const double* meas,
                      const double* info /* n * D*D row-major */, const double* params /* n*4, stereo n*5, or NULL */);
-/* params: the intrinsics of the projection types (G2OHIP_ERR_ARG when one of them gets NULL), NULL for the others. */
+/* params: the intrinsics of the projection types (G2OHIP_ERR_ARG when one of them gets NULL), the offsets of
+ * G2OHIP_E_SE3_PRIOR (n*7, or NULL: identity), NULL for the others. v1: NULL for the unary types (and only for them). */
 /* .g2o files do not carry G2OHIP_E_STEREO_SE3_PROJECT_XYZ: the reference's reader and writer for its tag
  * (EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP, types_six_dof_expmap.cpp:469-493) move four measurement values through a
  * 3-vector and no intrinsics. The loader skips the tag like any unknown one; g2ohip_save_g2o on a graph that holds
  * such edges writes nothing and returns G2OHIP_ERR_UNSUPPORTED (g2ohip_last_error says why). */
 int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
+/* g2ohip_load_g2o with flags. G2OHIP_LOAD_UNARY: the unary tags EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY, EDGE_PRIOR_XY,
+ * EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR and the PARAMS_SE3OFFSET lines the last one refers to are parsed (by the same
+ * parallel chunked parser) instead of skipped; an EDGE_SE3_PRIOR naming a parameter id the file does not define, a
+ * prior on a vertex of the wrong type or a short line fails the load (g2ohip_last_error says which). flags = 0 is
+ * g2ohip_load_g2o, which skips these tags like any unknown one. */
+#define G2OHIP_LOAD_UNARY 1u
+int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
+/* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
+ * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
+ * line per distinct offset ahead of the vertices; host-J unary edges are left out with a warning, as binary host-J
+ * ones are. */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
@@ -135,7 +163,8 @@ int g2ohip_minimal_state(g2ohip_graph* g, double* out);
 int g2ohip_set_robust_kernel(g2ohip_graph* g, int edge_type, int kind, double delta);
 /* Host-computed linearization of the G2OHIP_E_HOSTJ(D) edges of one type, in insertion order: per edge
  * [e (D) | Ji (D x dim(v0)) | Jj (D x dim(v1))], row-major, at the estimates the device holds (call after
- * g2ohip_set_estimates, before g2ohip_solver_build_system). The J_host_fallback of SURVEY.md 8b. */
+ * g2ohip_set_estimates, before g2ohip_solver_build_system). The J_host_fallback of SURVEY.md 8b.
+ * G2OHIP_E_HOSTJ_UNARY(D) edges: per edge [e (D) | Ji (D x dim(v0))]. */
 int g2ohip_set_host_jacobians(g2ohip_graph* g, int edge_type, const double* payload);
 /* Callback for the device-resident loops (g2ohip_optimize / g2ohip_chi2) when host-J edges exist: fill the
  * payload of every edge of `edge_type` at the current estimates (read them with g2ohip_get_estimates);
@@ -143,11 +172,13 @@ int g2ohip_set_host_jacobians(g2ohip_graph* g, int edge_type, const double* payl
 typedef int (*g2ohip_host_edge_fn)(void* user, int edge_type, int with_jacobians, double* payload);
 int g2ohip_set_host_edge_callback(g2ohip_graph* g, g2ohip_host_edge_fn fn, void* user);
 /* Length in doubles of the payload buffer of a host-J edge type (the `payload` the callback fills and
- * g2ohip_set_host_jacobians reads): sum over its edges of D * (1 + dim(v0) + dim(v1)). A callback must write exactly
- * this many doubles. */
+ * g2ohip_set_host_jacobians reads): sum over its edges of D * (1 + dim(v0) + dim(v1)), for a unary host-J type of
+ * D * (1 + dim(v0)). A callback must write exactly this many doubles. */
 long long g2ohip_host_payload_len(g2ohip_graph* g, int edge_type);
 
-/* OptimizationAlgorithmFactory::construct by name; default "lm_hip_var" */
+/* OptimizationAlgorithmFactory::construct by name; default "lm_hip_var". "lm_pcg6_3_eigen" (matrix-free CGLS on the
+ * Jacobian of BA edges) does not take unary edges: building the structure of such a graph under it returns
+ * G2OHIP_ERR_UNSUPPORTED. */
 int g2ohip_set_algorithm(g2ohip_graph* g, const char* name);
 /* SparseOptimizer::initializeOptimization(0): active edges/vertices, index mapping */
 int g2ohip_initialize(g2ohip_graph* g);
@@ -335,7 +366,8 @@ void g2ohip_kernel_timing_only(g2ohip_graph* g, const char* name);
 /* G2OBatchStatistics timers: 0 none, 1 timeLinearSolution only (2 events per LM trial), 2 (default)
  * every stage (timeSchurComplement, timeNumericDecomposition, timeLinearSolver, timeUpdate, timeQuadraticForm) */
 void g2ohip_set_stats_level(g2ohip_graph* g, int level);
-/* per-kernel-class average device time (ms) since the timer was enabled; classes: "linearize", "vreduce",
+/* per-kernel-class average device time (ms) since the timer was enabled; classes: "linearize", "linearize_unary"
+ * (the unary edge groups' launches, timed apart from the binary groups'), "vreduce",
  * "schur_dinv", "schur_diag", "schur_rows", "chol_factor", "chol_solve", "backsub", "error", "oplus" */
 double g2ohip_kernel_ms(g2ohip_graph* g, const char* name);
 long long g2ohip_kernel_count(g2ohip_graph* g, const char* name);
