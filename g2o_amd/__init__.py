@@ -43,6 +43,12 @@ class Config(C.Structure):
 E_STEREO_SE3_PROJECT_XYZ = 6
 
 
+# slam3d landmark edges (include/g2o_hip.h G2OHIP_E_SE3_XYZ*): v0 the VertexSE3 pose, v1 the point; meas x y z /
+# u v depth / u v 1/depth; params the sensor offset x y z qx qy qz qw (XYZ: or None, the identity), the camera types'
+# followed by fx fy cx cy
+E_SE3_XYZ, E_SE3_XYZ_DEPTH, E_SE3_XYZ_DISPARITY = 7, 8, 9
+
+
 # edge types the device does not know: host-supplied error + Jacobians (include/g2o_hip.h G2OHIP_E_HOSTJ)
 def E_HOSTJ(D: int) -> int:
     return 32 + D
@@ -59,6 +65,7 @@ def E_HOSTJ_UNARY(D: int) -> int:
 
 # g2ohip_load_g2o_ex flags
 LOAD_UNARY = 1
+LOAD_SLAM3D = 2
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -384,11 +391,13 @@ class SparseOptimizer:
         est = np.ascontiguousarray(est, np.float64)
         _check(lib().g2ohip_set_estimates(self.h, vtype, _p(est)), "set_estimates")
 
-    def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False):
+    def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
-        EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), which are skipped otherwise."""
-        _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), LOAD_UNARY if unary else 0),
-               "load")
+        EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
+        (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
+        PARAMS_CAMERACALIB); both are skipped otherwise."""
+        flags = (LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0)
+        _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:
         return int(lib().g2ohip_num_vertices(self.h))

@@ -5,6 +5,7 @@
 //   EdgeSE3 (QUAT)     types/slam3d/edge_se3.cpp:77-103, isometry3d_gradients.h:194-260
 //   EdgeSE2            types/slam2d/edge_se2.h:46-52, edge_se2.cpp:77-103
 //   EdgeSE2PointXY     types/slam2d/edge_se2_pointxy.h:41-75, edge_se2_pointxy.cpp:63-87
+//   EdgeSE3PointXYZ, ...Depth, ...Disparity  types/slam3d/edge_se3_pointxyz.cpp:100-135 and its two siblings
 //   unary priors       types/slam2d/edge_se2_prior.h:39-77, edge_se2_xyprior.h:39-71, edge_xy_prior.h,
 //                      types/slam3d/edge_se3_prior.cpp:89-102 (isometry3d_gradients.h:265-325), edge_xyz_prior.cpp:63-70
 //   oplus             types_six_dof_expmap.h:97-100 (SE3Quat::exp * T, se3quat.h:217-257),
@@ -240,7 +241,7 @@ struct EdgeData {
   const int* v1;
   const double* meas;       // per-edge measurement payload (family-specific stride; host-J: e | Ji | Jj)
   const double* info;       // packed upper information (family-specific stride)
-  const double* params;     // BA intrinsics [4] (stereo: [5], + bf) or nullptr
+  const double* params;     // BA intrinsics [4] (stereo: [5], + bf), slam3d inverse offset [12] (+ fx fy cx cy) or nullptr
   const double* s0;         // state array of vertex-0 type
   const double* s1;         // state array of vertex-1 type
   int rk;                   // robust kernel of the edge set (G2OHIP_RK_*), 0 none
@@ -672,6 +673,115 @@ struct FamilySE2XY {
     Jj[3] = c;
   }
 };
+
+// ---- slam3d landmark edges: v0 = VertexSE3 pose (Isometry3 [12], dim 6), v1 = point (3); meas 3, info packed 6.
+//   EdgeSE3PointXYZ           types/slam3d/edge_se3_pointxyz.cpp:100-135            meas x y z (sensor frame)
+//   EdgeSE3PointXYZDepth      types/slam3d/edge_se3_pointxyz_depth.cpp:91-138       meas u v depth
+//   EdgeSE3PointXYZDisparity  types/slam3d/edge_se3_pointxyz_disparity.cpp          meas u v 1/depth
+// With X = (R, t) the pose, P = (Rp, tp) the sensor offset and p the point: Zc = R^T (p - t) (the cache's w2l),
+// pn = Rp^T (Zc - tp) (w2n). Under VertexSE3's oplus X * (dt, dq), rotation ~ I + 2 [dq]x,
+//   d Zc = [ -I | 2 [Zc]x | R^T ] (dt, dq, dp)   (3 x 9, the last three columns the point's).
+// XYZ: e = pn - z, J = Rp^T dZc. Depth: pi = K pn, e = (pi.x / pi.z, pi.y / pi.z, pi.z) - z; with J' = K Rp^T dZc the
+// rows 0-1 are (J'_01 pi.z - pi.xy J'_2) / pi.z^2 and row 2 is J'_2. Disparity: as Depth with e.z = 1 / pi.z - z.z and
+// row 2 = -J'_2 / pi.z^2.
+// Parameter record (params, one shared record when EdgeData::ue bit 1 is set: the usual graph has one sensor for all
+// its edges): the inverse offset P^-1 as an isometry [Rp^T row-major (9) | -Rp^T tp (3)], made on the host; Depth and
+// Disparity append fx fy cx cy (16 doubles). ----
+enum { SLAM3D_XYZ = 0, SLAM3D_DEPTH = 1, SLAM3D_DISPARITY = 2 };
+template <int MODE>
+struct FamilySlam3d {
+  static constexpr int D = 3, DA = 6, DB = 3, MEAS = 3, INFO = 6, PAR = MODE == SLAM3D_XYZ ? 12 : 16;
+  // Zc and the sensor-frame point pn
+  DI static void to_sensor(const double* X, const double* p, const double* Pi, double* Zc, double* pn) {
+    const double d0 = p[0] - X[9], d1 = p[1] - X[10], d2 = p[2] - X[11];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) Zc[i] = X[i] * d0 + X[3 + i] * d1 + X[6 + i] * d2;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pn[i] = Pi[i * 3] * Zc[0] + Pi[i * 3 + 1] * Zc[1] + Pi[i * 3 + 2] * Zc[2] + Pi[9 + i];
+  }
+  // the error from pn; pi = K pn for the camera modes (pi = pn for XYZ)
+  DI static void residual(const double* Pi, const double* pn, const double* m, double* pi, double* err) {
+    if (MODE == SLAM3D_XYZ) {
+      pi[0] = pn[0]; pi[1] = pn[1]; pi[2] = pn[2];
+      err[0] = pn[0] - m[0]; err[1] = pn[1] - m[1]; err[2] = pn[2] - m[2];
+    } else {
+      const double fx = Pi[12], fy = Pi[13], cx = Pi[14], cy = Pi[15];
+      pi[0] = fx * pn[0] + cx * pn[2];
+      pi[1] = fy * pn[1] + cy * pn[2];
+      pi[2] = pn[2];
+      err[0] = pi[0] / pi[2] - m[0];
+      err[1] = pi[1] / pi[2] - m[1];
+      err[2] = (MODE == SLAM3D_DEPTH ? pi[2] : 1.0 / pi[2]) - m[2];
+    }
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* x = d.s0 + (size_t)d.v0[e] * 12;
+    const double* pt = d.s1 + (size_t)d.v1[e] * 3;
+    const double* Pi = param_rec(d, e, PAR);
+    const double* mp = d.meas + (size_t)e * 3;
+    double X[12], Zc[3], pn[3], pi[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) X[k] = x[k];
+    const double p[3] = {pt[0], pt[1], pt[2]}, m[3] = {mp[0], mp[1], mp[2]};
+    to_sensor(X, p, Pi, Zc, pn);
+    residual(Pi, pn, m, pi, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    const double* x = d.s0 + (size_t)d.v0[e] * 12;
+    const double* pt = d.s1 + (size_t)d.v1[e] * 3;
+    const double* Pi = param_rec(d, e, PAR);
+    const double* mp = d.meas + (size_t)e * 3;
+    double X[12], Zc[3], pn[3], pi[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) X[k] = x[k];
+    const double p[3] = {pt[0], pt[1], pt[2]}, m[3] = {mp[0], mp[1], mp[2]};
+    to_sensor(X, p, Pi, Zc, pn);
+    residual(Pi, pn, m, pi, err);
+    // M = Rp^T (XYZ) or K Rp^T (camera modes), then J' = M [ -I | 2 [Zc]x | R^T ]
+    double M[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (MODE == SLAM3D_XYZ) {
+        M[c] = Pi[c]; M[3 + c] = Pi[3 + c];
+      } else {
+        M[c] = Pi[12] * Pi[c] + Pi[14] * Pi[6 + c];
+        M[3 + c] = Pi[13] * Pi[3 + c] + Pi[15] * Pi[6 + c];
+      }
+      M[6 + c] = Pi[6 + c];
+    }
+    double Jp[27];  // 3 x 9 row-major
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const double m0 = M[r * 3], m1 = M[r * 3 + 1], m2 = M[r * 3 + 2];
+      Jp[r * 9 + 0] = -m0; Jp[r * 9 + 1] = -m1; Jp[r * 9 + 2] = -m2;
+      Jp[r * 9 + 3] = 2 * (m1 * Zc[2] - m2 * Zc[1]);  // row of M times [Zc]x = m x Zc
+      Jp[r * 9 + 4] = 2 * (m2 * Zc[0] - m0 * Zc[2]);
+      Jp[r * 9 + 5] = 2 * (m0 * Zc[1] - m1 * Zc[0]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Jp[r * 9 + 6 + c] = m0 * X[c * 3] + m1 * X[c * 3 + 1] + m2 * X[c * 3 + 2];
+    }
+    if (MODE != SLAM3D_XYZ) {
+      const double iz2 = 1.0 / (pi[2] * pi[2]);
+#pragma unroll
+      for (int c = 0; c < 9; ++c) {
+        const double j2 = Jp[18 + c];
+        Jp[c] = iz2 * (Jp[c] * pi[2] - pi[0] * j2);
+        Jp[9 + c] = iz2 * (Jp[9 + c] * pi[2] - pi[1] * j2);
+        if (MODE == SLAM3D_DISPARITY) Jp[18 + c] = -j2 * iz2;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) Ji[r * 6 + c] = Jp[r * 9 + c];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Jj[r * 3 + c] = Jp[r * 9 + 6 + c];
+    }
+  }
+};
+using FamilySE3XYZ = FamilySlam3d<SLAM3D_XYZ>;
+using FamilySE3XYZDepth = FamilySlam3d<SLAM3D_DEPTH>;
+using FamilySE3XYZDisparity = FamilySlam3d<SLAM3D_DISPARITY>;
 
 // ---- host-Jacobian edges (an edge type the device does not know): the host's linearizeOplus
 // (base_binary_edge.hpp:198-266 numeric, or the type's own analytic one) supplies, per edge, the error and

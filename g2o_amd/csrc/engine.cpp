@@ -49,6 +49,8 @@ static bool is_hostj_binary(int e) { return e > G2OHIP_E_HOSTJ(0) && e <= G2OHIP
 static bool is_hostj_unary(int e) { return e > G2OHIP_E_HOSTJ_UNARY(0) && e <= G2OHIP_E_HOSTJ_UNARY(6); }
 // host-Jacobian edge types of either arity
 static bool is_hostj(int e) { return is_hostj_binary(e) || is_hostj_unary(e); }
+// the slam3d landmark edges: EdgeSE3PointXYZ, ...Depth, ...Disparity
+static bool is_slam3d_type(int e) { return e >= G2OHIP_E_SE3_XYZ && e <= G2OHIP_E_SE3_XYZ_DISPARITY; }
 // BaseUnaryEdge types: the five priors and the unary host-J escape
 static bool is_unary_type(int e) { return (e >= G2OHIP_E_SE2_PRIOR && e <= G2OHIP_E_XYZ_PRIOR) || is_hostj_unary(e); }
 int edge_dim(int e) {
@@ -56,6 +58,7 @@ int edge_dim(int e) {
   if (is_hostj_unary(e)) return e - G2OHIP_E_HOSTJ_UNARY(0);
   switch (e) {
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: case G2OHIP_E_SE2_PRIOR: case G2OHIP_E_XYZ_PRIOR: return 3;
+    case G2OHIP_E_SE3_XYZ: case G2OHIP_E_SE3_XYZ_DEPTH: case G2OHIP_E_SE3_XYZ_DISPARITY: return 3;
     case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: return 2;
     case G2OHIP_E_SE3_PRIOR: return 6;
   }
@@ -65,12 +68,15 @@ int edge_meas_dim(int e) {
   if (is_hostj(e)) return 0;
   if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR) return 2;
   if (e == G2OHIP_E_SE3_PRIOR) return 7;
+  if (is_slam3d_type(e)) return 3;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
 }
 // doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
-// sensor offset x y z qx qy qz qw (optional: NULL = identity)
+// sensor offset x y z qx qy qz qw (optional: NULL = identity), as EdgeSE3PointXYZ's; the slam3d camera types' offset
+// followed by fx fy cx cy
 int edge_param_dim(int e) {
-  if (e == G2OHIP_E_SE3_PRIOR) return 7;
+  if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_XYZ) return 7;
+  if (e == G2OHIP_E_SE3_XYZ_DEPTH || e == G2OHIP_E_SE3_XYZ_DISPARITY) return 11;
   return e == G2OHIP_E_SE3_PROJECT_XYZ ? 4 : (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ ? 5 : 0);
 }
 static int family_of(int etype, int& vtA, int& vtB);
@@ -1187,7 +1193,7 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   const bool unary = is_unary_type(type);
   if (unary != (v1 == nullptr) && (n > 0 || v1)) return G2OHIP_ERR_ARG;  // v1 is NULL for the unary types, only for them
   const int np = edge_param_dim(type);
-  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR) return G2OHIP_ERR_ARG;
+  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ) return G2OHIP_ERR_ARG;
   const int nm = edge_meas_dim(type);
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
@@ -1208,7 +1214,7 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   if (nm > 0) es->meas.insert(es->meas.end(), meas, meas + (size_t)n * nm);
   es->info.insert(es->info.end(), info, info + (size_t)n * D * D);
   if (np > 0 && params) es->params.insert(es->params.end(), params, params + (size_t)n * np);
-  if (np > 0 && !params) {  // EdgeSE3Prior without an offset parameter: the identity
+  if (np > 0 && !params) {  // EdgeSE3Prior / EdgeSE3PointXYZ without an offset parameter: the identity
     const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
     for (int k = 0; k < n; ++k) es->params.insert(es->params.end(), ident, ident + 7);
   }
@@ -1263,8 +1269,10 @@ int Engine::set_host_callback(g2ohip_host_edge_fn fn, void* user) {
 // are skipped with one warning per tag (:455-460); FIX lines fix vertices after loading (:409-417).
 namespace {
 struct ParsedVertex { int type, id; double est[7]; };
-struct ParsedEdge { int type, a, b; double m[7], info[36], p[7]; };  // unary: b = -1, or the SE3 prior's parameter id
-struct ParsedParam { int id; double v[7]; };                        // PARAMS_SE3OFFSET id x y z qx qy qz qw
+// unary: b = -1, or the SE3 prior's parameter id; pid: the slam3d landmark edges' parameter id
+struct ParsedEdge { int type, a, b; double m[7], info[36], p[11]; int pid = -1; };
+// PARAMS_SE3OFFSET id x y z qx qy qz qw; camera: PARAMS_CAMERACALIB, the same followed by fx fy cx cy
+struct ParsedParam { int id; double v[11]; bool camera = false; };
 struct ParsedChunk {
   std::vector<ParsedVertex> verts;
   std::vector<ParsedEdge> edges;
@@ -1297,8 +1305,9 @@ struct Cursor {
   }
   bool more() { ws(); return p < e; }
 };
-// unary: the unary edge tags and PARAMS_SE3OFFSET are parsed (G2OHIP_LOAD_UNARY), else skipped as unknown tags
-void parse_chunk(const char* b, const char* e, bool unary, ParsedChunk& out) {
+// unary: the unary edge tags and PARAMS_SE3OFFSET are parsed (G2OHIP_LOAD_UNARY), else skipped as unknown tags;
+// slam3d: VERTEX_TRACKXYZ, PARAMS_SE3OFFSET, PARAMS_CAMERACALIB and the three landmark edge tags (G2OHIP_LOAD_SLAM3D)
+void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1318,8 +1327,9 @@ void parse_chunk(const char* b, const char* e, bool unary, ParsedChunk& out) {
         std::memcpy(v.est, w, sizeof w);
       }
       out.verts.push_back(v);
-    } else if (tag == "VERTEX_XYZ" || tag == "VERTEX_SE2") {
-      ParsedVertex v{tag == "VERTEX_XYZ" ? G2OHIP_V_XYZ : G2OHIP_V_SE2, c.i(), {}};
+    } else if (tag == "VERTEX_XYZ" || tag == "VERTEX_SE2" || (slam3d && tag == "VERTEX_TRACKXYZ")) {
+      // (VERTEX_TRACKXYZ: VertexPointXYZ, vertex_pointxyz.cpp: x y z)
+      ParsedVertex v{tag == "VERTEX_SE2" ? G2OHIP_V_SE2 : G2OHIP_V_XYZ, c.i(), {}};
       for (int k = 0; k < 3; ++k) v.est[k] = c.d();
       out.verts.push_back(v);
     } else if (tag == "VERTEX_XY") {  // vertex_point_xy.cpp:46-50
@@ -1354,10 +1364,26 @@ void parse_chunk(const char* b, const char* e, bool unary, ParsedChunk& out) {
       for (int r = 0; r < D; ++r)
         for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
       out.edges.push_back(ed);
-    } else if (unary && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
+    } else if ((unary || slam3d) && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
       ParsedParam pp{c.i(), {}};
+      for (int k = 0; k < 7; ++k) pp.v[k] = c.d();
+      out.params.push_back(pp);
+    } else if (slam3d && tag == "PARAMS_CAMERACALIB") {  // parameter_camera.cpp:62-85: id, offset, fx fy cx cy
+      ParsedParam pp{c.i(), {}, true};
       for (double& x : pp.v) x = c.d();
       out.params.push_back(pp);
+    } else if (slam3d && (tag == "EDGE_SE3_TRACKXYZ" || tag == "EDGE_PROJECT_DEPTH" || tag == "EDGE_PROJECT_DISPARITY")) {
+      // edge_se3_pointxyz.cpp:57-86 and its siblings: pose, point, parameter id, measurement, upper triangle of the
+      // information row-wise
+      ParsedEdge ed{tag == "EDGE_SE3_TRACKXYZ"    ? G2OHIP_E_SE3_XYZ
+                    : tag == "EDGE_PROJECT_DEPTH" ? G2OHIP_E_SE3_XYZ_DEPTH
+                                                  : G2OHIP_E_SE3_XYZ_DISPARITY,
+                    c.i(), c.i(), {}, {}, {}};
+      ed.pid = c.i();
+      for (int k = 0; k < 3; ++k) ed.m[k] = c.d();
+      for (int r = 0; r < 3; ++r)
+        for (int q = r; q < 3; ++q) ed.info[r * 3 + q] = ed.info[q * 3 + r] = c.d();
+      out.edges.push_back(ed);
     } else if (unary && (tag == "EDGE_PRIOR_SE2" || tag == "EDGE_PRIOR_SE2_XY" || tag == "EDGE_PRIOR_XY" ||
                          tag == "EDGE_POINTXYZ_PRIOR" || tag == "EDGE_SE3_PRIOR")) {
       // edge_se2_prior.cpp:43-55, edge_se2_xyprior.cpp:36-48, edge_xy_prior.cpp:45-57, edge_xyz_prior.cpp:37-52,
@@ -1385,7 +1411,7 @@ void parse_chunk(const char* b, const char* e, bool unary, ParsedChunk& out) {
 }  // namespace
 
 int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
-  const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0;
+  const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1413,7 +1439,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
-      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, chunks[t]); });
+      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1457,7 +1483,8 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
     ea.clear(); eb.clear(); em.clear(); ei.clear(); ep.clear();
     return r;
   };
-  // PARAMS_SE3OFFSET records by id (the parameters of the file's EDGE_SE3_PRIOR lines)
+  // PARAMS_SE3OFFSET / PARAMS_CAMERACALIB records by id (the parameters of the file's EDGE_SE3_PRIOR lines and of its
+  // slam3d landmark edges)
   std::unordered_map<int, const ParsedParam*> offsets;
   for (auto& c : chunks)
     for (auto& pp : c.params) offsets[pp.id] = &pp;
@@ -1478,12 +1505,22 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                 std::to_string(ed.a) + ", which is missing or of the wrong type");
         if (ed.type == G2OHIP_E_SE3_PRIOR) {
           auto po = offsets.find(ed.b);
-          if (po == offsets.end())
+          if (po == offsets.end() || po->second->camera)
             throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: EDGE_SE3_PRIOR on vertex " + std::to_string(ed.a) +
                                                   " names parameter id " + std::to_string(ed.b) +
                                                   ", which no PARAMS_SE3OFFSET line defines");
           std::memcpy(ed.p, po->second->v, sizeof(double) * 7);
         }
+      }
+      if (is_slam3d_type(ed.type)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
+        const bool cam = ed.type != G2OHIP_E_SE3_XYZ;
+        auto po = offsets.find(ed.pid);
+        if (po == offsets.end() || po->second->camera != cam)
+          throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: landmark edge (type " + std::to_string(ed.type) + ") " +
+                                                std::to_string(ed.a) + " -> " + std::to_string(ed.b) +
+                                                " names parameter id " + std::to_string(ed.pid) + ", which no " +
+                                                (cam ? "PARAMS_CAMERACALIB" : "PARAMS_SE3OFFSET") + " line defines");
+        std::memcpy(ed.p, po->second->v, sizeof(double) * (cam ? 11 : 7));
       }
       ea.push_back(ed.a);
       eb.push_back(ed.b);
@@ -1544,23 +1581,39 @@ int Engine::save(const char* path) {
   };
   // parameters first (optimizable_graph.cpp:663-667): one PARAMS_SE3OFFSET line per distinct offset of the SE3 priors,
   // ids in first-seen order; prior_pid[k] = the id edge k's line names
+  // The slam3d landmark edges' offsets and cameras (PARAMS_CAMERACALIB, parameter_camera.cpp:75-85) follow in the
+  // same id space; pids[set][k] = the id edge k of that set names. Track points: the G2OHIP_V_XYZ vertices such an
+  // edge touches, written as VERTEX_TRACKXYZ.
   std::vector<int> prior_pid;
-  if (const HEdgeSet* ps = hg.set_of(G2OHIP_E_SE3_PRIOR)) {
-    std::vector<const double*> distinct;
-    prior_pid.resize(ps->ev0.size());
-    for (size_t k = 0; k < ps->ev0.size(); ++k) {
-      const double* p = ps->params.data() + k * 7;
-      size_t j = 0;
-      while (j < distinct.size() && std::memcmp(distinct[j], p, sizeof(double) * 7) != 0) ++j;
-      if (j == distinct.size()) {
-        distinct.push_back(p);
-        LineBuf& L = out[0];
-        L.tag("PARAMS_SE3OFFSET"); L.i((int)j);
-        for (int q = 0; q < 7; ++q) L.d(p[q]);
-        L.nl();
+  std::vector<std::vector<int>> pids(hg.esets.size());
+  std::vector<char> track(hg.verts.size(), 0);
+  {
+    std::vector<std::pair<const double*, int>> distinct;  // record, its length (7 offset, 11 camera)
+    auto ids_of = [&](const HEdgeSet& es, std::vector<int>& ids) {
+      const int np = edge_param_dim(es.type);
+      ids.resize(es.ev0.size());
+      for (size_t k = 0; k < es.ev0.size(); ++k) {
+        const double* p = es.params.data() + k * np;
+        size_t j = 0;
+        while (j < distinct.size() &&
+               (distinct[j].second != np || std::memcmp(distinct[j].first, p, sizeof(double) * np) != 0))
+          ++j;
+        if (j == distinct.size()) {
+          distinct.emplace_back(p, np);
+          LineBuf& L = out[0];
+          L.tag(np == 7 ? "PARAMS_SE3OFFSET" : "PARAMS_CAMERACALIB"); L.i((int)j);
+          for (int q = 0; q < np; ++q) L.d(p[q]);
+          L.nl();
+        }
+        ids[k] = (int)j;
       }
-      prior_pid[k] = (int)j;
-    }
+    };
+    if (const HEdgeSet* ps = hg.set_of(G2OHIP_E_SE3_PRIOR)) ids_of(*ps, prior_pid);
+    for (size_t si = 0; si < hg.esets.size(); ++si)
+      if (is_slam3d_type(hg.esets[si].type)) {
+        ids_of(hg.esets[si], pids[si]);
+        for (int v : hg.esets[si].ev1) track[v] = 1;
+      }
     flush();
   }
   parallel_ranges(hg.verts.size(), nt, [&](int t, size_t lo, size_t hi) {
@@ -1574,7 +1627,7 @@ int Engine::save(const char* path) {
       int ne = 3;
       switch (v.type) {
         case G2OHIP_V_SE3_EXPMAP: L.tag("VERTEX_SE3:EXPMAP"); se3quat_inverse(e, c); std::memcpy(e, c, sizeof c); ne = 7; break;
-        case G2OHIP_V_XYZ: L.tag("VERTEX_XYZ"); break;
+        case G2OHIP_V_XYZ: L.tag(track[k] ? "VERTEX_TRACKXYZ" : "VERTEX_XYZ"); break;
         case G2OHIP_V_SE3_QUAT: L.tag("VERTEX_SE3:QUAT"); ne = 7; break;
         case G2OHIP_V_SE2: L.tag("VERTEX_SE2"); break;
         case G2OHIP_V_XY: L.tag("VERTEX_XY"); ne = 2; break;
@@ -1586,7 +1639,8 @@ int Engine::save(const char* path) {
     }
   });
   flush();
-  for (const HEdgeSet& es : hg.esets) {
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    const HEdgeSet& es = hg.esets[si];
     if (is_hostj(es.type)) {  // the device does not know the host type's tag: the host saves those edges
       fprintf(stderr, "g2o_hip save: %zu host-Jacobian edges (type %d) not written\n", es.ev0.size(), es.type);
       continue;
@@ -1610,6 +1664,13 @@ int Engine::save(const char* path) {
           if (es.type == G2OHIP_E_SE3_PRIOR) L.i(prior_pid[k]);
           for (int q = 0; q < nm; ++q) L.d(m[q]);
           for (int r = 0; r < D; ++r) for (int q = r; q < D; ++q) L.d(I[r * D + q]);
+        } else if (is_slam3d_type(es.type)) {  // edge_se3_pointxyz.cpp:88-96 and its siblings: the parameter id first
+          L.tag(es.type == G2OHIP_E_SE3_XYZ         ? "EDGE_SE3_TRACKXYZ"
+                : es.type == G2OHIP_E_SE3_XYZ_DEPTH ? "EDGE_PROJECT_DEPTH"
+                                                    : "EDGE_PROJECT_DISPARITY");
+          L.i(a); L.i(b); L.i(pids[si][k]);
+          for (int q = 0; q < 3; ++q) L.d(m[q]);
+          for (int r = 0; r < 3; ++r) for (int q = r; q < 3; ++q) L.d(I[r * 3 + q]);
         } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
           L.tag("EDGE_SE2_XY"); L.i(a); L.i(b);
           L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
@@ -1773,6 +1834,9 @@ static int family_of(int etype, int& vtA, int& vtB) {
     case G2OHIP_E_SE3_QUAT: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3;
     case G2OHIP_E_SE2: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2;
     case G2OHIP_E_SE2_XY: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY;
+    case G2OHIP_E_SE3_XYZ: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ;
+    case G2OHIP_E_SE3_XYZ_DEPTH: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DEPTH;
+    case G2OHIP_E_SE3_XYZ_DISPARITY: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DISPARITY;
     // unary types: vtB = 0 (no second vertex)
     case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
     case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
@@ -2032,8 +2096,12 @@ void Engine::setup_edges_device() {
       case FAM_U_SE2: case FAM_U_XYZ: mmeas = 3; break;
       case FAM_U_SE2XY: case FAM_U_XY: mmeas = 2; break;
       case FAM_U_SE3: mmeas = 24; break;
+      case FAM_SE3_XYZ: case FAM_SE3_XYZ_DEPTH: case FAM_SE3_XYZ_DISPARITY: mmeas = 3; break;
     }
-    const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type) : 0;
+    // device parameter record: the BA intrinsics as given; slam3d: the inverse offset as an isometry (12), the camera
+    // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp)
+    const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type)
+                     : g.family == FAM_SE3_XYZ ? 12 : (is_slam3d_family(g.family) ? 16 : 0);
     std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
         params(mpar ? (size_t)gne * mpar : 1);
     for (int k = 0; k < gne; ++k) {
@@ -2076,6 +2144,13 @@ void Engine::setup_edges_device() {
         mo[2] = th;
       } else if (g.family == FAM_SE2XY) {
         mo[0] = m[0]; mo[1] = m[1];
+      } else if (is_slam3d_family(g.family)) {  // the offset (x y z qx qy qz qw) -> its inverse [Rp^T | -Rp^T tp]
+        for (int j = 0; j < 3; ++j) mo[j] = m[j];
+        const int np = edge_param_dim(es.type);
+        const double* p = es.params.data() + (size_t)e * np;
+        double* po = params.data() + (size_t)k * mpar;
+        iso_inverse_of(p, po);
+        for (int j = 7; j < np; ++j) po[12 + j - 7] = p[j];
       }
       const double* I = es.info.data() + (size_t)e * D * D;
       double* io = info.data() + (size_t)k * minfo;
@@ -2089,7 +2164,7 @@ void Engine::setup_edges_device() {
        // record instead of 24 + 32 bytes per edge (G2OHIP_UNIFORM_RECORDS=0 keeps per-edge records, A/B)
       const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
       g.ue = 0;
-      if (is_ba_family(g.family) && gne > 1 && !(ev && atoi(ev) == 0)) {
+      if ((is_ba_family(g.family) || is_slam3d_family(g.family)) && gne > 1 && !(ev && atoi(ev) == 0)) {
         auto uniform = [&](const std::vector<double>& v, int st) {
           for (int k = 1; k < gne; ++k)
             if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
@@ -2451,6 +2526,12 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     int r = initialize();
     if (r) return r;
   }
+  if (use_cgls())
+    for (const HEdgeSet& es : hg.esets)
+      if (is_slam3d_type(es.type) && !es.ev0.empty())
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the slam3d "
+                          "landmark edges (edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
   if (use_cgls() && has_unary_)
     throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                       "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take unary edges: the "
@@ -4153,6 +4234,11 @@ double Engine::kernel_bytes(const std::string& name) const {
         const int D = g.D, np = g.family == FAM_BA ? 4 : 5;
         by += g.ne * ((D + D * (D + 1) / 2 + np) * 8.0 + 8 + (ba_fused ? 0.0 : 9.0 + 27.0) * 8 + ob) +
               (ba_fused ? local_lm.size() * 12 * 8.0 : 0.0);
+      } else if (is_slam3d_family(g.family)) {
+        // slam3d landmark edges (slot path): measurement 3 + packed information 6 (one record when uniform), the
+        // parameter record 12 / 16 (likewise), two vertex indices, the pose slot 27, the point slot 9, the Hpl block
+        const int np = g.family == FAM_SE3_XYZ ? 12 : 16;
+        by += g.ne * ((3 + ((g.ue & 1) ? 0 : 6) + ((g.ue & 2) ? 0 : np)) * 8.0 + 8 + (27.0 + 9.0) * 8 + pb);
       }
     return by;
   }

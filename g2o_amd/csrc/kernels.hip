@@ -1631,6 +1631,9 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_SE3: fn(FamilySE3{}); break;
     case FAM_SE2: fn(FamilySE2{}); break;
     case FAM_SE2XY: fn(FamilySE2XY{}); break;
+    case FAM_SE3_XYZ: fn(FamilySE3XYZ{}); break;
+    case FAM_SE3_XYZ_DEPTH: fn(FamilySE3XYZDepth{}); break;
+    case FAM_SE3_XYZ_DISPARITY: fn(FamilySE3XYZDisparity{}); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;

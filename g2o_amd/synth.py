@@ -17,6 +17,9 @@ Recipes:
     each point observed by exactly k cameras of a window of W consecutive ones.
   * ``ba_stereo`` - the same scene observed by a stereo rig (EdgeStereoSE3ProjectXYZ: u_l v u_r),
     all observations or a fraction of them (a mixed monocular + stereo graph).
+  * ``slam3d_landmarks`` - 3D SLAM with landmarks (VERTEX_SE3:QUAT poses with EDGE_SE3:QUAT odometry, VERTEX_TRACKXYZ
+    points seen through EDGE_SE3_TRACKXYZ / EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY), the shape of
+    g2o_simulator3d's output.
 """
 from __future__ import annotations
 
@@ -32,13 +35,17 @@ SEED = 20261015
 V_SE3_EXPMAP, V_XYZ, V_SE3_QUAT, V_SE2, V_XY = 1, 2, 3, 4, 5
 E_SE3_PROJECT_XYZ, E_SE3_QUAT, E_SE2, E_SE2_XY = 1, 2, 3, 5
 E_STEREO_SE3_PROJECT_XYZ = 6
+# slam3d landmark edges: v0 a V_SE3_QUAT pose, v1 a V_XYZ point
+E_SE3_XYZ, E_SE3_XYZ_DEPTH, E_SE3_XYZ_DISPARITY = 7, 8, 9
 # unary edge types (priors): EdgeSet.v1 is None
 E_SE2_PRIOR, E_SE2_XY_PRIOR, E_XY_PRIOR, E_SE3_PRIOR, E_XYZ_PRIOR = 16, 17, 18, 19, 20
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
-            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3}
+            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
+            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
-           E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3}
+           E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
+           E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3}
 # the vertex type a unary edge type attaches to
 PRIOR_VERTEX = {E_SE2_PRIOR: V_SE2, E_SE2_XY_PRIOR: V_SE2, E_XY_PRIOR: V_XY, E_SE3_PRIOR: V_SE3_QUAT, E_XYZ_PRIOR: V_XYZ}
 
@@ -60,7 +67,7 @@ class EdgeSet:
     meas: np.ndarray    # float64 [n, MEAS_DIM]
     info: np.ndarray    # float64 [n, D, D]
     # float64 [n, 4] (fx fy cx cy) for projection edges, [n, 5] (+ bf) for stereo, [n, 7] (offset x y z qx qy qz qw)
-    # or None (identity) for SE3 priors
+    # or None (identity) for SE3 priors and E_SE3_XYZ, [n, 11] (offset, fx fy cx cy) for E_SE3_XYZ_DEPTH / _DISPARITY
     params: np.ndarray | None = None
 
 
@@ -619,3 +626,98 @@ def twin_of(prob: Problem) -> Problem:
         iv = np.full(len(es.v0), ident[ivt], np.int32)
         edges.append(EdgeSet(bt, iv, es.v0.copy(), es.meas.copy(), es.info.copy(), None))
     return Problem(prob.name + "/twin", verts, edges, prob.pose_dim, prob.landmark_dim)
+
+
+# ---------------------------------------------------------------- slam3d landmark graphs
+def slam3d_landmarks(num_poses: int = 40, num_points: int = 600, kind=E_SE3_XYZ, offset=None, camera=None,
+                     obs_per_point: int = 4, pose_noise=(0.02, 0.01), point_noise: float = 0.05,
+                     meas_noise=(0.02, 1.0, 0.02, 0.002), seed: int = SEED) -> Problem:
+    """3D SLAM with landmarks (the shape of g2o_simulator3d's output): ``num_poses`` VertexSE3 poses on a circle of
+    radius 3 (sensor axis z pointing outwards, the first pose fixed) with E_SE3_QUAT odometry between consecutive ones,
+    and ``num_points`` VertexPointXYZ points (marginalized), each observed from the ``obs_per_point`` poses nearest
+    along the trajectory to the pose it was drawn in front of.  ``kind`` is one of E_SE3_XYZ, E_SE3_XYZ_DEPTH,
+    E_SE3_XYZ_DISPARITY or a sequence of them: one edge set per kind over the same (pose, point) pairs.  ``offset``
+    (x y z qx qy qz qw, None = identity) is the sensor offset on the pose, ``camera`` (fx fy cx cy, default
+    520 510 320 240) the intrinsics of the two camera kinds.  A point is drawn 3 to 6 units in front of its sensor and
+    an observation is kept only where the ground-truth sensor-frame z is >= 1 (the scene is ~10 across).
+    ``pose_noise`` = (translation, quaternion) sigma of the odometry, ``point_noise`` of the initial point estimates,
+    ``meas_noise`` = sigma of (sensor-frame xyz, pixels, depth, inverse depth).  The information is
+    sigma^-1 (I + A)(I + A)^T sigma^-1 with A random per edge: SPD, not diagonal."""
+    kinds = [int(kind)] if np.isscalar(kind) else [int(k) for k in kind]
+    n = num_poses
+    rng = _rng(seed, 40)
+    th = 2 * math.pi * np.arange(n) / n
+    zero, one = np.zeros(n), np.ones(n)
+    Rt = np.stack([np.stack([-np.sin(th), zero, np.cos(th)], 1), np.stack([np.cos(th), zero, np.sin(th)], 1),
+                   np.stack([zero, one, zero], 1)], 1)  # columns: tangent, up, outward radial
+    tt = 3.0 * np.stack([np.cos(th), np.sin(th), 0.1 * np.sin(3 * th)], 1)
+    # odometry prev^-1 * cur with noise, and the chained initial estimate (as sphere())
+    a, b = np.arange(0, n - 1), np.arange(1, n)
+    Rrel = np.transpose(Rt[a], (0, 2, 1)) @ Rt[b]
+    trel = np.einsum("nji,nj->ni", Rt[a], tt[b] - tt[a])
+    st, sq = pose_noise
+    qn = rng.standard_normal((n - 1, 3)) * sq
+    ang = np.linalg.norm(qn, axis=1)
+    dR = _axis_angle(np.where(ang[:, None] > 0, qn, [1.0, 0.0, 0.0]), 2 * ang)
+    Rm = Rrel @ dR
+    tm = trel + rng.standard_normal((n - 1, 3)) * st
+    odo_meas = np.concatenate([tm, rot_to_quat(Rm)], axis=1)
+    Rm = quat_to_rot(odo_meas[:, 3:7])
+    odo_info = np.zeros((6, 6))
+    odo_info[0:3, 0:3] = np.eye(3) / (st * st)
+    odo_info[3:6, 3:6] = np.eye(3) / (sq * sq)
+    Rc, tc = np.empty((n, 3, 3)), np.empty((n, 3))
+    Rc[0], tc[0] = Rt[0], tt[0]
+    for i in range(1, n):
+        Rc[i] = Rc[i - 1] @ Rm[i - 1]
+        tc[i] = Rc[i - 1] @ tm[i - 1] + tc[i - 1]
+    fixed = np.zeros(n, np.int32)
+    fixed[0] = 1
+    poses = VertexSet(V_SE3_QUAT, np.arange(n, dtype=np.int32), _iso_vec(Rc, tc), fixed, np.zeros(n, np.int32))
+    odo = EdgeSet(E_SE3_QUAT, a.astype(np.int32), b.astype(np.int32), odo_meas, np.broadcast_to(odo_info, (n - 1, 6, 6)).copy())
+    # the sensor frames S_i = X_i * P
+    off = np.array([0, 0, 0, 0, 0, 0, 1.0]) if offset is None else np.asarray(offset, np.float64).reshape(7).copy()
+    off[3:7] /= np.linalg.norm(off[3:7])
+    Rp = quat_to_rot(off[None, 3:7])[0]
+    Rs, ts = Rt @ Rp, tt + Rt @ off[0:3]
+    # points: drawn in the sensor frame of an anchor pose, seen from the poses nearest to it along the trajectory
+    m = num_points
+    anchor = rng.integers(0, n, m)
+    local = np.stack([rng.uniform(-1.5, 1.5, m), rng.uniform(-1.5, 1.5, m), rng.uniform(3.0, 6.0, m)], 1)
+    pts = ts[anchor] + np.einsum("nij,nj->ni", Rs[anchor], local)
+    steps = np.array([(k + 1) // 2 * (1 if k % 2 else -1) for k in range(obs_per_point)])  # 0, 1, -1, 2, -2, ...
+    op = ((anchor[:, None] + steps[None, :]) % n).ravel()
+    ol = np.repeat(np.arange(m), obs_per_point)
+    pn = np.einsum("nji,nj->ni", Rs[op], pts[ol] - ts[op])
+    keep = pn[:, 2] >= 1.0
+    op, ol, pn = op[keep], ol[keep], pn[keep]
+    ne = len(op)
+    pid = (n + np.arange(m)).astype(np.int32)
+    points = VertexSet(V_XYZ, pid, pts + rng.standard_normal((m, 3)) * point_noise, np.zeros(m, np.int32),
+                       np.ones(m, np.int32))
+    cam = np.array([520.0, 510.0, 320.0, 240.0]) if camera is None else np.asarray(camera, np.float64).reshape(4)
+    s_xyz, s_px, s_d, s_id = meas_noise
+    edges = [odo]
+    for kd in kinds:
+        r = _rng(seed, 41 + kd)
+        if kd == E_SE3_XYZ:
+            sg = np.full(3, s_xyz)
+            z = pn.copy()
+            params = None if offset is None else np.broadcast_to(off, (ne, 7)).copy()
+        else:
+            u = cam[0] * pn[:, 0] / pn[:, 2] + cam[2]
+            v = cam[1] * pn[:, 1] / pn[:, 2] + cam[3]
+            if kd == E_SE3_XYZ_DEPTH:
+                sg, z = np.array([s_px, s_px, s_d]), np.stack([u, v, pn[:, 2]], 1)
+            elif kd == E_SE3_XYZ_DISPARITY:
+                sg, z = np.array([s_px, s_px, s_id]), np.stack([u, v, 1.0 / pn[:, 2]], 1)
+            else:
+                raise KeyError(kd)
+            params = np.broadcast_to(np.concatenate([off, cam]), (ne, 11)).copy()
+        z = z + r.standard_normal((ne, 3)) * sg
+        A = np.eye(3) + 0.3 * r.standard_normal((ne, 3, 3))
+        info = np.einsum("nij,nkj->nik", A, A) / (sg[:, None] * sg[None, :])
+        info = 0.5 * (info + np.transpose(info, (0, 2, 1)))
+        edges.append(EdgeSet(kd, poses.ids[op].copy(), pid[ol].copy(), z, info, params))
+    name = f"slam3d{n}x{m}k" + "".join(str(k) for k in kinds)
+    return Problem(name, [poses, points], edges, 6, 3)

@@ -48,6 +48,17 @@ extern "C" {
                                       whose only edge type this is takes the fused assembly, as a monocular one does;
                                       with other types beside it (monocular edges, say) the generic one. Not carried by
                                       .g2o files: see g2ohip_load_g2o / g2ohip_save_g2o */
+/* slam3d landmark edges: v0 the pose (G2OHIP_V_SE3_QUAT), v1 the point (G2OHIP_V_XYZ), g2o's vertex order for these
+ * edges (the opposite of the BA types); info 3x3. The sensor offset is ParameterSE3Offset::offset() as x y z qx qy qz qw;
+ * the camera types take ParameterCamera: that offset, then fx fy cx cy. One record per edge; edges whose records are
+ * all equal share a single one on the device. They are assembled on the generic slot path (BlockSolver_6_3 with the
+ * points marginalized); lm_pcg6_3_eigen refuses them. */
+#define G2OHIP_E_SE3_XYZ 7           /* EdgeSE3PointXYZ (EDGE_SE3_TRACKXYZ), edge_se3_pointxyz.cpp:100-135: meas x y z in
+                                        the sensor frame; params offset (n*7), or NULL: every offset the identity */
+#define G2OHIP_E_SE3_XYZ_DEPTH 8     /* EdgeSE3PointXYZDepth (EDGE_PROJECT_DEPTH), edge_se3_pointxyz_depth.cpp:91-138:
+                                        meas u v depth; params offset + fx fy cx cy (n*11), NULL is G2OHIP_ERR_ARG */
+#define G2OHIP_E_SE3_XYZ_DISPARITY 9 /* EdgeSE3PointXYZDisparity (EDGE_PROJECT_DISPARITY): meas u v 1/depth; params as
+                                        G2OHIP_E_SE3_XYZ_DEPTH */
 /* An edge type the device does not know (any BaseBinaryEdge<D, E, Vi, Vj> between registered vertices of
  * dimension 2, 3 or 6): the host's own linearizeOplus (the type's analytic one, or BaseBinaryEdge's numeric
  * central differences, base_binary_edge.hpp:198-266) supplies the error and both Jacobians, see
@@ -130,7 +141,8 @@ int g2ohip_add_vertices(g2ohip_graph* g, int type, int n, const int* ids, const 
 int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int* v1, const double* meas,
                      const double* info /* n * D*D row-major */, const double* params /* n*4, stereo n*5, or NULL */);
 /* params: the intrinsics of the projection types (G2OHIP_ERR_ARG when one of them gets NULL), the offsets of
- * G2OHIP_E_SE3_PRIOR (n*7, or NULL: identity), NULL for the others. v1: NULL for the unary types (and only for them). */
+ * G2OHIP_E_SE3_PRIOR and G2OHIP_E_SE3_XYZ (n*7, or NULL: identity), offset + intrinsics of G2OHIP_E_SE3_XYZ_DEPTH /
+ * _DISPARITY (n*11, NULL is G2OHIP_ERR_ARG), NULL for the others. v1: NULL for the unary types (and only for them). */
 /* .g2o files do not carry G2OHIP_E_STEREO_SE3_PROJECT_XYZ: the reference's reader and writer for its tag
  * (EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP, types_six_dof_expmap.cpp:469-493) move four measurement values through a
  * 3-vector and no intrinsics. The loader skips the tag like any unknown one; g2ohip_save_g2o on a graph that holds
@@ -142,11 +154,20 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * prior on a vertex of the wrong type or a short line fails the load (g2ohip_last_error says which). flags = 0 is
  * g2ohip_load_g2o, which skips these tags like any unknown one. */
 #define G2OHIP_LOAD_UNARY 1u
+/* G2OHIP_LOAD_SLAM3D (may be combined with G2OHIP_LOAD_UNARY): VERTEX_TRACKXYZ id x y z loads as G2OHIP_V_XYZ
+ * (marginalized according to marginalize_xyz); PARAMS_SE3OFFSET and PARAMS_CAMERACALIB (id, x y z qx qy qz qw, fx fy cx
+ * cy; parameter_camera.cpp:62-85) are read; EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH and EDGE_PROJECT_DISPARITY (v0 v1
+ * paramId m0 m1 m2, then the six upper-triangle information values) load as G2OHIP_E_SE3_XYZ, _DEPTH and _DISPARITY. A
+ * parameter id that no line defines, or one of the wrong kind, fails the load with the id in g2ohip_last_error. */
+#define G2OHIP_LOAD_SLAM3D 2u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
  * line per distinct offset ahead of the vertices; host-J unary edges are left out with a warning, as binary host-J
- * ones are. */
+ * ones are. The slam3d landmark edges are written as EDGE_SE3_TRACKXYZ / EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY
+ * (edge_se3_pointxyz.cpp:88-96 and its siblings), their parameters as PARAMS_SE3OFFSET / PARAMS_CAMERACALIB lines, one
+ * per distinct record, in one id space with the prior offsets; a G2OHIP_V_XYZ vertex one of these edges touches is
+ * written as VERTEX_TRACKXYZ. */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
