@@ -49,6 +49,10 @@ E_STEREO_SE3_PROJECT_XYZ = 6
 E_SE3_XYZ, E_SE3_XYZ_DEPTH, E_SE3_XYZ_DISPARITY = 7, 8, 9
 
 
+# EdgeSE3Expmap (G2OHIP_E_SE3_EXPMAP): v0 = Ti, v1 = Tj, both V_SE3_EXPMAP; meas the SE3Quat C (tx ty tz qx qy qz qw)
+E_SE3_EXPMAP = 10
+
+
 # edge types the device does not know: host-supplied error + Jacobians (include/g2o_hip.h G2OHIP_E_HOSTJ)
 def E_HOSTJ(D: int) -> int:
     return 32 + D
@@ -56,6 +60,11 @@ def E_HOSTJ(D: int) -> int:
 
 # unary edge types (BaseUnaryEdge; include/g2o_hip.h G2OHIP_E_*_PRIOR): EdgeSet.v1 is None
 E_SE2_PRIOR, E_SE2_XY_PRIOR, E_XY_PRIOR, E_SE3_PRIOR, E_XYZ_PRIOR = 16, 17, 18, 19, 20
+
+
+# pose-only projections on a V_SE3_EXPMAP camera (G2OHIP_E_*_ONLYPOSE), unary: meas u v / u_l v u_r; params
+# Xw.x Xw.y Xw.z fx fy cx cy (stereo + bf)
+E_SE3_PROJECT_XYZ_ONLYPOSE, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE = 21, 22
 
 
 # any other BaseUnaryEdge: host-supplied error + Jacobian, payload [e | Ji] per edge (G2OHIP_E_HOSTJ_UNARY)
@@ -66,6 +75,7 @@ def E_HOSTJ_UNARY(D: int) -> int:
 # g2ohip_load_g2o_ex flags
 LOAD_UNARY = 1
 LOAD_SLAM3D = 2
+LOAD_EXPMAP = 4
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -391,12 +401,13 @@ class SparseOptimizer:
         est = np.ascontiguousarray(est, np.float64)
         _check(lib().g2ohip_set_estimates(self.h, vtype, _p(est)), "set_estimates")
 
-    def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False):
+    def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False,
+             expmap: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
         EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
         (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
-        PARAMS_CAMERACALIB); both are skipped otherwise."""
-        flags = (LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0)
+        PARAMS_CAMERACALIB), expmap=True EDGE_SE3:EXPMAP; all are skipped otherwise."""
+        flags = (LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0)
         _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:

@@ -102,7 +102,7 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
   return guarded([&] { return g->e->load(path, marginalize_xyz); });
 }
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
-  if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D))) return G2OHIP_ERR_ARG;
+  if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
@@ -115,6 +115,15 @@ int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
             "for the tag drop the intrinsics and misread the measurement)";
     return G2OHIP_ERR_UNSUPPORTED;
   }
+  // the pose-only projections likewise: their tags carry neither the point Xw nor the intrinsics
+  // (types_six_dof_expmap.cpp:543-567, 610-634)
+  for (int type : {G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE, G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE})
+    if (const auto* es = g->e->hg.set_of(type); es && !es->ev0.empty()) {
+      g_err = "g2ohip_save_g2o: the graph holds " + std::to_string(es->ev0.size()) + " pose-only projection edges (type " +
+              std::to_string(type) + "), which the .g2o format cannot carry (the reference's reader and writer for the "
+              "tag leave out the point Xw and the intrinsics)";
+      return G2OHIP_ERR_UNSUPPORTED;
+    }
   return guarded([&] { return g->e->save(path); });
 }
 int g2ohip_num_vertices(g2ohip_graph* g) { return g ? (int)g->e->hg.verts.size() : G2OHIP_ERR_ARG; }

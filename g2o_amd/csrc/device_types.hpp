@@ -6,6 +6,8 @@
 //   EdgeSE2            types/slam2d/edge_se2.h:46-52, edge_se2.cpp:77-103
 //   EdgeSE2PointXY     types/slam2d/edge_se2_pointxy.h:41-75, edge_se2_pointxy.cpp:63-87
 //   EdgeSE3PointXYZ, ...Depth, ...Disparity  types/slam3d/edge_se3_pointxyz.cpp:100-135 and its two siblings
+//   EdgeSE3Expmap      types/sba/types_six_dof_expmap.h:117-124, .cpp:278-293, slam3d/se3quat.h:99-130, 173-210, 259-268
+//   EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose  types_six_dof_expmap.h:242-246, 303-307, .cpp:569-665
 //   unary priors       types/slam2d/edge_se2_prior.h:39-77, edge_se2_xyprior.h:39-71, edge_xy_prior.h,
 //                      types/slam3d/edge_se3_prior.cpp:89-102 (isometry3d_gradients.h:265-325), edge_xyz_prior.cpp:63-70
 //   oplus             types_six_dof_expmap.h:97-100 (SE3Quat::exp * T, se3quat.h:217-257),
@@ -957,6 +959,204 @@ struct FamilyHostJUnary {
     for (int i = 0; i < D; ++i) err[i] = p[i];
 #pragma unroll
     for (int i = 0; i < D * DA; ++i) A[i] = p[D + i];
+  }
+};
+
+// ================================================================ the other edges on VertexSE3Expmap
+// (types/sba/types_six_dof_expmap.*): EdgeSE3Expmap between two cameras, and the two pose-only projections.
+
+// ---- SE3Quat as (q = x y z w, t) ----
+// SE3Quat::inverse (se3quat.h:118-123): r' = conj(r), t' = r' * (-t); no normalisation
+DI void se3q_inv(const double* q, const double* t, double* qo, double* to) {
+  qo[0] = -q[0]; qo[1] = -q[1]; qo[2] = -q[2]; qo[3] = q[3];
+  const double nt[3] = {t[0] * -1., t[1] * -1., t[2] * -1.};
+  qrot(qo, nt, to);
+}
+// SE3Quat::operator* (se3quat.h:99-105): t = ta + ra * tb, r = ra * rb, then normalizeRotation (w >= 0, unit norm)
+DI void se3q_mul(const double* qa, const double* ta, const double* qb, const double* tb, double* qo, double* to) {
+  double rt[3];
+  qrot(qa, tb, rt);
+  to[0] = ta[0] + rt[0]; to[1] = ta[1] + rt[1]; to[2] = ta[2] + rt[2];
+  qmul(qa, qb, qo);
+  qnormalize_pos(qo);
+}
+// SE3Quat::log (se3quat.h:173-210): out = (omega, upsilon). Both branches: d > 0.99999 takes omega = deltaR / 2 and
+// the series V^-1, otherwise acos and tan.
+DI void se3q_log(const double* q, const double* t, double* out) {
+  double R[9];
+  quat_to_R(q[0], q[1], q[2], q[3], R);
+  const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
+  const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+  double w[3], c;  // V^-1 = I - 0.5 Omega + c Omega^2
+  if (d > 0.99999) {
+    w[0] = 0.5 * dR[0]; w[1] = 0.5 * dR[1]; w[2] = 0.5 * dR[2];
+    c = 1. / 12.;
+  } else {
+    const double theta = acos(d);
+    const double s = theta / (2 * sqrt(1 - d * d));
+    w[0] = s * dR[0]; w[1] = s * dR[1]; w[2] = s * dR[2];
+    c = (1 - theta / (2 * tan(theta / 2))) / (theta * theta);
+  }
+  const double Om[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  double Om2[9];
+  mat3mul(Om, Om, Om2);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s += (((r == k) ? 1.0 : 0.0) - 0.5 * Om[r * 3 + k] + c * Om2[r * 3 + k]) * t[k];
+    out[r] = w[r];
+    out[3 + r] = s;
+  }
+}
+// SE3Quat::adj (se3quat.h:259-268) times sgn, row-major 6 x 6: [[R, 0], [skew(t) R, R]]
+DI void se3q_adj(const double* q, const double* t, double sgn, double* J) {
+  double R[9];
+  quat_to_R(q[0], q[1], q[2], q[3], R);
+  const double S[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
+  double SR[9];
+  mat3mul(S, R, SR);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      J[r * 6 + c] = sgn * R[r * 3 + c];
+      J[r * 6 + 3 + c] = 0;
+      J[(3 + r) * 6 + c] = sgn * SR[r * 3 + c];
+      J[(3 + r) * 6 + 3 + c] = sgn * R[r * 3 + c];
+    }
+}
+
+// ---- EdgeSE3Expmap (types_six_dof_expmap.h:117-124, .cpp:278-293): v0 = Ti, v1 = Tj, both SE3Quat cameras [8];
+// meas payload = the measurement C as stored [8] (tx ty tz qx qy qz qw pad), info packed upper 21.
+// error = log(Tj^-1 * C * Ti) in (omega, upsilon) order; Ji = adj(Tj^-1 * C), Jj = -adj(Ti^-1 * C^-1): the reference's
+// Jacobians, exact at zero error only. The error is finished before the Jacobians start, so that the temporaries of
+// the log and of the two adjoints are not live together. ----
+struct FamilyExpmap {
+  static constexpr int D = 6, DA = 6, DB = 6, MEAS = 8, INFO = 21;
+  DI static void load(const double* p, double* q, double* t) {
+    t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
+    q[0] = p[3]; q[1] = p[4]; q[2] = p[5]; q[3] = p[6];
+  }
+  // A = Tj^-1 * C
+  DI static void invTj_C(const EdgeData& d, int e, double* qa, double* ta) {
+    double qj[4], tj[3], qc[4], tc[3], qi[4], ti[3];
+    load(d.s1 + (size_t)d.v1[e] * 8, qj, tj);
+    load(d.meas + (size_t)e * 8, qc, tc);
+    se3q_inv(qj, tj, qi, ti);
+    se3q_mul(qi, ti, qc, tc, qa, ta);
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double qa[4], ta[3], qi[4], ti[3], qe[4], te[3];
+    invTj_C(d, e, qa, ta);
+    load(d.s0 + (size_t)d.v0[e] * 8, qi, ti);
+    se3q_mul(qa, ta, qi, ti, qe, te);
+    se3q_log(qe, te, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    error(d, e, err);
+    {
+      double qa[4], ta[3];
+      invTj_C(d, e, qa, ta);
+      se3q_adj(qa, ta, 1.0, Ji);
+    }
+    {
+      double qi[4], ti[3], qc[4], tc[3], qx[4], tx[3], qy[4], ty[3], qb[4], tb[3];
+      load(d.s0 + (size_t)d.v0[e] * 8, qi, ti);
+      load(d.meas + (size_t)e * 8, qc, tc);
+      se3q_inv(qi, ti, qx, tx);
+      se3q_inv(qc, tc, qy, ty);
+      se3q_mul(qx, tx, qy, ty, qb, tb);
+      se3q_adj(qb, tb, -1.0, Jj);
+    }
+  }
+};
+
+// ---- EdgeSE3ProjectXYZOnlyPose (types_six_dof_expmap.h:242-246, .cpp:569-599), unary: v0 = camera SE3Quat [8];
+// meas payload u v | Xw (5), info packed 3, params fx fy cx cy (one shared record when EdgeData::ue bit 1 is set).
+// error = obs - cam_project(T.map(Xw)); the Jacobian in the reference's invz / invz_2 products ----
+struct FamilyPoseOnly {
+  static constexpr int D = 2, DA = 6, MEAS = 5, INFO = 3, PAR = 4;
+  DI static void to_camera(const EdgeData& d, int e, const double* m, double* pc) {
+    const double* c = d.s0 + (size_t)d.v0[e] * 8;
+    const double q[4] = {c[3], c[4], c[5], c[6]};
+    const double pv[3] = {m[0], m[1], m[2]};
+    qrot(q, pv, pc);
+    pc[0] += c[0]; pc[1] += c[1]; pc[2] += c[2];
+  }
+  // rows 0-1 of the pose Jacobian (shared with the stereo type, .cpp:645-657)
+  DI static void jac_uv(const double* K, const double* pc, double invz, double invz_2, double* A) {
+    const double fx = K[0], fy = K[1], x = pc[0], y = pc[1];
+    A[0] = x * y * invz_2 * fx;
+    A[1] = -(1 + (x * x * invz_2)) * fx;
+    A[2] = y * invz * fx;
+    A[3] = -invz * fx;
+    A[4] = 0;
+    A[5] = x * invz_2 * fx;
+    A[6] = (1 + y * y * invz_2) * fy;
+    A[7] = -x * y * invz_2 * fy;
+    A[8] = -x * invz * fy;
+    A[9] = 0;
+    A[10] = -invz * fy;
+    A[11] = y * invz_2 * fy;
+  }
+  DI static void residual(const double* K, const double* pc, const double* m, double* err) {
+    err[0] = m[0] - (pc[0] / pc[2] * K[0] + K[2]);
+    err[1] = m[1] - (pc[1] / pc[2] * K[1] + K[3]);
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* m = d.meas + (size_t)e * MEAS;
+    double pc[3];
+    to_camera(d, e, m + 2, pc);
+    residual(param_rec(d, e, PAR), pc, m, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
+    const double* m = d.meas + (size_t)e * MEAS;
+    const double* K = param_rec(d, e, PAR);
+    double pc[3];
+    to_camera(d, e, m + 2, pc);
+    residual(K, pc, m, err);
+    const double invz = 1.0 / pc[2], invz_2 = invz * invz;
+    jac_uv(K, pc, invz, invz_2, A);
+  }
+};
+
+// ---- EdgeStereoSE3ProjectXYZOnlyPose (types_six_dof_expmap.h:303-307, .cpp:601-608, 636-665), unary: meas payload
+// u_l v u_r | Xw (6), info packed 6, params fx fy cx cy bf. cam_project holds 1/z in a float (`const float invz`), so
+// all three error components see it rounded; bf stays a double here. The Jacobian uses the double 1/z. ----
+struct FamilyStereoPoseOnly {
+  static constexpr int D = 3, DA = 6, MEAS = 6, INFO = 6, PAR = 5;
+  // No contraction: the projection rounds as the reference's does, operation by operation (as FamilyStereo::residual)
+  DI static void residual(const double* K, const double* pc, const double* m, double* err) {
+#pragma clang fp contract(off)
+    const double invz = (double)(float)(1.0 / pc[2]);
+    const double u = pc[0] * invz * K[0] + K[2];
+    const double v = pc[1] * invz * K[1] + K[3];
+    const double ur = u - K[4] * invz;
+    err[0] = m[0] - u;
+    err[1] = m[1] - v;
+    err[2] = m[2] - ur;
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* m = d.meas + (size_t)e * MEAS;
+    double pc[3];
+    FamilyPoseOnly::to_camera(d, e, m + 3, pc);
+    residual(param_rec(d, e, PAR), pc, m, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
+    const double* m = d.meas + (size_t)e * MEAS;
+    const double* K = param_rec(d, e, PAR);
+    double pc[3];
+    FamilyPoseOnly::to_camera(d, e, m + 3, pc);
+    residual(K, pc, m, err);
+    const double invz = 1.0 / pc[2], invz_2 = invz * invz, bf = K[4];
+    FamilyPoseOnly::jac_uv(K, pc, invz, invz_2, A);
+    A[12] = A[0] - bf * pc[1] * invz_2;
+    A[13] = A[1] + bf * pc[0] * invz_2;
+    A[14] = A[2];
+    A[15] = A[3];
+    A[16] = 0;
+    A[17] = A[5] - bf * invz_2;
   }
 };
 

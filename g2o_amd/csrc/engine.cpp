@@ -51,30 +51,36 @@ static bool is_hostj_unary(int e) { return e > G2OHIP_E_HOSTJ_UNARY(0) && e <= G
 static bool is_hostj(int e) { return is_hostj_binary(e) || is_hostj_unary(e); }
 // the slam3d landmark edges: EdgeSE3PointXYZ, ...Depth, ...Disparity
 static bool is_slam3d_type(int e) { return e >= G2OHIP_E_SE3_XYZ && e <= G2OHIP_E_SE3_XYZ_DISPARITY; }
-// BaseUnaryEdge types: the five priors and the unary host-J escape
-static bool is_unary_type(int e) { return (e >= G2OHIP_E_SE2_PRIOR && e <= G2OHIP_E_XYZ_PRIOR) || is_hostj_unary(e); }
+// BaseUnaryEdge types: the five priors, the two pose-only projections (EdgeSE3ProjectXYZOnlyPose and its stereo
+// sibling, on a VertexSE3Expmap) and the unary host-J escape
+static bool is_unary_type(int e) {
+  return (e >= G2OHIP_E_SE2_PRIOR && e <= G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE) || is_hostj_unary(e);
+}
 int edge_dim(int e) {
   if (is_hostj_binary(e)) return e - G2OHIP_E_HOSTJ(0);
   if (is_hostj_unary(e)) return e - G2OHIP_E_HOSTJ_UNARY(0);
   switch (e) {
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: case G2OHIP_E_SE2_PRIOR: case G2OHIP_E_XYZ_PRIOR: return 3;
     case G2OHIP_E_SE3_XYZ: case G2OHIP_E_SE3_XYZ_DEPTH: case G2OHIP_E_SE3_XYZ_DISPARITY: return 3;
-    case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: return 2;
-    case G2OHIP_E_SE3_PRIOR: return 6;
+    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: return 3;
+    case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: return 2;
+    case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: return 6;
   }
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 6 : (e == G2OHIP_E_SE2 ? 3 : -1));
 }
 int edge_meas_dim(int e) {
   if (is_hostj(e)) return 0;
-  if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR) return 2;
-  if (e == G2OHIP_E_SE3_PRIOR) return 7;
+  if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR || e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 2;
+  if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_EXPMAP) return 7;
   if (is_slam3d_type(e)) return 3;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
 }
 // doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
 // sensor offset x y z qx qy qz qw (optional: NULL = identity), as EdgeSE3PointXYZ's; the slam3d camera types' offset
-// followed by fx fy cx cy
+// followed by fx fy cx cy; the pose-only projections' Xw fx fy cx cy (stereo + bf)
 int edge_param_dim(int e) {
+  if (e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 7;
+  if (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE) return 8;
   if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_XYZ) return 7;
   if (e == G2OHIP_E_SE3_XYZ_DEPTH || e == G2OHIP_E_SE3_XYZ_DISPARITY) return 11;
   return e == G2OHIP_E_SE3_PROJECT_XYZ ? 4 : (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ ? 5 : 0);
@@ -1307,7 +1313,8 @@ struct Cursor {
 };
 // unary: the unary edge tags and PARAMS_SE3OFFSET are parsed (G2OHIP_LOAD_UNARY), else skipped as unknown tags;
 // slam3d: VERTEX_TRACKXYZ, PARAMS_SE3OFFSET, PARAMS_CAMERACALIB and the three landmark edge tags (G2OHIP_LOAD_SLAM3D)
-void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, ParsedChunk& out) {
+// expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP)
+void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1364,6 +1371,15 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, ParsedCh
       for (int r = 0; r < D; ++r)
         for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
       out.edges.push_back(ed);
+    } else if (expmap && tag == "EDGE_SE3:EXPMAP") {  // types_six_dof_expmap.cpp:114-129: the seven values are
+                                                      // cam2world, the measurement their inverse; information as is
+      ParsedEdge ed{G2OHIP_E_SE3_EXPMAP, c.i(), c.i(), {}, {}, {}};
+      double w[7];
+      for (double& x : w) x = c.d();
+      se3quat_inverse(w, ed.m);
+      for (int r = 0; r < 6; ++r)
+        for (int q = r; q < 6; ++q) ed.info[r * 6 + q] = ed.info[q * 6 + r] = c.d();
+      out.edges.push_back(ed);
     } else if ((unary || slam3d) && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
       ParsedParam pp{c.i(), {}};
       for (int k = 0; k < 7; ++k) pp.v[k] = c.d();
@@ -1411,7 +1427,8 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, ParsedCh
 }  // namespace
 
 int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
-  const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0;
+  const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0,
+             expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1439,7 +1456,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
-      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, chunks[t]); });
+      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1512,6 +1529,14 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
           std::memcpy(ed.p, po->second->v, sizeof(double) * 7);
         }
       }
+      if (ed.type == G2OHIP_E_SE3_EXPMAP)  // both endpoints are VERTEX_SE3:EXPMAP cameras
+        for (int id : {ed.a, ed.b}) {
+          auto it = hg.idmap.find(id);
+          if (it == hg.idmap.end() || hg.verts[it->second].type != G2OHIP_V_SE3_EXPMAP)
+            throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: EDGE_SE3:EXPMAP " + std::to_string(ed.a) + " -> " +
+                                                  std::to_string(ed.b) + ": vertex " + std::to_string(id) +
+                                                  " is missing or no VERTEX_SE3:EXPMAP");
+        }
       if (is_slam3d_type(ed.type)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
         const bool cam = ed.type != G2OHIP_E_SE3_XYZ;
         auto po = offsets.find(ed.pid);
@@ -1671,6 +1696,12 @@ int Engine::save(const char* path) {
           L.i(a); L.i(b); L.i(pids[si][k]);
           for (int q = 0; q < 3; ++q) L.d(m[q]);
           for (int r = 0; r < 3; ++r) for (int q = r; q < 3; ++q) L.d(I[r * 3 + q]);
+        } else if (es.type == G2OHIP_E_SE3_EXPMAP) {  // types_six_dof_expmap.cpp:131-140: the inverse measurement
+          double w[7];
+          se3quat_inverse(m, w);
+          L.tag("EDGE_SE3:EXPMAP"); L.i(a); L.i(b);
+          for (int q = 0; q < 7; ++q) L.d(w[q]);
+          for (int r = 0; r < 6; ++r) for (int q = r; q < 6; ++q) L.d(I[r * 6 + q]);
         } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
           L.tag("EDGE_SE2_XY"); L.i(a); L.i(b);
           L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
@@ -1837,12 +1868,15 @@ static int family_of(int etype, int& vtA, int& vtB) {
     case G2OHIP_E_SE3_XYZ: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ;
     case G2OHIP_E_SE3_XYZ_DEPTH: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DEPTH;
     case G2OHIP_E_SE3_XYZ_DISPARITY: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DISPARITY;
+    case G2OHIP_E_SE3_EXPMAP: vtA = vtB = G2OHIP_V_SE3_EXPMAP; return FAM_EXPMAP;
     // unary types: vtB = 0 (no second vertex)
     case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
     case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
     case G2OHIP_E_XY_PRIOR: vtA = G2OHIP_V_XY; vtB = 0; return FAM_U_XY;
     case G2OHIP_E_SE3_PRIOR: vtA = G2OHIP_V_SE3_QUAT; vtB = 0; return FAM_U_SE3;
     case G2OHIP_E_XYZ_PRIOR: vtA = G2OHIP_V_XYZ; vtB = 0; return FAM_U_XYZ;
+    case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: vtA = G2OHIP_V_SE3_EXPMAP; vtB = 0; return FAM_U_POSE_ONLY;
+    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: vtA = G2OHIP_V_SE3_EXPMAP; vtB = 0; return FAM_U_STEREO_POSE_ONLY;
   }
   vtA = vtB = 0;
   return is_hostj_binary(etype) ? FAM_HOSTJ : (is_hostj_unary(etype) ? FAM_U_HOSTJ : FAM_NONE);
@@ -2097,11 +2131,17 @@ void Engine::setup_edges_device() {
       case FAM_U_SE2XY: case FAM_U_XY: mmeas = 2; break;
       case FAM_U_SE3: mmeas = 24; break;
       case FAM_SE3_XYZ: case FAM_SE3_XYZ_DEPTH: case FAM_SE3_XYZ_DISPARITY: mmeas = 3; break;
+      case FAM_EXPMAP: mmeas = 8; break;              // the measurement as an SE3Quat, padded to a 64-byte record
+      case FAM_U_POSE_ONLY: mmeas = 5; break;         // u v | Xw
+      case FAM_U_STEREO_POSE_ONLY: mmeas = 6; break;  // u_l v u_r | Xw
     }
     // device parameter record: the BA intrinsics as given; slam3d: the inverse offset as an isometry (12), the camera
-    // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp)
+    // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
+    // point Xw ahead of them in the caller's record goes into the measurement payload)
     const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type)
-                     : g.family == FAM_SE3_XYZ ? 12 : (is_slam3d_family(g.family) ? 16 : 0);
+                     : g.family == FAM_SE3_XYZ ? 12
+                     : is_slam3d_family(g.family) ? 16
+                     : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3 : 0;
     std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
         params(mpar ? (size_t)gne * mpar : 1);
     for (int k = 0; k < gne; ++k) {
@@ -2144,6 +2184,20 @@ void Engine::setup_edges_device() {
         mo[2] = th;
       } else if (g.family == FAM_SE2XY) {
         mo[0] = m[0]; mo[1] = m[1];
+      } else if (g.family == FAM_EXPMAP) {  // SE3Quat(Vector7), se3quat.h:81-88: normalizeRotation (w >= 0, unit)
+        double q[4] = {m[3], m[4], m[5], m[6]};
+        const double sn = q[3] < 0 ? -1.0 : 1.0;
+        for (double& x : q) x *= sn;
+        const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        for (int j = 0; j < 3; ++j) mo[j] = m[j];
+        for (int j = 0; j < 4; ++j) mo[3 + j] = q[j] / n;
+        mo[7] = 0;
+      } else if (is_pose_only_family(g.family)) {  // caller's record Xw fx fy cx cy (bf) -> payload obs | Xw, intrinsics
+        const int np = edge_param_dim(es.type);
+        const double* p = es.params.data() + (size_t)e * np;
+        for (int j = 0; j < nm; ++j) mo[j] = m[j];
+        for (int j = 0; j < 3; ++j) mo[nm + j] = p[j];
+        for (int j = 3; j < np; ++j) params[(size_t)k * mpar + j - 3] = p[j];
       } else if (is_slam3d_family(g.family)) {  // the offset (x y z qx qy qz qw) -> its inverse [Rp^T | -Rp^T tp]
         for (int j = 0; j < 3; ++j) mo[j] = m[j];
         const int np = edge_param_dim(es.type);
@@ -2164,7 +2218,8 @@ void Engine::setup_edges_device() {
        // record instead of 24 + 32 bytes per edge (G2OHIP_UNIFORM_RECORDS=0 keeps per-edge records, A/B)
       const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
       g.ue = 0;
-      if ((is_ba_family(g.family) || is_slam3d_family(g.family)) && gne > 1 && !(ev && atoi(ev) == 0)) {
+      if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family)) && gne > 1 &&
+          !(ev && atoi(ev) == 0)) {
         auto uniform = [&](const std::vector<double>& v, int st) {
           for (int k = 1; k < gne; ++k)
             if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
@@ -2532,6 +2587,12 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
         throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                           "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the slam3d "
                           "landmark edges (edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
+  if (use_cgls())
+    for (const HEdgeSet& es : hg.esets)
+      if (es.type == G2OHIP_E_SE3_EXPMAP && !es.ev0.empty())
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take EdgeSE3Expmap "
+                          "(edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
   if (use_cgls() && has_unary_)
     throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                       "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take unary edges: the "
@@ -4249,7 +4310,11 @@ double Engine::kernel_bytes(const std::string& name) const {
     double by = 0;
     for (const EGroup& g : groups)
       if (is_unary_family(g.family)) {
-        const int mm = g.family == FAM_U_SE3 ? 24 : (g.family == FAM_U_HOSTJ ? g.payload_stride() : hg.esets[g.set].nm);
+        // (the pose-only projections: the point Xw behind the observation; their intrinsics are one shared record
+        // in the usual graph and not counted)
+        const int mm = g.family == FAM_U_SE3 ? 24
+                       : g.family == FAM_U_HOSTJ ? g.payload_stride()
+                       : hg.esets[g.set].nm + (is_pose_only_family(g.family) ? 3 : 0);
         by += g.ne * (8.0 + (mm + g.D * (g.D + 1) / 2 + vertex_state_stride(g.vtA) + g.DA * (g.DA + 1) / 2 + g.DA) * 8.0);
       }
     return by;

@@ -1601,6 +1601,8 @@ static void unary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_U_XY: fn(FamilyUnaryXY{}); break;
     case FAM_U_SE3: fn(FamilyUnarySE3{}); break;
     case FAM_U_XYZ: fn(FamilyUnaryXYZ{}); break;
+    case FAM_U_POSE_ONLY: fn(FamilyPoseOnly{}); break;
+    case FAM_U_STEREO_POSE_ONLY: fn(FamilyStereoPoseOnly{}); break;
     case FAM_U_HOSTJ:
       switch (a.D) {
         case 1: hju_a<1>(a.DA, fn); break;
@@ -1634,6 +1636,7 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_SE3_XYZ: fn(FamilySE3XYZ{}); break;
     case FAM_SE3_XYZ_DEPTH: fn(FamilySE3XYZDepth{}); break;
     case FAM_SE3_XYZ_DISPARITY: fn(FamilySE3XYZDisparity{}); break;
+    case FAM_EXPMAP: fn(FamilyExpmap{}); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;

@@ -17,6 +17,10 @@ Recipes:
     each point observed by exactly k cameras of a window of W consecutive ones.
   * ``ba_stereo`` - the same scene observed by a stereo rig (EdgeStereoSE3ProjectXYZ: u_l v u_r),
     all observations or a fraction of them (a mixed monocular + stereo graph).
+  * ``expmap_pose_graph`` - a pose graph on the BA camera parameterisation (VERTEX_SE3:EXPMAP cameras joined by
+    EDGE_SE3:EXPMAP odometry and loop closures).
+  * ``pose_only`` / ``with_pose_only`` - pose optimisation: cameras observing points held in the edges
+    (EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose), alone or beside a BA problem's edges.
   * ``slam3d_landmarks`` - 3D SLAM with landmarks (VERTEX_SE3:QUAT poses with EDGE_SE3:QUAT odometry, VERTEX_TRACKXYZ
     points seen through EDGE_SE3_TRACKXYZ / EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY), the shape of
     g2o_simulator3d's output.
@@ -39,15 +43,25 @@ E_STEREO_SE3_PROJECT_XYZ = 6
 E_SE3_XYZ, E_SE3_XYZ_DEPTH, E_SE3_XYZ_DISPARITY = 7, 8, 9
 # unary edge types (priors): EdgeSet.v1 is None
 E_SE2_PRIOR, E_SE2_XY_PRIOR, E_XY_PRIOR, E_SE3_PRIOR, E_XYZ_PRIOR = 16, 17, 18, 19, 20
+# EdgeSE3Expmap between two V_SE3_EXPMAP cameras; the pose-only projections (unary, on a V_SE3_EXPMAP camera; params
+# Xw fx fy cx cy, stereo + bf)
+E_SE3_EXPMAP = 10
+E_SE3_PROJECT_XYZ_ONLYPOSE, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE = 21, 22
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
-            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3}
+            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
+            E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
-           E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3}
+           E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
+           E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3}
 # the vertex type a unary edge type attaches to
 PRIOR_VERTEX = {E_SE2_PRIOR: V_SE2, E_SE2_XY_PRIOR: V_SE2, E_XY_PRIOR: V_XY, E_SE3_PRIOR: V_SE3_QUAT, E_XYZ_PRIOR: V_XYZ}
+# the same for the pose-only projections, and the binary projection each of them is the pose-only form of
+POSE_ONLY_VERTEX = {E_SE3_PROJECT_XYZ_ONLYPOSE: V_SE3_EXPMAP, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: V_SE3_EXPMAP}
+POSE_ONLY_BINARY = {E_SE3_PROJECT_XYZ_ONLYPOSE: E_SE3_PROJECT_XYZ,
+                    E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: E_STEREO_SE3_PROJECT_XYZ}
 
 
 @dataclasses.dataclass
@@ -67,7 +81,8 @@ class EdgeSet:
     meas: np.ndarray    # float64 [n, MEAS_DIM]
     info: np.ndarray    # float64 [n, D, D]
     # float64 [n, 4] (fx fy cx cy) for projection edges, [n, 5] (+ bf) for stereo, [n, 7] (offset x y z qx qy qz qw)
-    # or None (identity) for SE3 priors and E_SE3_XYZ, [n, 11] (offset, fx fy cx cy) for E_SE3_XYZ_DEPTH / _DISPARITY
+    # or None (identity) for SE3 priors and E_SE3_XYZ, [n, 11] (offset, fx fy cx cy) for E_SE3_XYZ_DEPTH / _DISPARITY,
+    # [n, 7] (Xw fx fy cx cy) / [n, 8] (+ bf) for the pose-only projections
     params: np.ndarray | None = None
 
 
@@ -721,3 +736,162 @@ def slam3d_landmarks(num_poses: int = 40, num_points: int = 600, kind=E_SE3_XYZ,
         edges.append(EdgeSet(kd, poses.ids[op].copy(), pid[ol].copy(), z, info, params))
     name = f"slam3d{n}x{m}k" + "".join(str(k) for k in kinds)
     return Problem(name, [poses, points], edges, 6, 3)
+
+
+# ---------------------------------------------------------------- EdgeSE3Expmap pose graphs
+def _se3_exp(u):
+    """SE3Quat::exp of [n, 6] (omega, upsilon) -> (R [n, 3, 3], t [n, 3])."""
+    u = np.asarray(u, np.float64).reshape(-1, 6)
+    om, ups = u[:, :3], u[:, 3:]
+    th = np.linalg.norm(om, axis=1)
+    small = th < 1e-5
+    t1 = np.where(small, 1.0, th)
+    Om = np.zeros((len(u), 3, 3))
+    Om[:, 0, 1], Om[:, 0, 2] = -om[:, 2], om[:, 1]
+    Om[:, 1, 0], Om[:, 1, 2] = om[:, 2], -om[:, 0]
+    Om[:, 2, 0], Om[:, 2, 1] = -om[:, 1], om[:, 0]
+    Om2 = Om @ Om
+    a = np.where(small, 1.0, np.sin(t1) / t1)[:, None, None]
+    b = np.where(small, 0.5, (1 - np.cos(t1)) / (t1 * t1))[:, None, None]
+    d = np.where(small, 1.0 / 6.0, (t1 - np.sin(t1)) / (t1 * t1 * t1))[:, None, None]
+    eye = np.eye(3)[None]
+    return eye + a * Om + b * Om2, np.einsum("nij,nj->ni", eye + b * Om + d * Om2, ups)
+
+
+def _spd_info(rng, n, sg):
+    """sigma^-1 (I + A)(I + A)^T sigma^-1 with A random per edge: SPD, not diagonal."""
+    D = len(sg)
+    A = np.eye(D) + 0.3 * rng.standard_normal((n, D, D))
+    info = np.einsum("nij,nkj->nik", A, A) / (sg[:, None] * sg[None, :])
+    return 0.5 * (info + np.transpose(info, (0, 2, 1)))
+
+
+def expmap_pose_graph(num_poses: int = 200, loops: int = 40, rot_noise: float = 0.01, trans_noise: float = 0.02,
+                      init: str = "odometry", seed: int = SEED) -> Problem:
+    """A pose graph on the BA camera parameterisation: ``num_poses`` VertexSE3Expmap cameras (world->camera, as in
+    :func:`ba`) on a rising circle of radius 5, looking along the direction of travel, joined by EdgeSE3Expmap
+    odometry (i, i + 1) and ``loops`` loop closures (i, j), j > i + 1, drawn at random.  With the edge's error
+    log(Tj^-1 C Ti) the measurement is C = Tj exp(noise) Ti^-1 of the true poses: at the true poses the error of an
+    edge is its noise, (omega, upsilon) with sigmas (``rot_noise``, ``trans_noise``).  The information is
+    sigma^-1 (I + A)(I + A)^T sigma^-1 with A random per edge: SPD, not diagonal.  Pose 0 is fixed.  Initial
+    estimates: ``init`` = "odometry" chains the measured odometry from pose 0, "truth" takes the true poses."""
+    n = num_poses
+    rng = _rng(seed, 60)
+    th = 2 * math.pi * np.arange(n) / max(n, 8) * 1.0
+    pos = np.stack([5 * np.cos(th), 5 * np.sin(th), 0.02 * np.arange(n)], 1)
+    zero, one = np.zeros(n), np.ones(n)
+    # camera-to-world attitude: x right (outward radial), y down (-z), z forward (tangent); a small random tilt on top
+    Rc = np.stack([np.stack([np.cos(th), zero, -np.sin(th)], 1), np.stack([np.sin(th), zero, np.cos(th)], 1),
+                   np.stack([zero, -one, zero], 1)], 1) @ _small_rot(rng, n, 0.05)
+    Rw = np.transpose(Rc, (0, 2, 1))
+    tw = -np.einsum("nij,nj->ni", Rw, pos)
+    a = np.arange(0, n - 1)
+    b = np.arange(1, n)
+    if loops > 0 and n > 2:
+        la = rng.integers(0, n - 2, loops)
+        lb = la + 2 + (rng.random(loops) * (n - 2 - la)).astype(np.int64)
+        a, b = np.concatenate([a, la]), np.concatenate([b, np.minimum(lb, n - 1)])
+    m = len(a)
+    sg = np.array([rot_noise] * 3 + [trans_noise] * 3)
+    Rn, tn = _se3_exp(rng.standard_normal((m, 6)) * sg)
+    # C = Tj * N * Ti^-1, (R1, t1) * (R2, t2) = (R1 R2, t1 + R1 t2)
+    Rjn, tjn = Rw[b] @ Rn, tw[b] + np.einsum("nij,nj->ni", Rw[b], tn)
+    Rm = Rjn @ np.transpose(Rw[a], (0, 2, 1))
+    tm = tjn - np.einsum("nij,nj->ni", Rm, tw[a])
+    meas = np.concatenate([tm, rot_to_quat(Rm)], axis=1)
+    info = _spd_info(rng, m, sg)
+    if init == "truth":
+        R0, t0 = Rw, tw
+    else:  # Tj = C * Ti along the odometry edges (zero error on them)
+        Rq = quat_to_rot(meas[: n - 1, 3:7])
+        R0, t0 = np.empty((n, 3, 3)), np.empty((n, 3))
+        R0[0], t0[0] = Rw[0], tw[0]
+        for i in range(1, n):
+            R0[i] = Rq[i - 1] @ R0[i - 1]
+            t0[i] = Rq[i - 1] @ t0[i - 1] + tm[i - 1]
+    fixed = np.zeros(n, np.int32)
+    fixed[0] = 1
+    ids = np.arange(n, dtype=np.int32)
+    verts = VertexSet(V_SE3_EXPMAP, ids, np.concatenate([t0, rot_to_quat(R0)], axis=1), fixed, np.zeros(n, np.int32))
+    edges = EdgeSet(E_SE3_EXPMAP, ids[a].copy(), ids[b].copy(), meas, info)
+    return Problem(f"expmap{n}l{loops}", [verts], [edges], 6, 0)
+
+
+# ---------------------------------------------------------------- pose-only projections
+def _pose_only_set(cam_ids, xw, uv, K, ur, bf, rng, pixel_sigma):
+    """One pose-only edge set: monocular (``ur`` None) or stereo. K: [n, 4] fx fy cx cy."""
+    n = len(cam_ids)
+    if ur is None:
+        return EdgeSet(E_SE3_PROJECT_XYZ_ONLYPOSE, cam_ids, None, uv, _spd_info(rng, n, np.full(2, pixel_sigma)),
+                       np.concatenate([xw, K], axis=1))
+    return EdgeSet(E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE, cam_ids, None, np.concatenate([uv, ur[:, None]], axis=1),
+                   _spd_info(rng, n, np.full(3, pixel_sigma)), np.concatenate([xw, K, np.full((n, 1), float(bf))], axis=1))
+
+
+def pose_only(num_cameras: int = 8, points_per_camera: int = 120, stereo: bool = False, pixel_noise: float = 1.0,
+              cam_rot_noise: float = 0.002, cam_trans_noise: float = 0.01, point_noise: float = 0.01,
+              bf: float = 100.3, seed: int = SEED) -> Problem:
+    """Pose optimisation: ``num_cameras`` free VertexSE3Expmap cameras, each observing its own points through
+    EdgeSE3ProjectXYZOnlyPose (``stereo``: EdgeStereoSE3ProjectXYZOnlyPose) edges.  Cameras, points and left-image
+    measurements are those of :func:`ba`'s scene maker with num_cameras * points_per_camera points, each seen by one
+    camera (the scene deals the points to the cameras at random, so a camera holds points_per_camera of them on
+    average); no camera is fixed.  Xw of an edge is the scene's point estimate (the true point plus ``point_noise``),
+    which nothing optimises.  Stereo: u_r = u_true - bf / z_true + noise, as :func:`ba_stereo`.  The information is
+    sigma^-1 (I + A)(I + A)^T sigma^-1 with A random per edge.  No landmarks: pose_dim 6, landmark_dim 0."""
+    prob, pc, uv_true = _ba_scene(num_cameras, num_cameras * points_per_camera, 1, 1, pixel_noise, cam_rot_noise,
+                                  cam_trans_noise, point_noise, 0, seed)
+    cams, pts = prob.vertices
+    e = prob.edges[0]
+    xw = pts.est[e.v0 - pts.ids[0]]
+    rng = _rng(seed, 61)
+    ur = None
+    if stereo:
+        ur = uv_true[:, 0] - bf / pc[:, 2] + _rng(seed, 62).standard_normal(len(e.v0)) * pixel_noise
+    es = _pose_only_set(e.v1.copy(), xw, e.meas.copy(), e.params.copy(), ur, bf, rng, pixel_noise)
+    return Problem(f"poseonly{num_cameras}x{points_per_camera}" + ("s" if stereo else ""), [cams], [es], 6, 0)
+
+
+def with_pose_only(prob: Problem, every: int = 3, per_camera: int = 20, stereo: bool = False, point_noise: float = 0.01,
+                   bf: float = 100.3, seed: int = SEED) -> Problem:
+    """A copy of a BA problem (:func:`ba`) with pose-only edges on every ``every``-th camera (fixed ones included:
+    their edges are inactive): the camera's first ``per_camera`` observations again, each as a pose-only edge whose Xw
+    is the point's estimate plus ``point_noise``.  Stereo: u_r = u - bf / z at the camera's and the point's estimates.
+    ``prob`` is left unchanged; vertex and edge sets are shared."""
+    cams, pts = prob.vertices[0], prob.vertices[1]
+    e = next(x for x in prob.edges if x.etype == E_SE3_PROJECT_XYZ)
+    rng = _rng(seed, 63)
+    sel = []
+    for c in cams.ids[::every]:
+        sel.append(np.nonzero(e.v1 == c)[0][:per_camera])
+    sel = np.concatenate(sel)
+    pt = pts.est[e.v0[sel] - pts.ids[0]]
+    xw = pt + rng.standard_normal(pt.shape) * point_noise
+    ur = None
+    if stereo:
+        ce = cams.est[e.v1[sel] - cams.ids[0]]
+        z = np.einsum("nij,nj->ni", quat_to_rot(ce[:, 3:7]), pt)[:, 2] + ce[:, 2]
+        ur = e.meas[sel, 0] - bf / z
+    es = _pose_only_set(e.v1[sel].copy(), xw, e.meas[sel].copy(), e.params[sel].copy(), ur, bf, rng, 1.0)
+    return Problem(prob.name + f"+poseonly{len(sel)}", prob.vertices, list(prob.edges) + [es], prob.pose_dim,
+                   prob.landmark_dim)
+
+
+def pose_only_twin(prob: Problem) -> Problem:
+    """The same graph with every pose-only edge replaced by the binary projection edge (E_SE3_PROJECT_XYZ,
+    E_STEREO_SE3_PROJECT_XYZ) to a **fixed** V_XYZ vertex at Xw, one new vertex (an unused id) per edge.  A fixed
+    vertex takes no part in the system, so H, b and the hessian order are the pose-only graph's.  For the monocular
+    type the twin's error is the pose-only edge's exactly; for the stereo type only to the float rounding of 1/z
+    (the pose-only edge rounds 1/z to float, the binary one bf)."""
+    next_id = max(int(v.ids.max()) for v in prob.vertices if len(v.ids)) + 1
+    verts, edges = list(prob.vertices), []
+    for es in prob.edges:
+        if es.etype not in POSE_ONLY_BINARY:
+            edges.append(es)
+            continue
+        n = len(es.v0)
+        ids = (next_id + np.arange(n)).astype(np.int32)
+        next_id += n
+        verts.append(VertexSet(V_XYZ, ids, es.params[:, :3].copy(), np.ones(n, np.int32), np.ones(n, np.int32)))
+        edges.append(EdgeSet(POSE_ONLY_BINARY[es.etype], ids, es.v0.copy(), es.meas.copy(), es.info.copy(),
+                             es.params[:, 3:].copy()))
+    return Problem(prob.name + "/twin", verts, edges, prob.pose_dim, prob.landmark_dim)

@@ -59,6 +59,14 @@ extern "C" {
                                         meas u v depth; params offset + fx fy cx cy (n*11), NULL is G2OHIP_ERR_ARG */
 #define G2OHIP_E_SE3_XYZ_DISPARITY 9 /* EdgeSE3PointXYZDisparity (EDGE_PROJECT_DISPARITY): meas u v 1/depth; params as
                                         G2OHIP_E_SE3_XYZ_DEPTH */
+#define G2OHIP_E_SE3_EXPMAP 10 /* EdgeSE3Expmap (EDGE_SE3:EXPMAP), types_six_dof_expmap.h:104-127: the pose-pose
+                                  constraint between two cameras, v0 = Ti and v1 = Tj both G2OHIP_V_SE3_EXPMAP; meas the
+                                  SE3Quat C as tx ty tz qx qy qz qw (n*7), in the convention of the vertex estimate
+                                  (the rotation is normalised to unit length, w >= 0); info 6x6 in (omega, upsilon)
+                                  order, rotation first, as the vertex's oplus; params NULL. error =
+                                  log(Tj^-1 * C * Ti); the Jacobians are the reference's adjoints (.cpp:278-293), exact
+                                  at zero error only. Generic slot path; lm_pcg6_3_eigen refuses a graph that holds
+                                  these edges (g2ohip_last_error says so) */
 /* An edge type the device does not know (any BaseBinaryEdge<D, E, Vi, Vj> between registered vertices of
  * dimension 2, 3 or 6): the host's own linearizeOplus (the type's analytic one, or BaseBinaryEdge's numeric
  * central differences, base_binary_edge.hpp:198-266) supplies the error and both Jacobians, see
@@ -77,7 +85,18 @@ extern "C" {
                                     info 6x6; params: the sensor offset x y z qx qy qz qw per edge (n*7,
                                     ParameterSE3Offset), NULL = identity */
 #define G2OHIP_E_XYZ_PRIOR 20    /* EdgeXYZPrior, edge_xyz_prior.cpp:63-70: v0 G2OHIP_V_XYZ; meas x y z; info 3x3 */
-/* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3 or 6 (pose-only reprojection, say): the
+/* The pose-only projections (pose optimisation on tracked frames): unary, v0 the camera (G2OHIP_V_SE3_EXPMAP); the
+ * 3-D point Xw and the intrinsics are members of the edge and come in params, one record per edge, NULL is
+ * G2OHIP_ERR_ARG. Edges whose intrinsics are all equal share one record on the device. Not carried by .g2o files (the
+ * reference's tags hold neither Xw nor the intrinsics): the loader skips the tags, g2ohip_save_g2o on a graph that
+ * holds such edges writes nothing and returns G2OHIP_ERR_UNSUPPORTED. */
+#define G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE 21 /* EdgeSE3ProjectXYZOnlyPose, types_six_dof_expmap.h:232-258, .cpp:569-599:
+                                    meas u v; info 2x2; params Xw.x Xw.y Xw.z fx fy cx cy (n*7) */
+#define G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE 22 /* EdgeStereoSE3ProjectXYZOnlyPose, .h:293-319, .cpp:601-665: meas
+                                    u_l v u_r; info 3x3; params Xw fx fy cx cy bf (n*8). As the reference's cam_project
+                                    keeps 1/z in a float (.cpp:602), the error sees 1/z rounded to float, the Jacobian
+                                    the double */
+/* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3 or 6 (an edge type of the application's own, say): the
  * host supplies the error and the Jacobian as for G2OHIP_E_HOSTJ, payload [e (D) | Ji (D x dim(v0))] row-major per
  * edge. meas unused (may be NULL); info D*D. */
 #define G2OHIP_E_HOSTJ_UNARY(D) (48 + (D)) /* D = error dimension, 1..6 */
@@ -142,7 +161,8 @@ int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int*
                      const double* info /* n * D*D row-major */, const double* params /* n*4, stereo n*5, or NULL */);
 /* params: the intrinsics of the projection types (G2OHIP_ERR_ARG when one of them gets NULL), the offsets of
  * G2OHIP_E_SE3_PRIOR and G2OHIP_E_SE3_XYZ (n*7, or NULL: identity), offset + intrinsics of G2OHIP_E_SE3_XYZ_DEPTH /
- * _DISPARITY (n*11, NULL is G2OHIP_ERR_ARG), NULL for the others. v1: NULL for the unary types (and only for them). */
+ * _DISPARITY (n*11, NULL is G2OHIP_ERR_ARG), the point and intrinsics of the pose-only projections (Xw fx fy cx cy,
+ * n*7, stereo + bf, n*8; NULL is G2OHIP_ERR_ARG), NULL for the others (G2OHIP_E_SE3_EXPMAP among them). v1: NULL for the unary types (and only for them). */
 /* .g2o files do not carry G2OHIP_E_STEREO_SE3_PROJECT_XYZ: the reference's reader and writer for its tag
  * (EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP, types_six_dof_expmap.cpp:469-493) move four measurement values through a
  * 3-vector and no intrinsics. The loader skips the tag like any unknown one; g2ohip_save_g2o on a graph that holds
@@ -160,6 +180,13 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * paramId m0 m1 m2, then the six upper-triangle information values) load as G2OHIP_E_SE3_XYZ, _DEPTH and _DISPARITY. A
  * parameter id that no line defines, or one of the wrong kind, fails the load with the id in g2ohip_last_error. */
 #define G2OHIP_LOAD_SLAM3D 2u
+/* G2OHIP_LOAD_EXPMAP (may be combined with the other flags): EDGE_SE3:EXPMAP v0 v1 m0..m6, then the 21 upper-triangle
+ * information values, loads as G2OHIP_E_SE3_EXPMAP. As in the reference (types_six_dof_expmap.cpp:114-129) the seven
+ * values are cam2world and the stored measurement is their inverse; the information is taken as is. A short line, or
+ * an endpoint that is no VERTEX_SE3:EXPMAP, fails the load (g2ohip_last_error names the tag). Without the flag the tag
+ * is skipped like any unknown one. The pose-only projection tags (EDGE_SE3_PROJECT_XYZONLYPOSE:EXPMAP,
+ * EDGE_STEREO_SE3_PROJECT_XYZONLYPOSE:EXPMAP) are always skipped: see G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE. */
+#define G2OHIP_LOAD_EXPMAP 4u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
@@ -167,7 +194,9 @@ int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, u
  * ones are. The slam3d landmark edges are written as EDGE_SE3_TRACKXYZ / EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY
  * (edge_se3_pointxyz.cpp:88-96 and its siblings), their parameters as PARAMS_SE3OFFSET / PARAMS_CAMERACALIB lines, one
  * per distinct record, in one id space with the prior offsets; a G2OHIP_V_XYZ vertex one of these edges touches is
- * written as VERTEX_TRACKXYZ. */
+ * written as VERTEX_TRACKXYZ. G2OHIP_E_SE3_EXPMAP edges are written as EDGE_SE3:EXPMAP with the inverse of the
+ * measurement and the upper triangle of the information (types_six_dof_expmap.cpp:131-140). A graph holding pose-only
+ * projection edges is not written: G2OHIP_ERR_UNSUPPORTED, as for G2OHIP_E_STEREO_SE3_PROJECT_XYZ. */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
@@ -198,8 +227,8 @@ int g2ohip_set_host_edge_callback(g2ohip_graph* g, g2ohip_host_edge_fn fn, void*
 long long g2ohip_host_payload_len(g2ohip_graph* g, int edge_type);
 
 /* OptimizationAlgorithmFactory::construct by name; default "lm_hip_var". "lm_pcg6_3_eigen" (matrix-free CGLS on the
- * Jacobian of BA edges) does not take unary edges: building the structure of such a graph under it returns
- * G2OHIP_ERR_UNSUPPORTED. */
+ * Jacobian of BA edges) does not take unary edges (priors, the pose-only projections), the slam3d landmark edges or
+ * G2OHIP_E_SE3_EXPMAP: building the structure of such a graph under it returns G2OHIP_ERR_UNSUPPORTED. */
 int g2ohip_set_algorithm(g2ohip_graph* g, const char* name);
 /* SparseOptimizer::initializeOptimization(0): active edges/vertices, index mapping */
 int g2ohip_initialize(g2ohip_graph* g);
