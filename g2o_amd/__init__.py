@@ -101,7 +101,8 @@ EXPORTS = [
     "g2ohip_kernel_count", "g2ohip_kernel_bytes", "g2ohip_kernel_flops", "g2ohip_last_error",
     "g2ohip_version", "g2ohip_host_payload_len", "g2ohip_solver_save_hessian", "g2ohip_solver_set_write_debug",
     "g2ohip_comm_local_reduce_host", "g2ohip_runtime_info", "g2ohip_device_synchronize", "g2ohip_lm_scale_factor",
-    "g2ohip_measure_peaks",
+    "g2ohip_measure_peaks", "g2ohip_set_dogleg_params", "g2ohip_dogleg_state", "g2ohip_dogleg_blend",
+    "g2ohip_dogleg_next_delta",
 ]
 
 
@@ -187,6 +188,10 @@ def lib() -> C.CDLL:
         "g2ohip_version": ([], C.c_char_p),
         "g2ohip_lm_scale_factor": ([D], D),
         "g2ohip_measure_peaks": ([I, P, I], I),
+        "g2ohip_set_dogleg_params": ([P, D, I, D, D], I),
+        "g2ohip_dogleg_state": ([P, P, I], I),
+        "g2ohip_dogleg_blend": ([D, D, D, D, D, D, P], I),
+        "g2ohip_dogleg_next_delta": ([D, D, D], D),
         "g2ohip_host_payload_len": ([P, I], LL),
         "g2ohip_solver_save_hessian": ([P, C.c_char_p], I),
         "g2ohip_solver_set_write_debug": ([P, I], I),
@@ -212,6 +217,19 @@ def runtime_info() -> dict:
 
 def device_synchronize(device: int = 0) -> None:
     _check(lib().g2ohip_device_synchronize(device), "device_synchronize")
+
+
+def dogleg_blend(hgn_norm, hsd_norm, hsd_sq, c, bma_sq, delta):
+    """The dogleg trial's step choice as host and device take it: (step type 1 SD / 2 GN / 3 DL, coef0, coef1) with
+    hdl = coef0 hsd + coef1 hgn (optimization_algorithm_dogleg.cpp:153-175). Needs no GPU."""
+    coef = np.zeros(2)
+    step = lib().g2ohip_dogleg_blend(hgn_norm, hsd_norm, hsd_sq, c, bma_sq, delta, _p(coef))
+    return int(step), float(coef[0]), float(coef[1])
+
+
+def dogleg_next_delta(delta, rho, hdl_norm) -> float:
+    """The trust-region update (optimization_algorithm_dogleg.cpp:199-203). Needs no GPU."""
+    return float(lib().g2ohip_dogleg_next_delta(delta, rho, hdl_norm))
 
 
 def measure_peaks(device: int = 0) -> dict:
@@ -320,8 +338,8 @@ def linear_solve_ccs(n, Ap, Ai, Ax, b, block_dim=1, device=0, info=False):
 
 
 class SparseOptimizer:
-    """g2o::SparseOptimizer with a device-resident ``lm_hip_*`` algorithm
-    (sparse_optimizer.h; optimization_algorithm_levenberg.h)."""
+    """g2o::SparseOptimizer with a device-resident ``lm_hip_*``, ``gn_hip_*`` or ``dl_hip_*`` algorithm
+    (sparse_optimizer.h; optimization_algorithm_levenberg.h, ..._gauss_newton.h, ..._dogleg.h)."""
 
     def __init__(self, device: int = 0):
         self.h = lib().g2ohip_graph_create(device)
@@ -429,6 +447,22 @@ class SparseOptimizer:
 
     def set_algorithm(self, name: str):
         _check(lib().g2ohip_set_algorithm(self.h, name.encode()), "set_algorithm")
+
+    def set_dogleg_params(self, initial_delta: float = 0.0, max_trials: int = 0, initial_lambda: float = 0.0,
+                          lambda_factor: float = 0.0):
+        """OptimizationAlgorithmDogleg's properties for the dl_hip_* algorithms (initialDelta 1e4,
+        maxTrialsAfterFailure 100, initialLambda 1e-7, lambdaFactor 10); a value <= 0 selects the default."""
+        _check(lib().g2ohip_set_dogleg_params(self.h, float(initial_delta), int(max_trials), float(initial_lambda),
+                                              float(lambda_factor)), "set_dogleg_params")
+
+    DOGLEG_STEPS = ("Undefined", "Descent", "GN", "Dogleg")  # stepType2Str, by the reference's enum order
+
+    def dogleg_state(self) -> dict:
+        """After the last dl_hip_* iteration: trustRegion(), lastStep (1 SD, 2 GN, 3 DL, 0 undefined), lastNumTries,
+        the damping of the not-PD branch and wasPDInAllIterations."""
+        out = np.zeros(5)
+        _check(lib().g2ohip_dogleg_state(self.h, _p(out), 5), "dogleg_state")
+        return dict(delta=float(out[0]), step=int(out[1]), tries=int(out[2]), lam=float(out[3]), was_pd=bool(out[4]))
 
     def initialize_optimization(self):
         _check(lib().g2ohip_initialize(self.h), "initializeOptimization")

@@ -37,9 +37,12 @@ int algorithm_known(const std::string& n) {
   // {gn,lm}_hip_{var,fix6_3,fix3_2,fix3_3,fix6_6} (cf. solver_csparse.cpp:51-84 name parsing)
   if (n.size() < 6) return 0;
   const std::string m = n.substr(0, 3), rest = n.substr(3);
-  if (m != "lm_" && m != "gn_") return 0;
+  if (m != "lm_" && m != "gn_" && m != "dl_") return 0;
   if (rest == "hip_var" || rest == "hip_fix6_3" || rest == "hip_fix3_2" || rest == "hip_fix3_3" || rest == "hip_fix6_6")
     return 1;
+  // Powell's dogleg needs an exact Gauss-Newton solve: the reference registers dl_* over the Cholesky solvers only
+  // (solver_csparse.cpp), never over PCG
+  if (m == "dl_") return 0;
   // g2o/solvers/pcg registry (solver_pcg.cpp:91-98): pcg (variable block size), pcg3_2, pcg6_3, pcg7_3.
   // Block-Jacobi PCG on the device replaces the Cholesky; pose blocks of 3 or 6 only.
   if (rest == "pcg" || rest == "pcg6_3" || rest == "pcg3_2") return 1;
@@ -171,7 +174,20 @@ int g2ohip_set_algorithm(g2ohip_graph* g, const char* name) {
     return G2OHIP_ERR_ARG;
   }
   g->e->algorithm = name;
-  g->e->levenberg = std::string(name).rfind("lm_", 0) == 0;
+  const std::string m = std::string(name).substr(0, 3);
+  g->e->algo = m == "lm_" ? g2ohip::Engine::Algo::Levenberg
+               : m == "dl_" ? g2ohip::Engine::Algo::Dogleg
+                            : g2ohip::Engine::Algo::GaussNewton;
+  return G2OHIP_OK;
+}
+int g2ohip_set_dogleg_params(g2ohip_graph* g, double initial_delta, int max_trials_after_failure, double initial_lambda,
+                             double lambda_factor) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return g->e->set_dogleg_params(initial_delta, max_trials_after_failure, initial_lambda, lambda_factor);
+}
+int g2ohip_dogleg_state(g2ohip_graph* g, double* out, int n) {
+  if (!g || !out || n < 5) return G2OHIP_ERR_ARG;
+  g->e->dogleg_state(out);
   return G2OHIP_OK;
 }
 int g2ohip_initialize(g2ohip_graph* g) {
@@ -574,6 +590,13 @@ int g2ohip_measure_peaks(int device, double* out, int n) {
   });
 }
 double g2ohip_lm_scale_factor(double rho) { return g2ohip::lm_scale_factor(rho); }
+int g2ohip_dogleg_blend(double hgn_norm, double hsd_norm, double hsd_sq, double c, double bma_sq, double delta,
+                        double coef[2]) {
+  return g2ohip::dogleg_blend(hgn_norm, hsd_norm, hsd_sq, c, bma_sq, delta, coef);
+}
+double g2ohip_dogleg_next_delta(double delta, double rho, double hdl_norm) {
+  return g2ohip::dogleg_next_delta(delta, rho, hdl_norm);
+}
 const char* g2ohip_version(void) { return "g2o_hip 0.2.0 (gfx950)"; }
 
 }  // extern "C"

@@ -130,4 +130,44 @@ __host__ __device__ inline double lm_scale_factor(double rho) {
   return 1. / 3. > alpha ? 1. / 3. : alpha;
 }
 
+// OptimizationAlgorithmDogleg's two scalar decisions, shared by the device kernels (k_dl_blend, k_dl_decide) and the
+// host (g2ohip_dogleg_blend, g2ohip_dogleg_next_delta). Products and sums are rounded one by one (no contraction into
+// FMAs), so host and device take the same branch on the same doubles.
+enum DoglegStep { DL_STEP_UNDEFINED = 0, DL_STEP_SD = 1, DL_STEP_GN = 2, DL_STEP_DL = 3 };  // the reference's enum order
+// step choice and blend (optimization_algorithm_dogleg.cpp:153-175): hdl = coef[0] hsd + coef[1] hgn from |hgn|, |hsd|,
+// hsd.hsd, c = hsd.(hgn - hsd), |hgn - hsd|^2 and delta; hdl = hsd + beta (hgn - hsd) is coef = (1 - beta, beta)
+__host__ __device__ inline int dogleg_blend(double hgn_norm, double hsd_norm, double hsd_sq, double c, double bma_sq,
+                                            double delta, double coef[2]) {
+#pragma clang fp contract(off)
+  if (hgn_norm < delta) {  // :153-155
+    coef[0] = 0.0;
+    coef[1] = 1.0;
+    return DL_STEP_GN;
+  }
+  if (hsd_norm > delta) {  // :157-159
+    coef[0] = delta / hsd_norm;
+    coef[1] = 0.0;
+    return DL_STEP_SD;
+  }
+  double beta;  // :161-173
+  if (c <= 0.) {
+    beta = (-c + sqrt(c * c + bma_sq * (delta * delta - hsd_sq))) / bma_sq;
+  } else {
+    beta = (delta * delta - hsd_sq) / (c + sqrt(c * c + bma_sq * (delta * delta - hsd_sq)));
+  }
+  coef[0] = 1.0 - beta;
+  coef[1] = beta;
+  return DL_STEP_DL;
+}
+// trust-region update (:199-203)
+__host__ __device__ inline double dogleg_next_delta(double delta, double rho, double hdl_norm) {
+#pragma clang fp contract(off)
+  if (rho > 0.75) {
+    const double t = 3 * hdl_norm;
+    return delta < t ? t : delta;  // std::max(delta, t)
+  }
+  if (rho < 0.25) return delta * 0.5;
+  return delta;
+}
+
 }  // namespace g2ohip

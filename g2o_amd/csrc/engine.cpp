@@ -6,6 +6,8 @@
 //       (block_solver.hpp:102-256, 462-565, 314-447)
 //   OptimizationAlgorithmLevenberg::solve / computeLambdaInit / computeScale
 //       (optimization_algorithm_levenberg.cpp:58-184)
+//   OptimizationAlgorithmGaussNewton::solve (optimization_algorithm_gauss_newton.cpp:50-92)
+//   OptimizationAlgorithmDogleg::solve (optimization_algorithm_dogleg.cpp:57-208)
 //   SparseOptimizer::optimize (sparse_optimizer.cpp:374-439), G2OBatchStatistics timers
 // The graph state lives in HBM during optimize(); the host only reads scalars
 // (chi2, scale, the not-PD flag) once per LM trial.
@@ -2581,6 +2583,11 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     int r = initialize();
     if (r) return r;
   }
+  if (algo == Algo::Dogleg && nranks > 1)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                      algorithm + ": Powell's dogleg is not supported on a sharded graph (" + std::to_string(nranks) +
+                          " ranks): it multiplies by Hpp (multiplyHessian), and a landmark shard's Hpp diagonal "
+                          "blocks are partial sums; use lm_hip_* or gn_hip_* there");
   if (use_cgls())
     for (const HEdgeSet& es : hg.esets)
       if (is_slam3d_type(es.type) && !es.ev0.empty())
@@ -3612,7 +3619,7 @@ int Engine::solve_sync() {
   return f[0] ? 0 : 1;
 }
 
-void Engine::update_async() {  // sparse_optimizer.cpp:441-454
+void Engine::update_async(const double* x) {  // sparse_optimizer.cpp:441-454
   timer.begin("oplus", stream);
   launch::OplusList L;
   for (int t = 1; t < NVT; ++t) {
@@ -3625,7 +3632,7 @@ void Engine::update_async() {  // sparse_optimizer.cpp:441-454
     if (t == G2OHIP_V_SE3_QUAT) L.nopl = dnopl.get();
     ++L.cnt;
   }
-  launch::oplus_multi(L, dx.get(), stream);
+  launch::oplus_multi(L, x ? x : dx.get(), stream);
   timer.end(stream);
   host_state_stale = true;
   ++state_ver;
@@ -3936,6 +3943,169 @@ int Engine::gn_solve(int iteration, g2ohip_batch_stats* st) {
   return f[0] == 0 ? 0 : 2;
 }
 
+int Engine::set_dogleg_params(double initial_delta, int max_trials, double initial_lambda, double lambda_factor) {
+  if (std::isnan(initial_delta) || std::isnan(initial_lambda) || std::isnan(lambda_factor)) return G2OHIP_ERR_ARG;
+  dl_user_delta = initial_delta > 0 ? initial_delta : 1e4;       // optimization_algorithm_dogleg.cpp:45
+  dl_max_trials = max_trials > 0 ? max_trials : 100;             // :46
+  dl_initial_lambda = initial_lambda > 0 ? initial_lambda : 1e-7;  // :47
+  dl_lambda_factor = lambda_factor > 0 ? lambda_factor : 10.0;   // :48
+  return G2OHIP_OK;
+}
+void Engine::dogleg_state(double* out) const {
+  out[0] = dl_delta;
+  out[1] = dl_last_step;
+  out[2] = dl_last_tries;
+  out[3] = dl_lambda;
+  out[4] = dl_was_pd ? 1.0 : 0.0;
+}
+
+// OptimizationAlgorithmDogleg::solve (optimization_algorithm_dogleg.cpp:57-208), the whole loop on the device: per
+// iteration one assembly, the alpha pass, one Gauss-Newton factorization (more only while the not-PD damping climbs)
+// and the delta-independent sums; per trial a blend, the Hpp product of the linear gain, push + oplus, the errors and
+// one decision kernel whose 16 scalars are the trial's only readback. A rejected trial re-blends; nothing is factored
+// again.
+int Engine::dl_solve(int iteration, g2ohip_batch_stats* st) {
+  if (iteration == 0) {  // :64-79 (online: optimize_step keeps the structure and dl_* start over, as lm_* do)
+    if (!structure_built) {
+      const double t0 = wall();
+      if (build_structure()) return 2;  // Fail (:66-70)
+      if (st) st->timeSymbolicDecomposition = wall() - t0;
+    }
+    dl_delta = dl_user_delta;        // :76
+    dl_lambda = dl_initial_lambda;   // :77
+    dl_was_pd = true;                // :78
+  }
+  double t = wall();
+  const double currentChi = chi2_sync();  // :82, :89
+  if (st) st->timeResiduals = wall() - t;
+  const bool ev1 = st && stats_level >= 1, ev2 = st && stats_level >= 2;
+  hipEvent_t e0 = lm_ev_[0], e1 = lm_ev_[1], e2 = lm_ev_[2], e3 = lm_ev_[3], q0 = lm_ev_[4], q1 = lm_ev_[5];
+  // :91. Always the plain buildSystem: multiplyHessian reads the whole Hpp, which a Schur-split assembly (an earlier
+  // lm_* iteration's speculative one included) leaves without its diagonal blocks
+  if (ev2) HIP_CHECK(hipEventRecord(q0, stream));
+  build_system();
+  if (ev2) HIP_CHECK(hipEventRecord(q1, stream));
+  built_ver = 0;
+  if (symv_hpp.key != structure_ver) {
+    symv_hpp.setup(num_poses, pd, hpp_bi, hpp_bj, stream);
+    symv_hpp.key = structure_ver;
+  }
+  const long long n = vector_size();
+  dhdl.resize((size_t)n);
+  ddl.resize(32);
+  ddl_part.resize(launch::dl_partials(size_poses, n));
+  const launch::DoglegSymv Hp{pd, size_poses, symv_hpp.rptr.get(), symv_hpp.ent.get(), symv_hpp.diag.get(), dH.get()};
+  // :98-105 alpha = |b|^2 / (aux . b), aux = Hpp b_p with its landmark part zero (block_solver.h:146), |b|^2 over the
+  // full vector; hsd = alpha b is not stored
+  timer.begin("dogleg", stream);
+  launch::dl_alpha(Hp, n, db.get(), ddl_part.get(), ddl.get(), stream);
+  timer.end(stream);
+
+  int& numTries = dl_last_tries;
+  numTries = 1;  // :113 (the Gauss-Newton solve belongs to the first trial)
+  {  // :115-148
+    const double minLambda = 1e-12, maxLambda = 1e3;
+    bool solverOk = false, first = true;
+    while (!solverOk) {
+      // :125-126 setLambda while not PD in some iteration before (lambda is virtual here: never in H, so
+      // restoreDiagonal, :128-129, is the reset to 0 below and the gain's multiplyHessian never sees it)
+      set_lambda_device(dl_was_pd ? 0.0 : dl_lambda, true);  // also clears the not-PD flags
+      if (ev1 && first) HIP_CHECK(hipEventRecord(e0, stream));
+      solve_async(false);  // :127
+      if (ev1 && first) HIP_CHECK(hipEventRecord(e1, stream));
+      int f[2] = {0, 0};
+      HIP_CHECK(hipMemcpyAsync(f, failp(), sizeof f, hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      timer.collect();
+      if (first) {
+        float ms = 0;
+        if (ev2) {
+          HIP_CHECK(hipEventElapsedTime(&ms, q0, q1));
+          st->timeQuadraticForm = ms * 1e-3;
+        }
+        if (ev1) {
+          HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+          st->timeLinearSolution = ms * 1e-3;
+        }
+        if (ev2 && ev_valid_) {
+          float a = 0, b = 0, c = 0;
+          HIP_CHECK(hipEventElapsedTime(&a, ev_[0], ev_[1]));
+          HIP_CHECK(hipEventElapsedTime(&b, ev_[1], ev_[2]));
+          HIP_CHECK(hipEventElapsedTime(&c, ev_[1], ev_[3]));
+          st->timeSchurComplement = do_schur ? a * 1e-3 : 0.0;
+          st->timeNumericDecomposition = b * 1e-3;
+          st->timeLinearSolver = c * 1e-3;
+        }
+      }
+      first = false;
+      solverOk = f[0] == 0;
+      if (!solverOk && write_debug && rank == 0) write_debug_dump();
+      dl_was_pd = dl_was_pd && solverOk;  // :130
+      if (!dl_was_pd) {                   // :131-142
+        if (solverOk) {
+          dl_lambda = std::max(minLambda, dl_lambda / (0.5 * dl_lambda_factor));
+        } else {
+          dl_lambda *= dl_lambda_factor;
+          if (dl_lambda > maxLambda) {
+            dl_lambda = maxLambda;
+            set_lambda_device(0.0);
+            return 2;  // Fail
+          }
+        }
+      }
+    }
+    if (lambda_host != 0.0) set_lambda_device(0.0);  // restoreDiagonal
+  }
+  // :147, :161-163 |hgn|, c = hsd . (hgn - hsd), |hgn - hsd|^2: they do not depend on delta, so once per iteration
+  timer.begin("dogleg", stream);
+  launch::dl_post(n, dx.get(), db.get(), ddl_part.get(), ddl.get(), stream);
+  timer.end(stream);
+
+  bool goodStep = false;
+  double chiLeft = currentChi;
+  for (;;) {  // :112-204
+    // :153-175 the step for this delta, :178-180 the Hpp product and dot products of the linear gain
+    timer.begin("dogleg", stream);
+    launch::dl_blend(n, dx.get(), db.get(), ddl.get(), dl_delta, dhdl.get(), stream);
+    launch::dl_gain_partials(Hp, n, dhdl.get(), db.get(), ddl_part.get(), stream);
+    timer.end(stream);
+    push();  // :183
+    if (ev2) HIP_CHECK(hipEventRecord(e2, stream));
+    update_async(dhdl.get());  // :184
+    if (ev2) HIP_CHECK(hipEventRecord(e3, stream));
+    compute_errors_async(false);  // :185-186 (host-Jacobian groups: their errors through the callback)
+    // :187-203 linearGain, rho, accepted and the next delta, decided on the device
+    timer.begin("dogleg", stream);
+    launch::dl_decide(Hp, n, ddl_part.get(), ddl.get(), dscal.get() + 1, currentChi, dl_delta, stream);
+    timer.end(stream);
+    HIP_CHECK(hipMemcpyAsync(hscal_, ddl.get() + launch::DL_OUT, 16 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    timer.collect();
+    if (ev2) {
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, e2, e3));
+      st->timeUpdate = ms * 1e-3;
+    }
+    dl_last_step = (int)hscal_[launch::DLO_STEP];
+    dl_delta = hscal_[launch::DLO_DELTA];
+    if (hscal_[launch::DLO_ACCEPT] != 0.0) {  // :192-194
+      discard_top();
+      goodStep = true;
+      chiLeft = hscal_[launch::DLO_CHI];
+    } else {  // :195-197
+      pop();
+    }
+    if (goodStep || numTries >= dl_max_trials) break;  // :204
+    ++numTries;
+  }
+  // the state left behind: the accepted trial's (its chi2 is newChi), or the popped one
+  chi_cache = chiLeft;
+  chi_ver = state_ver;
+  levenberg_iterations = 0;
+  if (numTries == dl_max_trials || !goodStep) return 1;  // Terminate (:205-206)
+  return 0;
+}
+
 int Engine::optimize_step(const g2ohip_config* cfgp, int i, g2ohip_batch_stats* st) {
   g2ohip_config cfg{10, 0.0, 0};
   if (cfgp) cfg = *cfgp;
@@ -3952,19 +4122,30 @@ int Engine::optimize_step(const g2ohip_config* cfgp, int i, g2ohip_batch_stats* 
     st->numVertices = (int)active.size();
   }
   const double ts = wall();
-  const int result = levenberg ? lm_solve(i, cfg, st) : gn_solve(i, st);
+  const bool levenberg = algo == Algo::Levenberg, dogleg = algo == Algo::Dogleg;
+  // (cfg's max_trials_after_failure and user_lambda_init are OptimizationAlgorithmLevenberg's: dl_* has its own,
+  // set_dogleg_params)
+  const int result = levenberg ? lm_solve(i, cfg, st) : dogleg ? dl_solve(i, st) : gn_solve(i, st);
   if (st || cfg.verbose) {
     const double c = chi2_sync();
     if (st) {
       st->chi2 = c;
-      st->lambda = levenberg ? current_lambda : 0.0;
+      // dogleg: the damping of the not-PD branch while it is in use (levenbergIterations stays 0: the reference's
+      // dogleg never sets it)
+      st->lambda = levenberg ? current_lambda : (dogleg && !dl_was_pd) ? dl_lambda : 0.0;
       st->timeIteration = wall() - ts;
       st->hessianPoseDimension = size_poses;
       st->hessianLandmarkDimension = size_landmarks;
       st->hessianDimension = size_poses + size_landmarks;
       st->choleskyNNZ = (long long)chol.sym.nnzL;
     }
-    if (cfg.verbose && rank == 0)
+    if (cfg.verbose && rank == 0 && dogleg) {  // printVerbose (optimization_algorithm_dogleg.cpp:210-218)
+      static const char* const step_name[] = {"Undefined", "Descent", "GN", "Dogleg"};
+      fprintf(stderr, "iteration= %d\t chi2= %.6f\t time= %g\t edges= %zu\t Delta= %g\t step= %s\t tries= %d", i, c,
+              wall() - ts, (size_t)hg.num_edges(), dl_delta, step_name[dl_last_step & 3], dl_last_tries);
+      if (!dl_was_pd) fprintf(stderr, "\t lambda= %g", dl_lambda);
+      fprintf(stderr, "\n");
+    } else if (cfg.verbose && rank == 0)
       fprintf(stderr, "iteration= %d\t chi2= %.6f\t time= %g\t edges= %zu\t lambda= %.6f\t levenbergIter= %d\n", i, c,
               wall() - ts, (size_t)hg.num_edges(), current_lambda, levenberg_iterations);
   }
@@ -4305,6 +4486,13 @@ double Engine::kernel_bytes(const std::string& name) const {
   }
   if (name == "backsub") return local_lm.size() * (3 * 8.0 * 2 + 72) + npl * (pb + 4) + size_poses * 8.0;
   if (name == "chol_factor") return (double)chol.sym.front_pool * 8 * 2;
+  // dl_solve's own launches over one iteration with one trial (the class holds four timed records then: alpha, post,
+  // blend + gain, decide): two Hpp products (every off-diagonal upper block read from both of its block rows, the vector
+  // gathered per block), the full-length passes b, b | x, b | x, b, hdl written | hdl, b
+  if (name == "dogleg") {
+    const double nblk = 2.0 * (double)hpp_bi.size() - num_poses;
+    return 2 * nblk * (pd * pd + pd) * 8.0 + (2 + 2 + 3 + 2) * 8.0 * (double)vector_size();
+  }
   if (name == "linearize_unary") {  // per edge: vertex index + hessian index, edge data (payload + packed information),
                                     // the vertex state read, the slot written
     double by = 0;
@@ -4330,6 +4518,10 @@ double Engine::kernel_flops(const std::string& name) const {
     return fl;
   }
   if (name == "chol_factor") return chol.sym.flops;
+  // one iteration with one trial (see kernel_bytes): two Hpp products and their row dots, 2 + 8 + 4 + 4 flops per
+  // element of the full-length passes
+  if (name == "dogleg")
+    return 2 * ((2.0 * (double)hpp_bi.size() - num_poses) * 2.0 * pd * pd + 2.0 * size_poses) + 18.0 * (double)vector_size();
   if (name == "schur_rows") return (double)npairs * (108 * 2);
   return 0;
 }

@@ -238,7 +238,14 @@ class Engine {
   std::string algorithm = "lm_hip_var";
   // G2OBatchStatistics timers: 0 none, 1 timeLinearSolution only (2 events per trial), 2 every stage
   int stats_level = 2;
-  bool levenberg = true;
+  // the optimization algorithm over the BlockSolver: OptimizationAlgorithmLevenberg (lm_*), ...GaussNewton (gn_*),
+  // ...Dogleg (dl_*)
+  enum class Algo { GaussNewton, Levenberg, Dogleg };
+  Algo algo = Algo::Levenberg;
+  // OptimizationAlgorithmDogleg properties (optimization_algorithm_dogleg.cpp:45-48); a value <= 0: the default
+  int set_dogleg_params(double initial_delta, int max_trials, double initial_lambda, double lambda_factor);
+  // [delta, lastStep, lastNumTries, currentLambda, wasPDInAllIterations] after the last dogleg iteration
+  void dogleg_state(double* out) const;
 
   // ---- graph ops ----
   int add_vertices(int type, int n, const int* ids, const double* est, const int* fixed, const int* marg);
@@ -489,11 +496,19 @@ class Engine {
   void ensure_hpp();
   void solve_async(bool reset_fail);
   int* failp() const { return reinterpret_cast<int*>(dscal.get() + 8); }
-  void update_async();
+  void update_async(const double* x = nullptr);  // oplus of every vertex with x (default: dx, the solver's x)
   void set_lambda_device(double l, bool reset_fail = false);
   void allreduce_sum(double* dptr, size_t n);
   int lm_solve(int iteration, const g2ohip_config& cfg, g2ohip_batch_stats* st);
   int gn_solve(int iteration, g2ohip_batch_stats* st);
+  int dl_solve(int iteration, g2ohip_batch_stats* st);
+  // dogleg state (optimization_algorithm_dogleg.h): properties, trust region, damping of the not-PD branch
+  double dl_user_delta = 1e4, dl_initial_lambda = 1e-7, dl_lambda_factor = 10.0;
+  int dl_max_trials = 100;
+  double dl_delta = 1e4, dl_lambda = 1e-7;
+  int dl_last_step = 0, dl_last_tries = 0;
+  bool dl_was_pd = true;
+  DevBuf<double> dhdl, ddl, ddl_part;  // the trial's step, the scalar block (launch::DoglegScalar), partial sums
   // upper blocks of the matrix the last factorization saw (S with lambda, or Hpp + lambda) as an Octave file
   void write_debug_dump();
 };

@@ -1563,6 +1563,210 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// ------------------------------------------------------------------------------ Powell dogleg
+// (optimization_algorithm_dogleg.cpp:57-208; Engine::dl_solve). Every sum is the fixed two-pass scheme above: per-block
+// partials in a fixed tree, one final workgroup adding them in a fixed order. No atomics.
+// The scalar block p (launch::DL_*): inputs of the trial at [0, 16), the trial's result at [16, 32) (the readback).
+
+// the RED_BLOCK tree of one value per thread; every thread gets the sum
+__device__ __forceinline__ double red_tree(double s, double* sh) {
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int m = RED_BLOCK / 2; m > 0; m >>= 1) {
+    if ((int)threadIdx.x < m) sh[threadIdx.x] += sh[threadIdx.x + m];
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+// k_sum_final's sum of partial[0, np) inside a workgroup
+__device__ __forceinline__ double red_final(const double* __restrict__ partial, int np, double* sh) {
+  double s = 0;
+  for (int i = threadIdx.x; i < np; i += RED_BLOCK) s += partial[i];
+  return red_tree(s, sh);
+}
+
+// multiplyHessian (block_solver.h:146: Hpp only, no lambda) of v's pose part fused with the dot products of its caller:
+// workgroups [0, nsb) are k_block_symv's rows (one per thread) and leave the partial of aux . v over their rows at
+// partial[blockIdx] (aux = Hpp v_p is never stored); workgroups [nsb, nsb + nps) are chunks of the full-length vectors
+// and leave w . v at partial[nsb + k] and v . v at partial[nsb + nps + k].
+// alpha pass (:99-102): v = w = b. Linear gain (:178-180): v = hdl, w = b.
+template <int PD>
+__global__ void __launch_bounds__(RED_BLOCK)
+    k_dl_symv_dots(int npose, long long n, int nsb, int nps, const int* __restrict__ rptr, const int2* __restrict__ ent,
+                   const int* __restrict__ diag, const double* __restrict__ vals, const double* __restrict__ v,
+                   const double* __restrict__ w, double* __restrict__ partial) {
+  __shared__ double sh[RED_BLOCK];
+  if ((int)blockIdx.x < nsb) {
+    const int row = blockIdx.x * RED_BLOCK + threadIdx.x;
+    double t = 0;
+    if (row < npose) {
+      const int i = row / PD, rr = row - i * PD;
+      const double* D = vals + (size_t)diag[i] * PD * PD;
+      double acc = 0;
+#pragma unroll
+      for (int c = 0; c < PD; ++c) acc += D[c * PD + rr] * v[(size_t)i * PD + c];
+      for (int e = rptr[i]; e < rptr[i + 1]; ++e) {
+        const int2 q = ent[e];
+        const int j = q.y & 0x7fffffff;
+        const double* B = vals + (size_t)q.x * PD * PD;
+        const double* vj = v + (size_t)j * PD;
+        if (q.y < 0) {
+#pragma unroll
+          for (int c = 0; c < PD; ++c) acc += B[rr * PD + c] * vj[c];
+        } else {
+#pragma unroll
+          for (int c = 0; c < PD; ++c) acc += B[c * PD + rr] * vj[c];
+        }
+      }
+      t = acc * v[row];
+    }
+    const double s = red_tree(t, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    return;
+  }
+  const int k = (int)blockIdx.x - nsb;
+  const long long base = (long long)k * RED_BLOCK * RED_PER_THREAD;
+  double vv[RED_PER_THREAD], wv[RED_PER_THREAD];
+#pragma unroll
+  for (int u = 0; u < RED_PER_THREAD; ++u) {  // every load of the chunk in flight before the first term
+    const long long i = base + (long long)u * RED_BLOCK + threadIdx.x;
+    vv[u] = i < n ? v[i] : 0.0;
+    wv[u] = i < n ? w[i] : 0.0;
+  }
+  double s0 = 0, s1 = 0;
+#pragma unroll
+  for (int u = 0; u < RED_PER_THREAD; ++u) {
+    s0 += wv[u] * vv[u];
+    s1 += vv[u] * vv[u];
+  }
+  s0 = red_tree(s0, sh);
+  s1 = red_tree(s1, sh);
+  if (threadIdx.x == 0) {
+    partial[nsb + k] = s0;
+    partial[nsb + nps + k] = s1;
+  }
+}
+
+// alpha = |b|^2 / (b_p^T Hpp b_p) (:101-102), |hsd|^2 = alpha^2 |b|^2 and |hsd| (:104-105; hsd = alpha b is not stored)
+__global__ void __launch_bounds__(RED_BLOCK) k_dl_alpha_final(const double* __restrict__ partial, int nsb, int nps,
+                                                              double* __restrict__ p) {
+  __shared__ double sh[RED_BLOCK];
+  const double auxb = red_final(partial, nsb, sh);
+  const double bsq = red_final(partial + nsb + nps, nps, sh);
+  if (threadIdx.x == 0) {
+    const double alpha = bsq / auxb;
+    const double hsd_sq = alpha * alpha * bsq;
+    p[launch::DL_ALPHA] = alpha;
+    p[launch::DL_BSQ] = bsq;
+    p[launch::DL_AUXB] = auxb;
+    p[launch::DL_HSD_SQ] = hsd_sq;
+    p[launch::DL_HSD_NORM] = sqrt(hsd_sq);
+  }
+}
+
+// after the Gauss-Newton solve, once per iteration (independent of delta): partials of x . x (:147),
+// c = hsd . (x - hsd) (:161-162) and |x - hsd|^2 (:163), each formed element by element from the vectors as the
+// reference forms them (hsd_i = alpha b_i), at partial[k], partial[nps + k], partial[2 nps + k]
+__global__ void __launch_bounds__(RED_BLOCK) k_dl_post_partial(long long n, int nps, const double* __restrict__ x,
+                                                               const double* __restrict__ b,
+                                                               const double* __restrict__ p,
+                                                               double* __restrict__ partial) {
+  __shared__ double sh[RED_BLOCK];
+  const double alpha = p[launch::DL_ALPHA];
+  const long long base = (long long)blockIdx.x * RED_BLOCK * RED_PER_THREAD;
+  double xv[RED_PER_THREAD], bv[RED_PER_THREAD];
+#pragma unroll
+  for (int u = 0; u < RED_PER_THREAD; ++u) {
+    const long long i = base + (long long)u * RED_BLOCK + threadIdx.x;
+    xv[u] = i < n ? x[i] : 0.0;
+    bv[u] = i < n ? b[i] : 0.0;
+  }
+  double s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+  for (int u = 0; u < RED_PER_THREAD; ++u) {
+    const double hsd = alpha * bv[u], d = xv[u] - hsd;
+    s0 += xv[u] * xv[u];
+    s1 += hsd * d;
+    s2 += d * d;
+  }
+  s0 = red_tree(s0, sh);
+  s1 = red_tree(s1, sh);
+  s2 = red_tree(s2, sh);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = s0;
+    partial[nps + blockIdx.x] = s1;
+    partial[2 * nps + blockIdx.x] = s2;
+  }
+}
+__global__ void __launch_bounds__(RED_BLOCK) k_dl_post_final(const double* __restrict__ partial, int nps,
+                                                             double* __restrict__ p) {
+  __shared__ double sh[RED_BLOCK];
+  const double xx = red_final(partial, nps, sh);
+  const double c = red_final(partial + nps, nps, sh);
+  const double bma = red_final(partial + 2 * nps, nps, sh);
+  if (threadIdx.x == 0) {
+    p[launch::DL_HGN_SQ] = xx;
+    p[launch::DL_HGN_NORM] = sqrt(xx);
+    p[launch::DL_C] = c;
+    p[launch::DL_BMA_SQ] = bma;
+  }
+}
+
+// one trial's step (:153-175): every workgroup takes the step choice itself from the scalar block (dogleg_blend, the
+// function the host exports) and writes its part of hdl = coef0 hsd + coef1 hgn; x (hgn) stays as it is for later trials
+__global__ void __launch_bounds__(256) k_dl_blend(long long n, const double* __restrict__ x, const double* __restrict__ b,
+                                                  double* __restrict__ p, double delta, double* __restrict__ hdl) {
+  double coef[2];
+  const double alpha = p[launch::DL_ALPHA];
+  const int step = dogleg_blend(p[launch::DL_HGN_NORM], p[launch::DL_HSD_NORM], p[launch::DL_HSD_SQ], p[launch::DL_C],
+                                p[launch::DL_BMA_SQ], delta, coef);
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) hdl[i] = coef[0] * (alpha * b[i]) + coef[1] * x[i];
+  if (i == 0) {  // [DL_COEF0, DL_STEP] are read by no workgroup of this launch
+    p[launch::DL_COEF0] = coef[0];
+    p[launch::DL_COEF1] = coef[1];
+    p[launch::DL_STEP] = (double)step;
+  }
+}
+
+// the finals of k_dl_symv_dots (v = hdl, w = b) and the trial's decision (:180-203) in the manner of k_lm_decide:
+// linearGain = -hdl_p^T Hpp hdl_p + 2 b . hdl with the 1e-12 clamp, rho, accepted, the next delta; the result block
+// p[16, 32) is the trial's one readback
+__global__ void __launch_bounds__(RED_BLOCK) k_dl_decide(const double* __restrict__ partial, int nsb, int nps,
+                                                         double* __restrict__ p, const double* __restrict__ chi,
+                                                         double current_chi, double delta) {
+  __shared__ double sh[RED_BLOCK];
+  const double auxhdl = red_final(partial, nsb, sh);
+  const double bhdl = red_final(partial + nsb, nps, sh);
+  const double hdlsq = red_final(partial + nsb + nps, nps, sh);
+  if (threadIdx.x == 0) {
+    const double new_chi = *chi;
+    double gain = -1 * auxhdl + 2 * bhdl;
+    if (fabs(gain) < 1e-12) gain = 1e-12;
+    const double rho = (current_chi - new_chi) / gain;
+    const double hdl_norm = sqrt(hdlsq);
+    double* o = p + launch::DL_OUT;
+    o[launch::DLO_CHI] = new_chi;
+    o[launch::DLO_GAIN] = gain;
+    o[launch::DLO_RHO] = rho;
+    o[launch::DLO_ACCEPT] = rho > 0 ? 1.0 : 0.0;
+    o[launch::DLO_DELTA] = dogleg_next_delta(delta, rho, hdl_norm);
+    o[launch::DLO_HDL_NORM] = hdl_norm;
+    o[launch::DLO_STEP] = p[launch::DL_STEP];
+    o[launch::DLO_AUXHDL] = auxhdl;
+    o[launch::DLO_BHDL] = bhdl;
+    o[launch::DLO_ALPHA] = p[launch::DL_ALPHA];
+    o[launch::DLO_HSD_NORM] = p[launch::DL_HSD_NORM];
+    o[launch::DLO_HGN_NORM] = p[launch::DL_HGN_NORM];
+    o[launch::DLO_C] = p[launch::DL_C];
+    o[launch::DLO_BMA_SQ] = p[launch::DL_BMA_SQ];
+    o[launch::DLO_COEF0] = p[launch::DL_COEF0];
+    o[launch::DLO_COEF1] = p[launch::DL_COEF1];
+  }
+}
+
 // ------------------------------------------------------------------------------ launchers
 namespace launch {
 
@@ -1916,6 +2120,47 @@ void block_symv(int pd, int n, const int* rptr, const int2* ent, const int* diag
 void scale_terms(long long n, const double* x, const double* b, const double* lam, double* out, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_scale_terms, grid_for(n, 256), 256, 0, s, n, x, b, lam, out);
+  KERNEL_CHECK();
+}
+
+// ---- Powell dogleg
+static int dl_nsb(int npose) { return (int)grid_for(npose, RED_BLOCK); }
+size_t dl_partials(int npose, long long n) { return (size_t)dl_nsb(npose) + 3 * sum_partials(n); }
+static void dl_symv_dots(const DoglegSymv& H, long long n, const double* v, const double* w, double* partial,
+                         hipStream_t s) {
+  const int nsb = dl_nsb(H.npose), nps = (int)sum_partials(n);
+  if (H.pd == 6)
+    hipLaunchKernelGGL(k_dl_symv_dots<6>, nsb + nps, RED_BLOCK, 0, s, H.npose, n, nsb, nps, H.rptr, H.ent, H.diag,
+                       H.vals, v, w, partial);
+  else if (H.pd == 3)
+    hipLaunchKernelGGL(k_dl_symv_dots<3>, nsb + nps, RED_BLOCK, 0, s, H.npose, n, nsb, nps, H.rptr, H.ent, H.diag,
+                       H.vals, v, w, partial);
+  else throw std::runtime_error("dogleg: block dimension must be 3 or 6");
+  KERNEL_CHECK();
+}
+void dl_alpha(const DoglegSymv& H, long long n, const double* b, double* partial, double* p, hipStream_t s) {
+  dl_symv_dots(H, n, b, b, partial, s);
+  hipLaunchKernelGGL(k_dl_alpha_final, 1, RED_BLOCK, 0, s, partial, dl_nsb(H.npose), (int)sum_partials(n), p);
+  KERNEL_CHECK();
+}
+void dl_post(long long n, const double* x, const double* b, double* partial, double* p, hipStream_t s) {
+  const int nps = (int)sum_partials(n);
+  hipLaunchKernelGGL(k_dl_post_partial, nps, RED_BLOCK, 0, s, n, nps, x, b, p, partial);
+  hipLaunchKernelGGL(k_dl_post_final, 1, RED_BLOCK, 0, s, partial, nps, p);
+  KERNEL_CHECK();
+}
+void dl_blend(long long n, const double* x, const double* b, double* p, double delta, double* hdl, hipStream_t s) {
+  hipLaunchKernelGGL(k_dl_blend, grid_for((size_t)n, 256), 256, 0, s, n, x, b, p, delta, hdl);
+  KERNEL_CHECK();
+}
+void dl_gain_partials(const DoglegSymv& H, long long n, const double* hdl, const double* b, double* partial,
+                      hipStream_t s) {
+  dl_symv_dots(H, n, hdl, b, partial, s);
+}
+void dl_decide(const DoglegSymv& H, long long n, const double* partial, double* p, const double* chi,
+               double current_chi, double delta, hipStream_t s) {
+  hipLaunchKernelGGL(k_dl_decide, 1, RED_BLOCK, 0, s, partial, dl_nsb(H.npose), (int)sum_partials(n), p, chi,
+                     current_chi, delta);
   KERNEL_CHECK();
 }
 

@@ -174,6 +174,40 @@ void lm_decide(double* p, double current_chi, double ni, bool rank0, hipStream_t
 // per-row (y - b)^2 -> r2 and b^2 -> b2 (y may be null)
 void block_symv(int pd, int n, const int* rptr, const int2* ent, const int* diag, const double* vals, const double* lam,
                 const double* x, double* y, const double* b, double* r2, double* b2, hipStream_t s);
+// ---- Powell dogleg (OptimizationAlgorithmDogleg, Engine::dl_solve) ----
+// the dogleg scalar block (32 doubles): what an iteration's passes leave for its trials ...
+enum DoglegScalar {
+  DL_ALPHA = 0, DL_BSQ, DL_AUXB, DL_HSD_SQ, DL_HSD_NORM,  // dl_alpha: alpha, |b|^2, b_p^T Hpp b_p, |hsd|^2, |hsd|
+  DL_HGN_SQ, DL_HGN_NORM, DL_C, DL_BMA_SQ,                // dl_post: |x|^2, |x|, hsd . (x - hsd), |x - hsd|^2
+  DL_COEF0, DL_COEF1, DL_STEP,                            // dl_blend: hdl = coef0 hsd + coef1 x, the step type
+  DL_OUT = 16                                             // dl_decide: the 16 scalars of the trial's readback
+};
+// ... and the readback, relative to DL_OUT
+enum DoglegOut {
+  DLO_CHI = 0, DLO_GAIN, DLO_RHO, DLO_ACCEPT, DLO_DELTA, DLO_HDL_NORM, DLO_STEP, DLO_AUXHDL, DLO_BHDL, DLO_ALPHA,
+  DLO_HSD_NORM, DLO_HGN_NORM, DLO_C, DLO_BMA_SQ, DLO_COEF0, DLO_COEF1
+};
+// the upper-block CSR of BlockSymv (Hpp), its values, and the partial-sum scratch of dl_partials(npose, n) doubles
+struct DoglegSymv {
+  int pd, npose;
+  const int* rptr;
+  const int2* ent;
+  const int* diag;
+  const double* vals;
+};
+size_t dl_partials(int npose, long long n);
+// alpha pass: Hpp b_p fused with the partials of (Hpp b_p) . b_p and b . b, then alpha, |hsd|^2, |hsd| into p
+void dl_alpha(const DoglegSymv& H, long long n, const double* b, double* partial, double* p, hipStream_t s);
+// after the Gauss-Newton solve: |x|^2, hsd . (x - hsd), |x - hsd|^2 (hsd = alpha b) into p
+void dl_post(long long n, const double* x, const double* b, double* partial, double* p, hipStream_t s);
+// one trial: hdl = coef0 alpha b + coef1 x for the trust region delta (step choice on the device, from p) ...
+void dl_blend(long long n, const double* x, const double* b, double* p, double delta, double* hdl, hipStream_t s);
+// ... Hpp hdl_p fused with the partials of (Hpp hdl_p) . hdl_p, b . hdl, hdl . hdl ...
+void dl_gain_partials(const DoglegSymv& H, long long n, const double* hdl, const double* b, double* partial,
+                      hipStream_t s);
+// ... and, the trial state's chi2 at *chi: the finals, linearGain, rho, accept and the next delta into p[DL_OUT ...)
+void dl_decide(const DoglegSymv& H, long long n, const double* partial, double* p, const double* chi,
+               double current_chi, double delta, hipStream_t s);
 struct CopyList {  // up to 4 device-to-device copies of doubles in one launch (vertex push/pop)
   const double* src[4];
   double* dst[4];

@@ -12,6 +12,7 @@
  *   OptimizableGraph::load / save (core/optimizable_graph.cpp:397-679) .. g2ohip_load_g2o / g2ohip_save_g2o
  *   OptimizationAlgorithmFactory::construct (core/optimization_algorithm_factory.cpp:84-93)
  *        .. g2ohip_set_algorithm("lm_hip_fix6_3" | "lm_hip_fix3_3" | "lm_hip_fix6_6" | "lm_hip_var" | "gn_hip_*"
+ *           | "dl_hip_*" (Powell's dogleg, core/optimization_algorithm_dogleg.cpp:57-208; the same suffixes)
  *           | "{lm,gn}_pcg" | "{lm,gn}_pcg6_3" (block-Jacobi PCG, solver_pcg.cpp:91-98)
  *           | "lm_pcg6_3_eigen" (fork JacobiSolver_6_3 + LinearSolverPCGEigen CGLS, solver_eigen.cpp:80,126))
  *   G2OBatchStatistics (core/batch_stats.h:42-72) .. g2ohip_batch_stats
@@ -228,8 +229,21 @@ long long g2ohip_host_payload_len(g2ohip_graph* g, int edge_type);
 
 /* OptimizationAlgorithmFactory::construct by name; default "lm_hip_var". "lm_pcg6_3_eigen" (matrix-free CGLS on the
  * Jacobian of BA edges) does not take unary edges (priors, the pose-only projections), the slam3d landmark edges or
- * G2OHIP_E_SE3_EXPMAP: building the structure of such a graph under it returns G2OHIP_ERR_UNSUPPORTED. */
+ * G2OHIP_E_SE3_EXPMAP: building the structure of such a graph under it returns G2OHIP_ERR_UNSUPPORTED.
+ * "dl_hip_{var,fix6_3,fix3_2,fix3_3,fix6_6}" is OptimizationAlgorithmDogleg over the Cholesky solver ("dl_pcg*" is
+ * unknown: the reference registers no dogleg over PCG, the step needs an exact Gauss-Newton solve). Under dl_* the
+ * max_trials_after_failure and user_lambda_init of g2ohip_config are ignored (g2ohip_set_dogleg_params),
+ * g2ohip_batch_stats.levenbergIterations stays 0 and .lambda is the damping of the not-PD branch while it is in use,
+ * else 0. A sharded graph (g2ohip_set_comm*, nranks > 1) under dl_* returns G2OHIP_ERR_UNSUPPORTED from the structure
+ * build: the step multiplies by Hpp, whose diagonal blocks are partial on a landmark shard. */
 int g2ohip_set_algorithm(g2ohip_graph* g, const char* name);
+/* OptimizationAlgorithmDogleg properties (optimization_algorithm_dogleg.cpp:45-48); a value <= 0 keeps the default:
+ * initialDelta 1e4, maxTrialsAfterFailure 100, initialLambda 1e-7, lambdaFactor 10 */
+int g2ohip_set_dogleg_params(g2ohip_graph* g, double initial_delta, int max_trials_after_failure,
+                             double initial_lambda, double lambda_factor);
+/* state after the last dogleg iteration: out[0] delta (trustRegion()), out[1] lastStep (1 SD, 2 GN, 3 DL, 0 undefined;
+ * the reference's enum order), out[2] lastNumTries, out[3] currentLambda, out[4] wasPDInAllIterations; n >= 5 */
+int g2ohip_dogleg_state(g2ohip_graph* g, double* out, int n);
 /* SparseOptimizer::initializeOptimization(0): active edges/vertices, index mapping */
 int g2ohip_initialize(g2ohip_graph* g);
 /* SparseOptimizer::updateInitialization(vset, eset) + BlockSolver::updateStructure (sparse_optimizer.cpp:465-502,
@@ -435,6 +449,14 @@ int g2ohip_measure_peaks(int device, double* out, int n);
 /* The accepted LM trial's lambda factor max(1/3, min(2/3, 1 - (2 rho - 1)^3)) exactly as the device decision and the
  * host loop compute it (optimization_algorithm_levenberg.cpp:127-136; the cube rounded once, like glibc's pow). */
 double g2ohip_lm_scale_factor(double rho);
+/* The two scalar decisions of a dogleg trial exactly as the device kernels take them (one shared function each).
+ * step choice and blend of :153-175: hdl = coef[0] * hsd + coef[1] * hgn. Inputs: |hgn|, |hsd|, hsd.hsd,
+ * c = hsd.(hgn - hsd), |hgn - hsd|^2, delta. Returns the step type (1 SD, 2 GN, 3 DL). Both beta branches
+ * (c <= 0 and c > 0) exactly as written in the reference. */
+int g2ohip_dogleg_blend(double hgn_norm, double hsd_norm, double hsd_sq, double c, double bma_sq, double delta,
+                        double coef[2]);
+/* trust-region update of :199-203 */
+double g2ohip_dogleg_next_delta(double delta, double rho, double hdl_norm);
 const char* g2ohip_version(void);
 
 #ifdef __cplusplus
