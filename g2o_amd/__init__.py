@@ -102,7 +102,7 @@ EXPORTS = [
     "g2ohip_version", "g2ohip_host_payload_len", "g2ohip_solver_save_hessian", "g2ohip_solver_set_write_debug",
     "g2ohip_comm_local_reduce_host", "g2ohip_runtime_info", "g2ohip_device_synchronize", "g2ohip_lm_scale_factor",
     "g2ohip_measure_peaks", "g2ohip_set_dogleg_params", "g2ohip_dogleg_state", "g2ohip_dogleg_blend",
-    "g2ohip_dogleg_next_delta",
+    "g2ohip_dogleg_next_delta", "g2ohip_structure_only_calc",
 ]
 
 
@@ -192,6 +192,7 @@ def lib() -> C.CDLL:
         "g2ohip_dogleg_state": ([P, P, I], I),
         "g2ohip_dogleg_blend": ([D, D, D, D, D, D, P], I),
         "g2ohip_dogleg_next_delta": ([D, D, D], D),
+        "g2ohip_structure_only_calc": ([P, I, P, I, I, P], I),
         "g2ohip_host_payload_len": ([P, I], LL),
         "g2ohip_solver_save_hessian": ([P, C.c_char_p], I),
         "g2ohip_solver_set_write_debug": ([P, I], I),
@@ -463,6 +464,27 @@ class SparseOptimizer:
         out = np.zeros(5)
         _check(lib().g2ohip_dogleg_state(self.h, _p(out), 5), "dogleg_state")
         return dict(delta=float(out[0]), step=int(out[1]), tries=int(out[2]), lam=float(out[3]), was_pd=bool(out[4]))
+
+    STRUCTURE_ONLY_COUNTS = ("accepted", "rejected", "gradient_stops", "exhausted", "fixed_skipped")
+
+    def structure_only(self, ids=None, iterations: int = 1, max_trials: int = 10) -> dict:
+        """StructureOnlySolver::calc(points, iterations, max_trials) (structure_only_solver.h:72-212) on the device:
+        every marginalised landmark (``ids`` None) or the given landmark ids refined with all other vertices held
+        fixed, in one kernel launch. ba_demo's sequence is ``structure_only(iterations=10)`` and then
+        ``set_algorithm("lm_hip_fix6_3")`` and ``optimize`` on the same handle. Returns the five counts."""
+        counts = np.zeros(5, dtype=np.int64)
+        if ids is None:
+            n, idp = 0, None
+        else:
+            ida = np.ascontiguousarray(ids, dtype=np.int32)
+            n, idp = int(ida.size), _p(ida)
+        args = (self.h, n, idp, int(iterations), int(max_trials), _p(counts))
+        r = lib().g2ohip_structure_only_calc(*args)
+        if r == -2:  # G2OHIP_ERR_STATE: initializeOptimization first, as optimize() does by itself
+            self.initialize_optimization()
+            r = lib().g2ohip_structure_only_calc(*args)
+        _check(r, "structure_only")
+        return dict(zip(self.STRUCTURE_ONLY_COUNTS, (int(c) for c in counts)))
 
     def initialize_optimization(self):
         _check(lib().g2ohip_initialize(self.h), "initializeOptimization")

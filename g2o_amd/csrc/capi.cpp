@@ -34,6 +34,8 @@ int guarded(F&& f) {
 }
 // 1 known, 0 unknown, -1 a reference name this backend does not build (with g_err set)
 int algorithm_known(const std::string& n) {
+  // StructureOnlySolver<3> / <2> (solvers/structure_only/structure_only.cpp:64-65)
+  if (n == "structure_only_3" || n == "structure_only_2") return 1;
   // {gn,lm}_hip_{var,fix6_3,fix3_2,fix3_3,fix6_6} (cf. solver_csparse.cpp:51-84 name parsing)
   if (n.size() < 6) return 0;
   const std::string m = n.substr(0, 3), rest = n.substr(3);
@@ -175,8 +177,9 @@ int g2ohip_set_algorithm(g2ohip_graph* g, const char* name) {
   }
   g->e->algorithm = name;
   const std::string m = std::string(name).substr(0, 3);
-  g->e->algo = m == "lm_" ? g2ohip::Engine::Algo::Levenberg
+  g->e->algo = m == "lm_"   ? g2ohip::Engine::Algo::Levenberg
                : m == "dl_" ? g2ohip::Engine::Algo::Dogleg
+               : m == "str" ? g2ohip::Engine::Algo::StructureOnly
                             : g2ohip::Engine::Algo::GaussNewton;
   return G2OHIP_OK;
 }
@@ -189,6 +192,13 @@ int g2ohip_dogleg_state(g2ohip_graph* g, double* out, int n) {
   if (!g || !out || n < 5) return G2OHIP_ERR_ARG;
   g->e->dogleg_state(out);
   return G2OHIP_OK;
+}
+int g2ohip_structure_only_calc(g2ohip_graph* g, int n, const int* ids, int num_iters, int num_max_trials,
+                               long long* counts) {
+  if (!g) return G2OHIP_ERR_ARG;
+  const int r = guarded([&] { return g->e->structure_only_calc(n, ids, num_iters, num_max_trials, counts); });
+  if (r == G2OHIP_ERR_STATE) g_err = "structure_only_calc: initializeOptimization first";
+  return r;
 }
 int g2ohip_initialize(g2ohip_graph* g) {
   if (!g) return G2OHIP_ERR_ARG;

@@ -1823,7 +1823,7 @@ void Engine::sync_host_state() {
 }
 
 int Engine::get_estimates(int type, double* out, int* ids) {
-  if (type < 1 || type > 4) return G2OHIP_ERR_ARG;
+  if (type < 1 || type >= NVT) return G2OHIP_ERR_ARG;  // G2OHIP_V_XY (5) included: structure_only_2's landmarks
   sync_host_state();
   const int ed = vertex_est_dim(type), sd = vertex_state_stride(type);
   const auto& lst = hg.by_type[type];
@@ -1835,7 +1835,7 @@ int Engine::get_estimates(int type, double* out, int* ids) {
 }
 
 int Engine::set_estimates(int type, const double* est) {
-  if (type < 1 || type > 4) return G2OHIP_ERR_ARG;
+  if (type < 1 || type >= NVT) return G2OHIP_ERR_ARG;  // G2OHIP_V_XY (5) included: structure_only_2's landmarks
   sync_host_state();
   const int ed = vertex_est_dim(type), sd = vertex_state_stride(type);
   for (size_t k = 0; k < hg.by_type[type].size(); ++k) set_state_from_est(type, est + k * ed, hg.st[type].data() + k * sd);
@@ -1955,6 +1955,7 @@ int Engine::initialize() {  // sparse_optimizer.cpp:201-279 + buildIndexMapping 
       const int a = hidx[es.ev0[k]], b = hidx[es.ev1[k]];
       if (a >= num_poses && b >= num_poses) return G2OHIP_ERR_UNSUPPORTED;
     }
+  so_check_dim();  // structure_only_2 / _3 against the marginalised vertices' dimension
   initialized = true;
   structure_built = false;
   edges_ready = false;
@@ -2356,6 +2357,7 @@ void Engine::setup_edges_device() {
   for (auto& g : groups) ptot += (long long)launch::sum_partials(std::max(g.ne, 1));
   dpartial.resize(std::max<size_t>(launch::sum_partials(maxp) + (size_t)ptot + 64, 128));  // chi2 + scale partials
   edges_ready = true;
+  ++edges_ver;
   ++state_ver;  // the edge set (and so chi2) changed
 }
 
@@ -4114,7 +4116,8 @@ int Engine::optimize_step(const g2ohip_config* cfgp, int i, g2ohip_batch_stats* 
     if (r) return r;
   }
   if (ivmap.empty()) return -1;
-  if (i == 0) structure_built = false;  // algorithm init: symbolic rebuilt on iteration 0 (linear_solver init())
+  const bool structure_only = algo == Algo::StructureOnly;  // no linear solver under it: nothing to rebuild
+  if (i == 0 && !structure_only) structure_built = false;  // algorithm init: symbolic rebuilt on iteration 0 (linear_solver init())
   if (st) {
     std::memset(st, 0, sizeof *st);
     st->iteration = i;
@@ -4125,7 +4128,8 @@ int Engine::optimize_step(const g2ohip_config* cfgp, int i, g2ohip_batch_stats* 
   const bool levenberg = algo == Algo::Levenberg, dogleg = algo == Algo::Dogleg;
   // (cfg's max_trials_after_failure and user_lambda_init are OptimizationAlgorithmLevenberg's: dl_* has its own,
   // set_dogleg_params)
-  const int result = levenberg ? lm_solve(i, cfg, st) : dogleg ? dl_solve(i, st) : gn_solve(i, st);
+  const int result = structure_only ? so_solve() : levenberg ? lm_solve(i, cfg, st) : dogleg ? dl_solve(i, st) : gn_solve(i, st);
+  if (result < 0) return result;
   if (st || cfg.verbose) {
     const double c = chi2_sync();
     if (st) {
@@ -4482,6 +4486,22 @@ double Engine::kernel_bytes(const std::string& name) const {
         const int np = g.family == FAM_SE3_XYZ ? 12 : 16;
         by += g.ne * ((3 + ((g.ue & 1) ? 0 : 6) + ((g.ue & 2) ? 0 : np)) * 8.0 + 8 + (27.0 + 9.0) * 8 + pb);
       }
+    return by;
+  }
+  if (name == "structure_only") {
+    // one pass over every landmark's edge list (calc makes 1 + iterations + trials of them, the later ones from cache
+    // where the lists fit): the (group, edge) entry, the other vertex's index and, per edge, measurement, information
+    // and parameter records (one shared record when uniform); every camera / pose once; the point read and written
+    if (so_.key != edges_ver) return 0;  // no list for the current edge groups (no calc since the last edge setup)
+    double by = (double)so_.nlm * (4 + 4 + 1 + 2.0 * so_.ld * 8);
+    for (int gi : so_.group_of) {
+      const EGroup& g = groups[gi];
+      const int np = g.family == FAM_BA ? 4 : g.family == FAM_BA_STEREO ? 5 : g.family == FAM_SE3_XYZ ? 12
+                     : is_slam3d_family(g.family) ? 16 : 0;
+      by += g.ne * (8.0 + (g.vtB ? 4.0 : 0.0) + g.D * 8.0 + ((g.ue & 1) ? 0.0 : g.D * (g.D + 1) / 2 * 8.0) +
+                    ((g.ue & 2) ? 0.0 : np * 8.0));
+    }
+    for (int t : {G2OHIP_V_SE3_EXPMAP, G2OHIP_V_SE3_QUAT, G2OHIP_V_SE2}) by += dstate[t].bytes();
     return by;
   }
   if (name == "backsub") return local_lm.size() * (3 * 8.0 * 2 + 72) + npl * (pb + 4) + size_poses * 8.0;

@@ -16,6 +16,7 @@
 #include "kernels.hpp"
 #include "cgls.hpp"
 #include "pcg.hpp"
+#include "structure_only.hpp"
 #include "symbolic.hpp"
 
 namespace g2ohip {
@@ -239,13 +240,18 @@ class Engine {
   // G2OBatchStatistics timers: 0 none, 1 timeLinearSolution only (2 events per trial), 2 every stage
   int stats_level = 2;
   // the optimization algorithm over the BlockSolver: OptimizationAlgorithmLevenberg (lm_*), ...GaussNewton (gn_*),
-  // ...Dogleg (dl_*)
-  enum class Algo { GaussNewton, Levenberg, Dogleg };
+  // ...Dogleg (dl_*), StructureOnlySolver<PointDoF> (structure_only_2 / structure_only_3: no BlockSolver under it)
+  enum class Algo { GaussNewton, Levenberg, Dogleg, StructureOnly };
   Algo algo = Algo::Levenberg;
   // OptimizationAlgorithmDogleg properties (optimization_algorithm_dogleg.cpp:45-48); a value <= 0: the default
   int set_dogleg_params(double initial_delta, int max_trials, double initial_lambda, double lambda_factor);
   // [delta, lastStep, lastNumTries, currentLambda, wasPDInAllIterations] after the last dogleg iteration
   void dogleg_state(double* out) const;
+
+  // StructureOnlySolver::calc (structure_only_solver.h:72-212) in one launch: ids == nullptr every marginalised active
+  // vertex (init(), :214-225), else n landmark ids; counts (optional): accepted steps, rejected trials, points stopped by
+  // the gradient test, by exhausted trials, fixed points skipped
+  int structure_only_calc(int n, const int* ids, int num_iters, int num_max_trials, long long* counts);
 
   // ---- graph ops ----
   int add_vertices(int type, int n, const int* ids, const double* est, const int* fixed, const int* marg);
@@ -372,6 +378,7 @@ class Engine {
   std::vector<std::vector<DevBuf<double>>> stack_;  // per push level: per type (buffers reused)
   int stack_depth_ = 0;
   bool edges_ready = false;
+  unsigned long long edges_ver = 0;  // bumped by every setup_edges_device (the groups and their device arrays)
   hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};  // schur start, factor start, factor end, solve end
   bool ev_valid_ = false;
   DevBuf<int> d_xoff[NVT];         // per type local -> x offset or -1
@@ -502,6 +509,24 @@ class Engine {
   int lm_solve(int iteration, const g2ohip_config& cfg, g2ohip_batch_stats* st);
   int gn_solve(int iteration, g2ohip_batch_stats* st);
   int dl_solve(int iteration, g2ohip_batch_stats* st);
+  int so_solve();  // StructureOnlySolver::solve (:65-70): calc(_points, 1)
+  // structure-only: the marginalised active vertices (id order) and their (group, edge) lists, built once per edge
+  // setup (key: edges_ver)
+  struct SoList {
+    unsigned long long key = 0;
+    int nlm = 0, ld = 0, vt = 0, single_family = -1;
+    std::string refuse;               // why calc is refused on this graph (a host-Jacobian edge on a landmark), or empty
+    std::vector<int> lm_of_vertex;    // vertex index -> landmark, -1
+    std::vector<int> group_of;        // per SoGroup its index in `groups`
+    DevBuf<launch::SoGroup> groups;
+    DevBuf<int> ptr, local, sel;
+    DevBuf<int2> ent;
+    DevBuf<unsigned char> fixed;
+    DevBuf<long long> part;
+    long long nent = 0;
+  } so_;
+  void so_build_list();
+  void so_check_dim() const;  // throws G2OHIP_ERR_UNSUPPORTED: the name's PointDoF against the marginalised vertices
   // dogleg state (optimization_algorithm_dogleg.h): properties, trust region, damping of the not-PD branch
   double dl_user_delta = 1e4, dl_initial_lambda = 1e-7, dl_lambda_factor = 10.0;
   int dl_max_trials = 100;

@@ -13,6 +13,8 @@
  *   OptimizationAlgorithmFactory::construct (core/optimization_algorithm_factory.cpp:84-93)
  *        .. g2ohip_set_algorithm("lm_hip_fix6_3" | "lm_hip_fix3_3" | "lm_hip_fix6_6" | "lm_hip_var" | "gn_hip_*"
  *           | "dl_hip_*" (Powell's dogleg, core/optimization_algorithm_dogleg.cpp:57-208; the same suffixes)
+ *           | "structure_only_3" | "structure_only_2" (StructureOnlySolver<PointDoF>, solvers/structure_only/
+ *             structure_only.cpp:64-65, structure_only_solver.h:60-229; g2ohip_structure_only_calc is its calc())
  *           | "{lm,gn}_pcg" | "{lm,gn}_pcg6_3" (block-Jacobi PCG, solver_pcg.cpp:91-98)
  *           | "lm_pcg6_3_eigen" (fork JacobiSolver_6_3 + LinearSolverPCGEigen CGLS, solver_eigen.cpp:80,126))
  *   G2OBatchStatistics (core/batch_stats.h:42-72) .. g2ohip_batch_stats
@@ -244,6 +246,30 @@ int g2ohip_set_dogleg_params(g2ohip_graph* g, double initial_delta, int max_tria
 /* state after the last dogleg iteration: out[0] delta (trustRegion()), out[1] lastStep (1 SD, 2 GN, 3 DL, 0 undefined;
  * the reference's enum order), out[2] lastNumTries, out[3] currentLambda, out[4] wasPDInAllIterations; n >= 5 */
 int g2ohip_dogleg_state(g2ohip_graph* g, double* out, int n);
+/* StructureOnlySolver<PointDoF>::calc(points, num_iters, num_max_trials) (structure_only_solver.h:72-212), as ba_demo
+ * and sba_demo call it before the joint optimisation: with every other vertex held fixed, each landmark runs its own
+ * damped Gauss-Newton loop (mu = 0.01 and nu = 2 fresh per point and per call, :86-87; gradient stop |b| < 0.001, :148;
+ * accept on chi2 - new_chi2 > 0 with a finite new_chi2, mu *= 1/3, :179-195; else mu *= nu, nu *= 2 and the point stops
+ * after num_max_trials failures in a row, :197-203; a non-finite trial chi2 is a rejected trial). One kernel launch runs
+ * all iterations and trials of every point. Callable after g2ohip_initialize under any algorithm.
+ * ids == NULL: every marginalised active vertex (init(), :214-225; none: nothing is done, G2OHIP_OK), n is ignored.
+ * Otherwise n landmark ids; an unknown id, one that is no marginalised active vertex or one given twice returns
+ * G2OHIP_ERR_ARG and changes nothing. num_iters < 0 or num_max_trials < 1: G2OHIP_ERR_ARG. All edges of the landmark
+ * count (v->edges(), :82: an edge to a fixed camera included): EdgeSE3ProjectXYZ, EdgeStereoSE3ProjectXYZ, the three
+ * slam3d landmark edges, EdgeSE2PointXY, EdgeXYZPrior and EdgeXYPrior in any mix, each under its type's robust kernel.
+ * counts (may be NULL) receives the totals over the points: [0] accepted steps, [1] rejected trials, [2] points stopped
+ * by the gradient test, [3] points stopped by exhausted trials, [4] fixed points skipped (:104); per-block partial
+ * counts summed in block order. Cameras, poses and fixed points are not written; the push / pop stack is not touched;
+ * the next chi2, buildSystem, optimize or stage sees the new landmarks. G2OHIP_ERR_UNSUPPORTED (text in
+ * g2ohip_last_error): a sharded graph (nranks > 1), a landmark that carries a host-Jacobian edge (G2OHIP_E_HOSTJ*),
+ * another edge type on a marginalised vertex.
+ * Under "structure_only_3" / "structure_only_2" g2ohip_optimize and g2ohip_optimize_step run calc(points, 1) per
+ * iteration (solve(), :65-70: mu restarts at 0.01 every iteration, a trajectory other than calc(points, n)'s), always
+ * answer OK (g2ohip_optimize returns the iteration count), fill stats.chi2 with the robust chi2 after the step and
+ * leave levenbergIterations 0. g2ohip_initialize (and the calls above) return G2OHIP_ERR_UNSUPPORTED when the
+ * marginalised vertices' dimension is not the name's (the reference asserts it, :81). */
+int g2ohip_structure_only_calc(g2ohip_graph* g, int n, const int* ids, int num_iters, int num_max_trials,
+                               long long* counts);
 /* SparseOptimizer::initializeOptimization(0): active edges/vertices, index mapping */
 int g2ohip_initialize(g2ohip_graph* g);
 /* SparseOptimizer::updateInitialization(vset, eset) + BlockSolver::updateStructure (sparse_optimizer.cpp:465-502,
