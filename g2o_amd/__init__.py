@@ -557,6 +557,23 @@ class SparseOptimizer:
         _check(lib().g2ohip_solver_get_b(self.h, _p(out)), "b")
         return out
 
+    def update(self, x=None):
+        """SparseOptimizer::update (sparse_optimizer.cpp:441-454): oplus of every free vertex with its part of x, a
+        host vector in the Hessian order (see x()); None applies the solver's own x."""
+        if x is not None:
+            x = np.ascontiguousarray(x, np.float64)
+            if x.size != self.vector_size():
+                raise ValueError(f"update: x has {x.size} entries, the solver's vector has {self.vector_size()}")
+        _check(lib().g2ohip_update(self.h, _p(x)), "update")
+
+    def push(self):
+        """SparseOptimizer::push: every vertex's estimate onto its stack."""
+        _check(lib().g2ohip_push(self.h), "push")
+
+    def pop(self):
+        """SparseOptimizer::pop: the estimates as the matching push() saved them."""
+        _check(lib().g2ohip_pop(self.h), "pop")
+
     def multiply_hessian(self, src) -> np.ndarray:
         """BlockSolverBase::multiplyHessian (block_solver.h:146): Hpp @ src (pose part)."""
         src = np.ascontiguousarray(src, np.float64)

@@ -69,8 +69,9 @@ def oplus(vtype, est, u):
         return np.array([est[0] + u[0], est[1] + u[1], _norm_theta(est[2] + u[2])])
     if vtype == synth.V_SE3_QUAT:  # vertex_se3.h:105-113: estimate * fromVectorMQT(u)
         R = _R(est[3:7])
-        w = np.sqrt(max(0.0, 1.0 - u[3:6] @ u[3:6]))
-        return np.concatenate([est[:3] + R @ u[:3], _quat(R @ _R(np.concatenate([u[3:6], [w]])))])
+        w2 = 1.0 - u[3:6] @ u[3:6]  # fromCompactQuaternion (isometry3d_mappings.cpp:85-92): identity when |dq|^2 > 1
+        inc = np.eye(3) if w2 < 0 else _R(np.concatenate([u[3:6], [np.sqrt(w2)]]))
+        return np.concatenate([est[:3] + R @ u[:3], _quat(R @ inc)])
     if vtype == synth.V_SE3_EXPMAP:  # types_six_dof_expmap.h:97-100: exp(u) * estimate
         return stereo_ref.oplus_cam(est, u)
     raise KeyError(vtype)
