@@ -103,7 +103,12 @@ EXPORTS = [
     "g2ohip_comm_local_reduce_host", "g2ohip_runtime_info", "g2ohip_device_synchronize", "g2ohip_lm_scale_factor",
     "g2ohip_measure_peaks", "g2ohip_set_dogleg_params", "g2ohip_dogleg_state", "g2ohip_dogleg_blend",
     "g2ohip_dogleg_next_delta", "g2ohip_structure_only_calc",
+    "g2ohip_set_edge_levels", "g2ohip_get_edge_levels", "g2ohip_initialize_level", "g2ohip_edge_chi2",
+    "g2ohip_classify_edges",
 ]
+
+# G2OHIP_LEVEL_KEEP: classify_edges leaves the level of the edges on that side as it is
+LEVEL_KEEP = -2147483648
 
 
 def build(arch: str = "gfx950") -> None:
@@ -143,6 +148,11 @@ def lib() -> C.CDLL:
         "g2ohip_minimal_state": ([P, P], I),
         "g2ohip_set_algorithm": ([P, C.c_char_p], I),
         "g2ohip_initialize": ([P], I),
+        "g2ohip_initialize_level": ([P, I], I),
+        "g2ohip_set_edge_levels": ([P, I, I, P, P], I),
+        "g2ohip_get_edge_levels": ([P, I, P, I], I),
+        "g2ohip_edge_chi2": ([P, I, P, P], I),
+        "g2ohip_classify_edges": ([P, I, D, I, I, I, P], I),
         "g2ohip_update_initialization": ([P], I),
         "g2ohip_chi2": ([P], D),
         "g2ohip_optimize": ([P, P, I, P], I),
@@ -486,8 +496,49 @@ class SparseOptimizer:
         _check(r, "structure_only")
         return dict(zip(self.STRUCTURE_ONLY_COUNTS, (int(c) for c in counts)))
 
-    def initialize_optimization(self):
-        _check(lib().g2ohip_initialize(self.h), "initializeOptimization")
+    def initialize_optimization(self, level: int = 0):
+        """SparseOptimizer::initializeOptimization(level): the edges on ``level`` (every edge when it is negative) and
+        the vertices they touch form the system; the handle remembers the level."""
+        _check(lib().g2ohip_initialize_level(self.h, int(level)), "initializeOptimization")
+
+    # ---- edge levels, per-edge chi2, outlier classification ----
+    LEVEL_KEEP = LEVEL_KEEP
+
+    def set_edge_levels(self, etype: int, levels, idx=None):
+        """Edge::setLevel for the edges of a type (insertion order): ``levels[k]`` for edge ``idx[k]``, or for edge k
+        when ``idx`` is None (then one level per edge of the type). Takes effect at the next
+        initialize_optimization."""
+        lv = np.ascontiguousarray(levels, np.int32)
+        ix = None if idx is None else np.ascontiguousarray(idx, np.int32)
+        if ix is not None and ix.size != lv.size:
+            raise ValueError(f"set_edge_levels: {ix.size} indices for {lv.size} levels")
+        _check(lib().g2ohip_set_edge_levels(self.h, etype, int(lv.size), _p(ix), _p(lv)), "set_edge_levels")
+
+    def edge_levels(self, etype: int) -> np.ndarray:
+        """Edge::level() of every edge of a type, in insertion order."""
+        n = _check(lib().g2ohip_get_edge_levels(self.h, etype, None, 0), "edge_levels")
+        out = np.zeros(n, np.int32)
+        _check(lib().g2ohip_get_edge_levels(self.h, etype, _p(out), n), "edge_levels")
+        return out
+
+    def edge_chi2(self, etype: int, depth: bool = False):
+        """Edge::chi2() (e^T Omega e, not robustified) of every edge of a type, active or not, at the device's
+        estimates; with ``depth`` also isDepthPositive() as a bool array: (chi2, depth_positive)."""
+        n = _check(lib().g2ohip_get_edge_levels(self.h, etype, None, 0), "edge_chi2")
+        chi = np.zeros(max(n, 1))
+        dp = np.zeros(max(n, 1), np.uint8) if depth else None
+        _check(lib().g2ohip_edge_chi2(self.h, etype, _p(chi), _p(dp)), "edge_chi2")
+        return (chi[:n], dp[:n].astype(bool)) if depth else chi[:n]
+
+    def classify_edges(self, etype: int, chi2_max: float, check_depth: bool = False, inlier_level: int = 0,
+                       outlier_level: int = 1) -> dict:
+        """One device pass over every edge of a type: bad = chi2 > chi2_max or (check_depth and not z > 0); the edge
+        moves to ``outlier_level`` when bad, else to ``inlier_level`` (LEVEL_KEEP: stays where it is). Returns the
+        counts ``over_chi2``, ``depth_failed`` and ``bad``."""
+        counts = np.zeros(3, np.int64)
+        _check(lib().g2ohip_classify_edges(self.h, etype, float(chi2_max), int(check_depth), int(inlier_level),
+                                           int(outlier_level), _p(counts)), "classify_edges")
+        return dict(over_chi2=int(counts[0]), depth_failed=int(counts[1]), bad=int(counts[2]))
 
     def update_initialization(self):
         """SparseOptimizer::updateInitialization (online mode, non-Schur): vertices / edges added since

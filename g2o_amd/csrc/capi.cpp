@@ -202,7 +202,33 @@ int g2ohip_structure_only_calc(g2ohip_graph* g, int n, const int* ids, int num_i
 }
 int g2ohip_initialize(g2ohip_graph* g) {
   if (!g) return G2OHIP_ERR_ARG;
-  return guarded([&] { return g->e->initialize(); });
+  return guarded([&] { return g->e->initialize_level(0); });
+}
+int g2ohip_initialize_level(g2ohip_graph* g, int level) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->initialize_level(level); });
+}
+int g2ohip_set_edge_levels(g2ohip_graph* g, int edge_type, int n, const int* idx, const int* levels) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->set_edge_levels(edge_type, n, idx, levels); });
+}
+int g2ohip_get_edge_levels(g2ohip_graph* g, int edge_type, int* out, int cap) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->get_edge_levels(edge_type, out, cap); });
+}
+int g2ohip_edge_chi2(g2ohip_graph* g, int edge_type, double* chi2, unsigned char* depth_positive) {
+  if (!g || !chi2) return G2OHIP_ERR_ARG;
+  const int r = guarded([&] { return g->e->edge_chi2(edge_type, chi2, depth_positive); });
+  if (r == G2OHIP_ERR_STATE) g_err = "edge_chi2: initializeOptimization first";
+  return r;
+}
+int g2ohip_classify_edges(g2ohip_graph* g, int edge_type, double chi2_max, int check_depth, int inlier_level,
+                          int outlier_level, long long counts[3]) {
+  if (!g) return G2OHIP_ERR_ARG;
+  const int r = guarded(
+      [&] { return g->e->classify_edges(edge_type, chi2_max, check_depth, inlier_level, outlier_level, counts); });
+  if (r == G2OHIP_ERR_STATE) g_err = "classify_edges: initializeOptimization first";
+  return r;
 }
 
 int g2ohip_update_initialization(g2ohip_graph* g) {

@@ -346,7 +346,8 @@ DI void load_info(const double* p, double* Om) {  // packed upper -> full row-ma
 struct FamilyBA {
   static constexpr int D = 2, DA = 3, DB = 6, MEAS = 2, INFO = 3;
   static constexpr int SA = 8 /*unused*/, S0 = 3, S1 = 8;  // state strides
-  DI static void error(const EdgeData& d, int e, double* err) {
+  // the error, and the point's z in the camera frame (isDepthPositive, types_six_dof_expmap.h:218-222)
+  DI static double depth(const EdgeData& d, int e, double* err) {
     const double* c = d.s1 + (size_t)d.v1[e] * 8;
     const double* p = d.s0 + (size_t)d.v0[e] * 3;
     double pc[3];
@@ -357,7 +358,9 @@ struct FamilyBA {
     const double* K = param_rec(d, e, 4);
     err[0] = d.meas[(size_t)e * 2 + 0] - (pc[0] / pc[2] * K[0] + K[2]);
     err[1] = d.meas[(size_t)e * 2 + 1] - (pc[1] / pc[2] * K[1] + K[3]);
+    return pc[2];
   }
+  DI static void error(const EdgeData& d, int e, double* err) { depth(d, e, err); }
   DI static void linearize(const EdgeData& d, int e, double* err, double* A, double* B) {
     double pc[3];
     linearize(d, e, err, A, B, pc);
@@ -436,12 +439,15 @@ struct FamilyStereo {
     err[1] = m1 - v;
     err[2] = m2 - ur;
   }
-  DI static void error(const EdgeData& d, int e, double* err) {
+  // the error, and the point's z in the camera frame (isDepthPositive, types_six_dof_expmap.h:279-283)
+  DI static double depth(const EdgeData& d, int e, double* err) {
     double q[4], pc[3];
     to_camera(d, d.v0[e], d.v1[e], q, pc);
     const double* m = d.meas + (size_t)e * 3;
     residual(param_rec(d, e, PAR), pc, m[0], m[1], m[2], err);
+    return pc[2];
   }
+  DI static void error(const EdgeData& d, int e, double* err) { depth(d, e, err); }
   DI static void linearize(const EdgeData& d, int e, double* err, double* A, double* B) {
     double pc[3];
     linearize(d, e, err, A, B, pc);
@@ -1104,12 +1110,15 @@ struct FamilyPoseOnly {
     err[0] = m[0] - (pc[0] / pc[2] * K[0] + K[2]);
     err[1] = m[1] - (pc[1] / pc[2] * K[1] + K[3]);
   }
-  DI static void error(const EdgeData& d, int e, double* err) {
+  // the error, and the point's z in the camera frame (isDepthPositive, types_six_dof_expmap.h:248-251)
+  DI static double depth(const EdgeData& d, int e, double* err) {
     const double* m = d.meas + (size_t)e * MEAS;
     double pc[3];
     to_camera(d, e, m + 2, pc);
     residual(param_rec(d, e, PAR), pc, m, err);
+    return pc[2];
   }
+  DI static void error(const EdgeData& d, int e, double* err) { depth(d, e, err); }
   DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
     const double* m = d.meas + (size_t)e * MEAS;
     const double* K = param_rec(d, e, PAR);
@@ -1137,12 +1146,15 @@ struct FamilyStereoPoseOnly {
     err[1] = m[1] - v;
     err[2] = m[2] - ur;
   }
-  DI static void error(const EdgeData& d, int e, double* err) {
+  // the error, and the point's z in the camera frame (isDepthPositive, types_six_dof_expmap.h:309-312)
+  DI static double depth(const EdgeData& d, int e, double* err) {
     const double* m = d.meas + (size_t)e * MEAS;
     double pc[3];
     FamilyPoseOnly::to_camera(d, e, m + 3, pc);
     residual(param_rec(d, e, PAR), pc, m, err);
+    return pc[2];
   }
+  DI static void error(const EdgeData& d, int e, double* err) { depth(d, e, err); }
   DI static void linearize(const EdgeData& d, int e, double* err, double* A) {
     const double* m = d.meas + (size_t)e * MEAS;
     const double* K = param_rec(d, e, PAR);

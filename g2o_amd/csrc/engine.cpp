@@ -1227,6 +1227,8 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
     for (int k = 0; k < n; ++k) es->params.insert(es->params.end(), ident, ident + 7);
   }
   es->payload.clear();
+  if (!es->level.empty()) es->level.resize(es->ev0.size(), 0);  // new edges arrive at level 0
+  if (const size_t si = es - hg.esets.data(); si < views_.size()) views_[si].reset();  // the all-edges view is stale
   initialized = false;
   return G2OHIP_OK;
 }
@@ -1884,36 +1886,70 @@ static int family_of(int etype, int& vtA, int& vtB) {
   return is_hostj_binary(etype) ? FAM_HOSTJ : (is_hostj_unary(etype) ? FAM_U_HOSTJ : FAM_NONE);
 }
 
-// type checks and the vertices that have edges (initialize / update_initialization); a unary set checks one vertex
-static int mark_edge_vertices(const HostGraph& hg, std::vector<char>& has, bool& hostj, bool& unary) {
+// type checks and the vertices that have edges at the level (act: per edge set, per edge, 1 active; an empty list:
+// every edge) (initialize / update_initialization); a unary set checks one vertex
+static int mark_edge_vertices(const HostGraph& hg, const std::vector<std::vector<char>>& act, std::vector<char>& has,
+                              bool& hostj, bool& unary) {
   hostj = unary = false;
-  for (const HEdgeSet& es : hg.esets) {
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    const HEdgeSet& es = hg.esets[si];
     int vtA, vtB;
     const int fam = family_of(es.type, vtA, vtB);
     if (fam == FAM_NONE) return G2OHIP_ERR_UNSUPPORTED;
     hostj |= is_hostj_family(fam);
-    unary |= es.unary && !es.ev0.empty();
+    const std::vector<char>* on = si < act.size() && !act[si].empty() ? &act[si] : nullptr;
     for (size_t k = 0; k < es.ev0.size(); ++k) {
       const HVertex& a = hg.verts[es.ev0[k]];
       if (!is_hostj_family(fam) && a.type != vtA)
         throw StatusError(G2OHIP_ERR_UNSUPPORTED, "edge type " + std::to_string(es.type) + " on vertex " +
                                                       std::to_string(a.id) + " of vertex type " + std::to_string(a.type));
+      if (!es.unary) {
+        const HVertex& b = hg.verts[es.ev1[k]];
+        if (!is_hostj_family(fam) && b.type != vtB)
+          throw StatusError(G2OHIP_ERR_UNSUPPORTED, "edge type " + std::to_string(es.type) + " on vertex " +
+                                                        std::to_string(b.id) + " of vertex type " + std::to_string(b.type));
+      }
+      // (the types of every edge are checked, whatever its level: the all-edges view and structure-only read them all)
+      if (on && !(*on)[k]) continue;  // set aside on another level: it makes no vertex active
+      unary |= es.unary;
       has[es.ev0[k]] = 1;
-      if (es.unary) continue;
-      const HVertex& b = hg.verts[es.ev1[k]];
-      if (!is_hostj_family(fam) && b.type != vtB)
-        throw StatusError(G2OHIP_ERR_UNSUPPORTED, "edge type " + std::to_string(es.type) + " on vertex " +
-                                                      std::to_string(b.id) + " of vertex type " + std::to_string(b.type));
-      has[es.ev1[k]] = 1;
+      if (!es.unary) has[es.ev1[k]] = 1;
     }
   }
   return G2OHIP_OK;
 }
 
-int Engine::initialize() {  // sparse_optimizer.cpp:201-279 + buildIndexMapping :168-192
+int Engine::initialize_level(int level) {  // sparse_optimizer.cpp:201-279 + buildIndexMapping :168-192
   if (hg.num_edges() == 0) return G2OHIP_ERR_STATE;
+  // the edges of the level (:232): a snapshot, so that a level changed later waits for the next initialization
+  std::vector<std::vector<char>> act(hg.esets.size());
+  bool filtered = false;
+  if (level >= 0) {
+    long long non = 0;
+    for (size_t si = 0; si < hg.esets.size(); ++si) {
+      const HEdgeSet& es = hg.esets[si];
+      const size_t n = es.ev0.size();
+      if (es.level.empty()) {  // every edge at level 0
+        if (level != 0 && n) { act[si].assign(n, 0); filtered = true; }
+        else non += (long long)n;
+        continue;
+      }
+      std::vector<char> a(n);
+      size_t cnt = 0;
+      for (size_t k = 0; k < n; ++k) cnt += (a[k] = es.level[k] == level ? 1 : 0);
+      non += (long long)cnt;
+      if (cnt != n) { act[si] = std::move(a); filtered = true; }
+    }
+    if (non == 0) return G2OHIP_ERR_STATE;  // no edge at the level: an empty graph to the optimizer (:209-212)
+  }
+  initialized = false;
+  level_ = level;
+  eact_ = std::move(act);
+  level_filtered_ = filtered;
+  einit_.resize(hg.esets.size());
+  for (size_t si = 0; si < hg.esets.size(); ++si) einit_[si] = hg.esets[si].ev0.size();
   std::vector<char> has(hg.verts.size(), 0);
-  if (int r = mark_edge_vertices(hg, has, has_hostj, has_unary_)) return r;
+  if (int r = mark_edge_vertices(hg, eact_, has, has_hostj, has_unary_)) return r;
   active.clear();
   for (size_t k = 0; k < hg.verts.size(); ++k)
     if (has[k]) active.push_back((int)k);
@@ -1950,11 +1986,14 @@ int Engine::initialize() {  // sparse_optimizer.cpp:201-279 + buildIndexMapping 
   if (do_schur && !((pd == 6 && ld == 3) || (pd == 3 && ld == 2))) return G2OHIP_ERR_UNSUPPORTED;
   // landmark-landmark edges have no place in BlockSolver's Schur layout here (a prior on a landmark is no such edge:
   // it lands in the landmark's own Hll block)
-  for (const HEdgeSet& es : hg.esets)
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    const HEdgeSet& es = hg.esets[si];
     for (size_t k = 0; k < es.ev0.size() && !es.unary; ++k) {
+      if (!edge_on(si, k)) continue;
       const int a = hidx[es.ev0[k]], b = hidx[es.ev1[k]];
       if (a >= num_poses && b >= num_poses) return G2OHIP_ERR_UNSUPPORTED;
     }
+  }
   so_check_dim();  // structure_only_2 / _3 against the marginalised vertices' dimension
   initialized = true;
   structure_built = false;
@@ -1976,7 +2015,23 @@ int Engine::update_initialization() {
   std::vector<char> was(hg.verts.size(), 0), has(hg.verts.size(), 0);
   for (int vi : active) was[vi] = 1;
   bool hj = false, un = false;
-  if (int r = mark_edge_vertices(hg, has, hj, un)) return r;
+  // the edges added since the last initialization join when they are on the handle's level (they arrive at level 0
+  // unless the caller moved them); the earlier edges keep the state that initialization gave them
+  std::vector<std::vector<char>> act = eact_;
+  act.resize(hg.esets.size());
+  bool filtered = level_filtered_;
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    const HEdgeSet& es = hg.esets[si];
+    const size_t n = es.ev0.size(), n0 = si < einit_.size() ? einit_[si] : 0;
+    std::vector<char>& a = act[si];
+    bool all_on = true;
+    for (size_t k = n0; k < n; ++k) all_on &= level_ < 0 || es.level_of(k) == level_;
+    if (a.empty() && all_on) continue;
+    if (a.empty()) a.assign(n0, 1);
+    for (size_t k = n0; k < n; ++k) a.push_back(level_ < 0 || es.level_of(k) == level_ ? 1 : 0);
+    filtered |= !all_on;
+  }
+  if (int r = mark_edge_vertices(hg, act, has, hj, un)) return r;
   std::vector<int> fresh;
   for (size_t k = 0; k < hg.verts.size(); ++k)
     if (has[k] && !was[k]) fresh.push_back((int)k);
@@ -1994,12 +2049,142 @@ int Engine::update_initialization() {
     ++num_poses;
   }
   size_poses = num_poses * pd;
+  eact_ = std::move(act);
+  level_filtered_ = filtered;
+  einit_.resize(hg.esets.size());
+  for (size_t si = 0; si < hg.esets.size(); ++si) einit_[si] = hg.esets[si].ev0.size();
   has_hostj = hj;
   has_unary_ = un;
   initialized = true;
   structure_built = false;
   edges_ready = false;
   return G2OHIP_OK;
+}
+
+// the edges at the initialization's level (the graph's edges when no level set any aside)
+long long Engine::level_edge_count() const {
+  if (!level_filtered_) return hg.num_edges();
+  long long n = 0;
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    if (si >= eact_.size() || eact_[si].empty()) n += (long long)hg.esets[si].ev0.size();
+    else n += std::count(eact_[si].begin(), eact_[si].end(), (char)1);
+  }
+  return n;
+}
+
+// ---- Edge::setLevel / level()
+int Engine::set_edge_levels(int type, int n, const int* idx, const int* levels) {
+  HEdgeSet* es = hg.set_of(type);
+  if (!es || n < 0 || (n > 0 && !levels)) return G2OHIP_ERR_ARG;
+  const size_t ne_set = es->ev0.size();
+  if (!idx && (size_t)n != ne_set) return G2OHIP_ERR_ARG;
+  for (int k = 0; k < n; ++k)
+    if (levels[k] < 0) return G2OHIP_ERR_ARG;
+  if (idx) {
+    std::vector<char> seen(ne_set, 0);
+    for (int k = 0; k < n; ++k) {
+      if (idx[k] < 0 || (size_t)idx[k] >= ne_set || seen[idx[k]]) return G2OHIP_ERR_ARG;
+      seen[idx[k]] = 1;
+    }
+  }
+  if (n == 0) return G2OHIP_OK;
+  if (es->level.empty()) es->level.assign(ne_set, 0);
+  for (int k = 0; k < n; ++k) es->level[idx ? idx[k] : k] = levels[k];
+  return G2OHIP_OK;
+}
+
+int Engine::get_edge_levels(int type, int* out, int cap) {
+  const HEdgeSet* es = hg.set_of(type);
+  if (!es || cap < 0 || (cap > 0 && !out)) return G2OHIP_ERR_ARG;
+  const size_t n = std::min((size_t)cap, es->ev0.size());
+  for (size_t k = 0; k < n; ++k) out[k] = es->level_of(k);
+  return (int)es->ev0.size();
+}
+
+// ---- Edge::chi2(), isDepthPositive() and setLevel of every edge of a type: one pass of k_classify (classify.hip) over
+// the set's all-edges view
+int Engine::eval_edges(int type, bool classify, double* chi2, unsigned char* depth, double chi_max, int check_depth,
+                       int inlier, int outlier, long long* counts) {
+  HEdgeSet* es = hg.set_of(type);
+  if (!es) throw StatusError(G2OHIP_ERR_ARG, "the graph holds no edge of type " + std::to_string(type));
+  const size_t si = es - hg.esets.data();
+  int vtA, vtB;
+  const int fam = family_of(type, vtA, vtB);
+  if ((depth || check_depth) && !launch::family_has_depth(fam))
+    throw StatusError(G2OHIP_ERR_ARG, "edge type " + std::to_string(type) + " has no isDepthPositive()");
+  if (classify && ((inlier < 0 && inlier != G2OHIP_LEVEL_KEEP) || (outlier < 0 && outlier != G2OHIP_LEVEL_KEEP)))
+    throw StatusError(G2OHIP_ERR_ARG, "classify_edges: a level is >= 0 or G2OHIP_LEVEL_KEEP");
+  if (is_hostj_family(fam) || fam == FAM_NONE)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED, "per-edge chi2 of host-Jacobian edges (type " + std::to_string(type) +
+                                                  ") is not computed on the device: the host holds their errors itself");
+  if (nranks > 1)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED, "per-edge chi2 / classification on a sharded graph (" +
+                                                  std::to_string(nranks) + " ranks) is not supported");
+  if (!initialized) return G2OHIP_ERR_STATE;
+  ensure_device_state();
+  const int n = (int)es->ev0.size();
+  if (views_.size() < hg.esets.size()) views_.resize(hg.esets.size());
+  if (!views_[si]) {  // every edge of the set in insertion order, whatever its level or its vertices' state
+    auto v = std::make_unique<EdgeView>();
+    EGroup& g = v->g;
+    g.set = (int)si;
+    g.family = fam;
+    g.vtA = vtA;
+    g.vtB = vtB;
+    g.D = es->D;
+    g.DA = vertex_dim(vtA);
+    g.DB = vtB ? vertex_dim(vtB) : 0;
+    g.edges.resize(n);
+    std::iota(g.edges.begin(), g.edges.end(), 0);
+    g.ne = n;
+    fill_group_device(g);
+    v->chi.resize(std::max(n, 1));
+    v->depth.resize(std::max(n, 1));
+    v->level.resize(std::max(n, 1));
+    v->part.resize((size_t)launch::classify_blocks(n) * 3 + 3);
+    views_[si] = std::move(v);
+  }
+  EdgeView& V = *views_[si];
+  const bool want_depth = depth || check_depth;
+  const int nb = launch::classify_blocks(n);
+  launch::ClassifyArgs c{V.chi.get(), want_depth ? V.depth.get() : nullptr, nullptr, chi_max, check_depth, inlier,
+                         outlier, V.part.get(), V.part.get() + (size_t)nb * 3};
+  // both sides G2OHIP_LEVEL_KEEP: only the counts are wanted, no level is read or written (the array stays as it is)
+  const bool moves = classify && (inlier != G2OHIP_LEVEL_KEEP || outlier != G2OHIP_LEVEL_KEEP);
+  if (classify) c.level = V.level.get();
+  if (moves) {
+    std::vector<int> lv(std::max(n, 1), 0);
+    for (int k = 0; k < n; ++k) lv[k] = es->level_of(k);
+    V.level.upload(lv, stream);
+  }
+  timer.begin("classify", stream);
+  launch::classify(fam, group_args(V.g), n, c, stream);
+  timer.end(stream);
+  std::vector<int> lv;
+  long long cnt[3] = {0, 0, 0};
+  if (chi2 && n) V.chi.download(chi2, n, stream);
+  if (depth && n) V.depth.download(depth, n, stream);
+  if (moves) {
+    lv.resize(std::max(n, 1));
+    V.level.download(lv.data(), lv.size(), stream);
+  }
+  if (classify) HIP_CHECK(hipMemcpyAsync(cnt, c.counts, sizeof cnt, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  timer.collect();
+  if (moves) {
+    lv.resize(n);
+    es->level = std::move(lv);  // what get_edge_levels and the next initialize_level see
+  }
+  if (classify && counts) std::copy(cnt, cnt + 3, counts);
+  return G2OHIP_OK;
+}
+
+int Engine::edge_chi2(int type, double* chi2, unsigned char* depth) {
+  return eval_edges(type, false, chi2, depth, 0.0, 0, 0, 0, nullptr);
+}
+
+int Engine::classify_edges(int type, double chi_max, int check_depth, int inlier, int outlier, long long* counts) {
+  return eval_edges(type, true, nullptr, nullptr, chi_max, check_depth != 0, inlier, outlier, counts);
 }
 
 EdgeArgs Engine::group_args(const EGroup& g) const {
@@ -2055,18 +2240,128 @@ void Engine::refresh_host_payload(bool jacobians) {
 // the Kt records of nrec observations stay cache-resident between the linearize and camera passes (MALL)
 static bool kx_records_cached(double nrec) { return nrec * 80.0 <= 192.0 * (1 << 20); }
 
-void Engine::setup_edges_device() {
+void Engine::fill_group_device(EGroup& g) {
+  const HEdgeSet& es = hg.esets[g.set];
+  const int D = g.D, nm = es.nm, gne = g.ne;
+  std::vector<int> v0(std::max(gne, 1), 0), v1(std::max(gne, 1), 0);
+  const int minfo = D * (D + 1) / 2;
+  int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY
+                  ? 2
+                  : (g.family == FAM_SE3 ? 12 : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO ? 3 : 0));
+  switch (g.family) {  // unary families: the payload k_linearize_unary's family reads (device_types.hpp)
+    case FAM_U_SE2: case FAM_U_XYZ: mmeas = 3; break;
+    case FAM_U_SE2XY: case FAM_U_XY: mmeas = 2; break;
+    case FAM_U_SE3: mmeas = 24; break;
+    case FAM_SE3_XYZ: case FAM_SE3_XYZ_DEPTH: case FAM_SE3_XYZ_DISPARITY: mmeas = 3; break;
+    case FAM_EXPMAP: mmeas = 8; break;              // the measurement as an SE3Quat, padded to a 64-byte record
+    case FAM_U_POSE_ONLY: mmeas = 5; break;         // u v | Xw
+    case FAM_U_STEREO_POSE_ONLY: mmeas = 6; break;  // u_l v u_r | Xw
+  }
+  // device parameter record: the BA intrinsics as given; slam3d: the inverse offset as an isometry (12), the camera
+  // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
+  // point Xw ahead of them in the caller's record goes into the measurement payload)
+  const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type)
+                   : g.family == FAM_SE3_XYZ ? 12
+                   : is_slam3d_family(g.family) ? 16
+                   : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3 : 0;
+  std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
+      params(mpar ? (size_t)gne * mpar : 1);
+  for (int k = 0; k < gne; ++k) {
+    const int e = g.edges[k];
+    v0[k] = hg.verts[es.ev0[e]].local;
+    if (!es.unary) v1[k] = hg.verts[es.ev1[e]].local;
+    const double* m = es.meas.data() + (size_t)e * nm;
+    double* mo = meas.data() + (size_t)k * mmeas;
+    // x y z qx qy qz qw -> Z^-1 as [R^T (row-major) | -R^T t]: normalise q, Z = fromVectorQT (edge_se3.cpp:42-50)
+    auto iso_inverse_of = [](const double* m, double* mo) {
+      double q[4] = {m[3], m[4], m[5], m[6]};
+      const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (double& x : q) x /= n;
+      double Z[9];
+      q2R(q[0], q[1], q[2], q[3], Z);
+      double Rt[9] = {Z[0], Z[3], Z[6], Z[1], Z[4], Z[7], Z[2], Z[5], Z[8]};
+      for (int j = 0; j < 9; ++j) mo[j] = Rt[j];
+      for (int i = 0; i < 3; ++i) mo[9 + i] = -(Rt[i * 3] * m[0] + Rt[i * 3 + 1] * m[1] + Rt[i * 3 + 2] * m[2]);
+    };
+    if (is_ba_family(g.family)) {
+      for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+      for (int j = 0; j < mpar; ++j) params[(size_t)k * mpar + j] = es.params[(size_t)e * mpar + j];
+    } else if (g.family == FAM_SE3) {
+      iso_inverse_of(m, mo);
+    } else if (g.family == FAM_U_SE3) {  // edge_se3_prior.cpp:55-63: Z^-1, then the offset P = fromVectorQT(params)
+      iso_inverse_of(m, mo);
+      const double* p = es.params.data() + (size_t)e * 7;
+      double q[4] = {p[3], p[4], p[5], p[6]};
+      const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (double& x : q) x /= n;
+      q2R(q[0], q[1], q[2], q[3], mo + 12);
+      for (int i = 0; i < 3; ++i) mo[21 + i] = p[i];
+    } else if (g.family == FAM_U_SE2XY || g.family == FAM_U_XY || g.family == FAM_U_XYZ) {
+      for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+    } else if (g.family == FAM_SE2 || g.family == FAM_U_SE2) {  // edge_se2.cpp:41-47, edge_se2_prior.cpp:67-71: inverse measurement
+      const double th = norm_theta(-m[2]);
+      const double c = std::cos(th), s = std::sin(th);
+      mo[0] = c * (-m[0]) - s * (-m[1]);
+      mo[1] = s * (-m[0]) + c * (-m[1]);
+      mo[2] = th;
+    } else if (g.family == FAM_SE2XY) {
+      mo[0] = m[0]; mo[1] = m[1];
+    } else if (g.family == FAM_EXPMAP) {  // SE3Quat(Vector7), se3quat.h:81-88: normalizeRotation (w >= 0, unit)
+      double q[4] = {m[3], m[4], m[5], m[6]};
+      const double sn = q[3] < 0 ? -1.0 : 1.0;
+      for (double& x : q) x *= sn;
+      const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (int j = 0; j < 3; ++j) mo[j] = m[j];
+      for (int j = 0; j < 4; ++j) mo[3 + j] = q[j] / n;
+      mo[7] = 0;
+    } else if (is_pose_only_family(g.family)) {  // caller's record Xw fx fy cx cy (bf) -> payload obs | Xw, intrinsics
+      const int np = edge_param_dim(es.type);
+      const double* p = es.params.data() + (size_t)e * np;
+      for (int j = 0; j < nm; ++j) mo[j] = m[j];
+      for (int j = 0; j < 3; ++j) mo[nm + j] = p[j];
+      for (int j = 3; j < np; ++j) params[(size_t)k * mpar + j - 3] = p[j];
+    } else if (is_slam3d_family(g.family)) {  // the offset (x y z qx qy qz qw) -> its inverse [Rp^T | -Rp^T tp]
+      for (int j = 0; j < 3; ++j) mo[j] = m[j];
+      const int np = edge_param_dim(es.type);
+      const double* p = es.params.data() + (size_t)e * np;
+      double* po = params.data() + (size_t)k * mpar;
+      iso_inverse_of(p, po);
+      for (int j = 7; j < np; ++j) po[12 + j - 7] = p[j];
+    }
+    const double* I = es.info.data() + (size_t)e * D * D;
+    double* io = info.data() + (size_t)k * minfo;
+    int q = 0;
+    for (int c = 0; c < D; ++c)
+      for (int r = 0; r <= c; ++r) io[q++] = I[r * D + c];
+  }
+  g.v0.upload(v0, stream);
+  g.v1.upload(v1, stream);
+  {  // BA: edges sharing one information matrix / one set of intrinsics (the usual monocular case) read a single
+     // record instead of 24 + 32 bytes per edge (G2OHIP_UNIFORM_RECORDS=0 keeps per-edge records, A/B)
+    const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
+    g.ue = 0;
+    if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family)) && gne > 1 &&
+        !(ev && atoi(ev) == 0)) {
+      auto uniform = [&](const std::vector<double>& v, int st) {
+        for (int k = 1; k < gne; ++k)
+          if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
+        return true;
+      };
+      if (uniform(info, minfo)) { g.ue |= 1; info.resize(minfo); }
+      if (uniform(params, mpar)) { g.ue |= 2; params.resize(mpar); }
+    }
+  }
+  g.info.upload(info, stream);
+  g.params.upload(params, stream);
+  if (is_hostj_family(g.family)) upload_group_payload(hg, g, stream);
+  else g.meas.upload(meas, stream);
+}
+
+void Engine::form_groups(bool filtered, std::vector<EGroup>& out) const {
   // landmark shards: contiguous ranges of the hessian order, aligned with the factorization's cut (align_shards) or
   // the uniform split
   std::vector<int> bnd(nranks + 1);
   for (int r = 0; r <= nranks; ++r) bnd[r] = lm_bnd.empty() ? (int)((long long)num_landmarks * r / nranks) : lm_bnd[r];
-  int lm_begin = 0, lm_end = num_landmarks;
-  if (do_schur && nranks > 1) {
-    lm_begin = bnd[rank];
-    lm_end = bnd[rank + 1];
-  }
-  local_lm.clear();
-  for (int l = lm_begin; l < lm_end; ++l) local_lm.push_back(l);
   // an edge belongs to the rank owning its landmark endpoint; edges without a (free) landmark are assembled by rank 0
   // once. Pose graphs run replicas: every rank assembles every edge.
   // (a prior on a free landmark goes to that landmark's rank, one on a pose to rank 0: vb = -1 has no hessian index)
@@ -2076,8 +2371,7 @@ void Engine::setup_edges_device() {
     if (h < 0) return 0;
     return (int)(std::upper_bound(bnd.begin(), bnd.end(), h - num_poses) - bnd.begin()) - 1;
   };
-  groups.clear();
-  ne = 0;
+  out.clear();
   for (size_t si = 0; si < hg.esets.size(); ++si) {
     const HEdgeSet& es = hg.esets[si];
     int vtA, vtB;
@@ -2086,6 +2380,7 @@ void Engine::setup_edges_device() {
     std::vector<std::pair<int, int>> keys;
     std::vector<std::vector<int>> lists;
     for (size_t k = 0; k < es.ev0.size(); ++k) {
+      if (filtered && !edge_on(si, k)) continue;  // on another level than the initialization's
       const int va = es.ev0[k], vb = es.v1(k);
       // a unary edge on a fixed vertex is inactive (sparse_optimizer.cpp:241, allVerticesFixed): no chi2, no H, no b
       if (es.unary && hidx[va] < 0) continue;
@@ -2096,8 +2391,8 @@ void Engine::setup_edges_device() {
       lists[gi].push_back((int)k);
     }
     for (size_t gi = 0; gi < keys.size(); ++gi) {
-      groups.emplace_back();
-      EGroup& g = groups.back();
+      out.emplace_back();
+      EGroup& g = out.back();
       g.set = (int)si;
       g.family = fam;
       g.vtA = keys[gi].first;
@@ -2107,9 +2402,23 @@ void Engine::setup_edges_device() {
       g.DB = g.vtB ? vertex_dim(g.vtB) : 0;
       g.edges = std::move(lists[gi]);
       g.ne = (int)g.edges.size();
-      ne += g.ne;
     }
   }
+}
+
+void Engine::setup_edges_device() {
+  {  // this rank's landmarks (form_groups splits the edges by the same ranges)
+    int lm_begin = 0, lm_end = num_landmarks;
+    if (do_schur && nranks > 1) {
+      lm_begin = lm_bnd.empty() ? (int)((long long)num_landmarks * rank / nranks) : lm_bnd[rank];
+      lm_end = lm_bnd.empty() ? (int)((long long)num_landmarks * (rank + 1) / nranks) : lm_bnd[rank + 1];
+    }
+    local_lm.clear();
+    for (int l = lm_begin; l < lm_end; ++l) local_lm.push_back(l);
+  }
+  form_groups(true, groups);
+  ne = 0;
+  for (const EGroup& g : groups) ne += g.ne;
   // fused BA assembly: the only edge group is BA (monocular or stereo) and the Schur complement is formed
   // (G2OHIP_ASM_FUSED=0 keeps the generic slot path, for A/B checks)
   {
@@ -2121,122 +2430,7 @@ void Engine::setup_edges_device() {
     const HEdgeSet& es = hg.esets[g.set];
     std::stable_sort(g.edges.begin(), g.edges.end(), [&](int a, int b) { return hidx[es.ev0[a]] < hidx[es.ev0[b]]; });
   }
-  for (EGroup& g : groups) {
-    const HEdgeSet& es = hg.esets[g.set];
-    const int D = g.D, nm = es.nm, gne = g.ne;
-    std::vector<int> v0(std::max(gne, 1), 0), v1(std::max(gne, 1), 0);
-    const int minfo = D * (D + 1) / 2;
-    int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY
-                    ? 2
-                    : (g.family == FAM_SE3 ? 12 : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO ? 3 : 0));
-    switch (g.family) {  // unary families: the payload k_linearize_unary's family reads (device_types.hpp)
-      case FAM_U_SE2: case FAM_U_XYZ: mmeas = 3; break;
-      case FAM_U_SE2XY: case FAM_U_XY: mmeas = 2; break;
-      case FAM_U_SE3: mmeas = 24; break;
-      case FAM_SE3_XYZ: case FAM_SE3_XYZ_DEPTH: case FAM_SE3_XYZ_DISPARITY: mmeas = 3; break;
-      case FAM_EXPMAP: mmeas = 8; break;              // the measurement as an SE3Quat, padded to a 64-byte record
-      case FAM_U_POSE_ONLY: mmeas = 5; break;         // u v | Xw
-      case FAM_U_STEREO_POSE_ONLY: mmeas = 6; break;  // u_l v u_r | Xw
-    }
-    // device parameter record: the BA intrinsics as given; slam3d: the inverse offset as an isometry (12), the camera
-    // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
-    // point Xw ahead of them in the caller's record goes into the measurement payload)
-    const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type)
-                     : g.family == FAM_SE3_XYZ ? 12
-                     : is_slam3d_family(g.family) ? 16
-                     : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3 : 0;
-    std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
-        params(mpar ? (size_t)gne * mpar : 1);
-    for (int k = 0; k < gne; ++k) {
-      const int e = g.edges[k];
-      v0[k] = hg.verts[es.ev0[e]].local;
-      if (!es.unary) v1[k] = hg.verts[es.ev1[e]].local;
-      const double* m = es.meas.data() + (size_t)e * nm;
-      double* mo = meas.data() + (size_t)k * mmeas;
-      // x y z qx qy qz qw -> Z^-1 as [R^T (row-major) | -R^T t]: normalise q, Z = fromVectorQT (edge_se3.cpp:42-50)
-      auto iso_inverse_of = [](const double* m, double* mo) {
-        double q[4] = {m[3], m[4], m[5], m[6]};
-        const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        for (double& x : q) x /= n;
-        double Z[9];
-        q2R(q[0], q[1], q[2], q[3], Z);
-        double Rt[9] = {Z[0], Z[3], Z[6], Z[1], Z[4], Z[7], Z[2], Z[5], Z[8]};
-        for (int j = 0; j < 9; ++j) mo[j] = Rt[j];
-        for (int i = 0; i < 3; ++i) mo[9 + i] = -(Rt[i * 3] * m[0] + Rt[i * 3 + 1] * m[1] + Rt[i * 3 + 2] * m[2]);
-      };
-      if (is_ba_family(g.family)) {
-        for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
-        for (int j = 0; j < mpar; ++j) params[(size_t)k * mpar + j] = es.params[(size_t)e * mpar + j];
-      } else if (g.family == FAM_SE3) {
-        iso_inverse_of(m, mo);
-      } else if (g.family == FAM_U_SE3) {  // edge_se3_prior.cpp:55-63: Z^-1, then the offset P = fromVectorQT(params)
-        iso_inverse_of(m, mo);
-        const double* p = es.params.data() + (size_t)e * 7;
-        double q[4] = {p[3], p[4], p[5], p[6]};
-        const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        for (double& x : q) x /= n;
-        q2R(q[0], q[1], q[2], q[3], mo + 12);
-        for (int i = 0; i < 3; ++i) mo[21 + i] = p[i];
-      } else if (g.family == FAM_U_SE2XY || g.family == FAM_U_XY || g.family == FAM_U_XYZ) {
-        for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
-      } else if (g.family == FAM_SE2 || g.family == FAM_U_SE2) {  // edge_se2.cpp:41-47, edge_se2_prior.cpp:67-71: inverse measurement
-        const double th = norm_theta(-m[2]);
-        const double c = std::cos(th), s = std::sin(th);
-        mo[0] = c * (-m[0]) - s * (-m[1]);
-        mo[1] = s * (-m[0]) + c * (-m[1]);
-        mo[2] = th;
-      } else if (g.family == FAM_SE2XY) {
-        mo[0] = m[0]; mo[1] = m[1];
-      } else if (g.family == FAM_EXPMAP) {  // SE3Quat(Vector7), se3quat.h:81-88: normalizeRotation (w >= 0, unit)
-        double q[4] = {m[3], m[4], m[5], m[6]};
-        const double sn = q[3] < 0 ? -1.0 : 1.0;
-        for (double& x : q) x *= sn;
-        const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        for (int j = 0; j < 3; ++j) mo[j] = m[j];
-        for (int j = 0; j < 4; ++j) mo[3 + j] = q[j] / n;
-        mo[7] = 0;
-      } else if (is_pose_only_family(g.family)) {  // caller's record Xw fx fy cx cy (bf) -> payload obs | Xw, intrinsics
-        const int np = edge_param_dim(es.type);
-        const double* p = es.params.data() + (size_t)e * np;
-        for (int j = 0; j < nm; ++j) mo[j] = m[j];
-        for (int j = 0; j < 3; ++j) mo[nm + j] = p[j];
-        for (int j = 3; j < np; ++j) params[(size_t)k * mpar + j - 3] = p[j];
-      } else if (is_slam3d_family(g.family)) {  // the offset (x y z qx qy qz qw) -> its inverse [Rp^T | -Rp^T tp]
-        for (int j = 0; j < 3; ++j) mo[j] = m[j];
-        const int np = edge_param_dim(es.type);
-        const double* p = es.params.data() + (size_t)e * np;
-        double* po = params.data() + (size_t)k * mpar;
-        iso_inverse_of(p, po);
-        for (int j = 7; j < np; ++j) po[12 + j - 7] = p[j];
-      }
-      const double* I = es.info.data() + (size_t)e * D * D;
-      double* io = info.data() + (size_t)k * minfo;
-      int q = 0;
-      for (int c = 0; c < D; ++c)
-        for (int r = 0; r <= c; ++r) io[q++] = I[r * D + c];
-    }
-    g.v0.upload(v0, stream);
-    g.v1.upload(v1, stream);
-    {  // BA: edges sharing one information matrix / one set of intrinsics (the usual monocular case) read a single
-       // record instead of 24 + 32 bytes per edge (G2OHIP_UNIFORM_RECORDS=0 keeps per-edge records, A/B)
-      const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
-      g.ue = 0;
-      if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family)) && gne > 1 &&
-          !(ev && atoi(ev) == 0)) {
-        auto uniform = [&](const std::vector<double>& v, int st) {
-          for (int k = 1; k < gne; ++k)
-            if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
-          return true;
-        };
-        if (uniform(info, minfo)) { g.ue |= 1; info.resize(minfo); }
-        if (uniform(params, mpar)) { g.ue |= 2; params.resize(mpar); }
-      }
-    }
-    g.info.upload(info, stream);
-    g.params.upload(params, stream);
-    if (is_hostj_family(g.family)) upload_group_payload(hg, g, stream);
-    else g.meas.upload(meas, stream);
-  }
+  for (EGroup& g : groups) fill_group_device(g);
   if (ba_fused) {
     const EGroup& g = groups[0];
     const HEdgeSet& es = hg.esets[g.set];
@@ -2368,14 +2562,17 @@ void Engine::schur_pattern(std::vector<int>& sbi, std::vector<int>& sbj, std::ve
   std::vector<std::vector<int>> lmposes(num_landmarks);
   std::vector<std::vector<int>> rowcols(num_poses);
   for (int i = 0; i < num_poses; ++i) rowcols[i].push_back(i);
-  for (const HEdgeSet& es : hg.esets)
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    const HEdgeSet& es = hg.esets[si];
     for (size_t e = 0; e < es.ev0.size(); ++e) {
+      if (!edge_on(si, e)) continue;  // not at the initialization's level
       const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
       if (i1 < 0 || i2 < 0) continue;
       if (i1 >= num_poses && i2 < num_poses) lmposes[i1 - num_poses].push_back(i2);
       else if (i2 >= num_poses && i1 < num_poses) lmposes[i2 - num_poses].push_back(i1);
       else if (i1 < num_poses && i2 < num_poses) rowcols[std::min(i1, i2)].push_back(std::max(i1, i2));
     }
+  }
   for (auto& ps : lmposes) {
     std::sort(ps.begin(), ps.end());
     ps.erase(std::unique(ps.begin(), ps.end()), ps.end());
@@ -2397,12 +2594,15 @@ void Engine::schur_pattern(std::vector<int>& sbi, std::vector<int>& sbj, std::ve
 // Per pose: the landmark-sharded work that follows it in the cut's model (its observations of free landmarks).
 std::vector<double> Engine::pose_work() const {
   std::vector<double> w(num_poses, 0.0);
-  for (const HEdgeSet& es : hg.esets)
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    const HEdgeSet& es = hg.esets[si];
     for (size_t e = 0; e < es.ev0.size(); ++e) {
+      if (!edge_on(si, e)) continue;  // not at the initialization's level
       const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
       if (i1 >= num_poses && i2 >= 0 && i2 < num_poses) w[i2] += dist_cost::OBS_S;
       else if (i2 >= num_poses && i1 >= 0 && i1 < num_poses) w[i1] += dist_cost::OBS_S;
     }
+  }
   return w;
 }
 
@@ -2452,12 +2652,15 @@ void Engine::align_shards() {
   al_plan = planp;
   // per landmark its free poses (all edges)
   std::vector<std::vector<int>> lp(num_landmarks);
-  for (const HEdgeSet& es : hg.esets)
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    const HEdgeSet& es = hg.esets[si];
     for (size_t e = 0; e < es.ev0.size(); ++e) {
+      if (!edge_on(si, e)) continue;  // not at the initialization's level
       const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
       if (i1 >= num_poses && i2 >= 0 && i2 < num_poses) lp[i1 - num_poses].push_back(i2);
       else if (i2 >= num_poses && i1 >= 0 && i1 < num_poses) lp[i2 - num_poses].push_back(i1);
     }
+  }
   std::vector<int> lm_ptr(num_landmarks + 1, 0), lm_cams;
   for (int l = 0; l < num_landmarks; ++l) {
     lm_cams.insert(lm_cams.end(), lp[l].begin(), lp[l].end());
@@ -3295,14 +3498,17 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
           const int* it = std::lower_bound(b, e, j);
           return it != e && *it == j ? (int)(it - s_bj.data()) : -1;
         };
-        for (const HEdgeSet& es : hg.esets)
+        for (size_t si = 0; si < hg.esets.size(); ++si) {
+          const HEdgeSet& es = hg.esets[si];
           for (size_t e = 0; e < es.ev0.size(); ++e) {
+            if (!edge_on(si, e)) continue;  // not at the initialization's level
             const int i1 = hidx[es.ev0[e]], i2 = hx(es.v1(e));  // unary: i2 = -1
             if (i1 >= num_poses || i2 >= num_poses) continue;  // a free landmark endpoint: its owner's
             for (int h : {i1, i2})
               if (h >= 0) { const int t = blk(h, h); if (t >= 0) by0[t] = 1; }
             if (i1 >= 0 && i2 >= 0 && i1 != i2) { const int t = blk(std::min(i1, i2), std::max(i1, i2)); if (t >= 0) by0[t] = 1; }
           }
+        }
         chol.blk_local.assign(nS, 1);
         for (int t = 0; t < nS; ++t) {
           const int o = al_bowner[std::min(al_bpinv[s_bi[t]], al_bpinv[s_bj[t]])];
@@ -4121,7 +4327,7 @@ int Engine::optimize_step(const g2ohip_config* cfgp, int i, g2ohip_batch_stats* 
   if (st) {
     std::memset(st, 0, sizeof *st);
     st->iteration = i;
-    st->numEdges = (int)hg.num_edges();
+    st->numEdges = (int)level_edge_count();
     st->numVertices = (int)active.size();
   }
   const double ts = wall();
@@ -4146,12 +4352,12 @@ int Engine::optimize_step(const g2ohip_config* cfgp, int i, g2ohip_batch_stats* 
     if (cfg.verbose && rank == 0 && dogleg) {  // printVerbose (optimization_algorithm_dogleg.cpp:210-218)
       static const char* const step_name[] = {"Undefined", "Descent", "GN", "Dogleg"};
       fprintf(stderr, "iteration= %d\t chi2= %.6f\t time= %g\t edges= %zu\t Delta= %g\t step= %s\t tries= %d", i, c,
-              wall() - ts, (size_t)hg.num_edges(), dl_delta, step_name[dl_last_step & 3], dl_last_tries);
+              wall() - ts, (size_t)level_edge_count(), dl_delta, step_name[dl_last_step & 3], dl_last_tries);
       if (!dl_was_pd) fprintf(stderr, "\t lambda= %g", dl_lambda);
       fprintf(stderr, "\n");
     } else if (cfg.verbose && rank == 0)
       fprintf(stderr, "iteration= %d\t chi2= %.6f\t time= %g\t edges= %zu\t lambda= %.6f\t levenbergIter= %d\n", i, c,
-              wall() - ts, (size_t)hg.num_edges(), current_lambda, levenberg_iterations);
+              wall() - ts, (size_t)level_edge_count(), current_lambda, levenberg_iterations);
   }
   return result;
 }

@@ -46,6 +46,8 @@ struct HEdgeSet {
                                            // the offset, 7)
   int rk = 0;                           // robust kernel (G2OHIP_RK_*), delta
   double rk_delta = 1.0;
+  std::vector<int> level;               // OptimizableGraph::Edge::level() per edge; empty: every edge at level 0
+  int level_of(size_t k) const { return level.empty() ? 0 : level[k]; }
   std::vector<double> payload;          // host-J edges: latest [e | Ji | Jj] per edge from the host
   unsigned long long payload_ver = 0;   // device-state version the payload was computed at (0: set by the caller)
 };
@@ -280,7 +282,16 @@ class Engine {
   int minimal_state(double* out);
 
   // ---- SparseOptimizer / Solver ----
-  int initialize();
+  int initialize() { return initialize_level(level_); }  // (again) at the level the handle remembers
+  // SparseOptimizer::initializeOptimization(level) (sparse_optimizer.cpp:201-279): level < 0 every edge
+  int initialize_level(int level);
+  // Edge::setLevel / level() per edge of a type (insertion order); idx == nullptr: all n edges
+  int set_edge_levels(int type, int n, const int* idx, const int* levels);
+  int get_edge_levels(int type, int* out, int cap);
+  // Edge::chi2() and isDepthPositive() of every edge of the type (active or not), and with classify the new levels:
+  // bad = chi2 > chi_max || (check_depth && !(z > 0)), level = bad ? outlier : inlier (G2OHIP_LEVEL_KEEP: unchanged)
+  int edge_chi2(int type, double* chi2, unsigned char* depth);
+  int classify_edges(int type, double chi_max, int check_depth, int inlier, int outlier, long long* counts);
   // SparseOptimizer::updateInitialization + BlockSolver::updateStructure (online mode, non-Schur): vertices and edges
   // added after initialize() join with appended hessian indices; the existing vertices keep theirs
   int update_initialization();
@@ -348,6 +359,15 @@ class Engine {
   bool do_schur = false;
   int ne = 0;                    // local edges over all groups
   std::vector<EGroup> groups;
+  // the level filter of the last (update_)initialization: per edge set, per edge, 1 active at that level (empty: every
+  // edge of the set). Everything that forms the system reads this snapshot, never HEdgeSet::level, so a changed level
+  // waits for the next initialization
+  int level_ = 0;
+  std::vector<std::vector<char>> eact_;
+  std::vector<size_t> einit_;  // per edge set: its edge count at that initialization
+  bool level_filtered_ = false;  // some edge is inactive by its level
+  long long level_edge_count() const;
+  bool edge_on(size_t si, size_t k) const { return si >= eact_.size() || eact_[si].empty() || eact_[si][k] != 0; }
   bool has_hostj = false;
   bool has_unary_ = false;  // some edge set is unary (lm_pcg6_3_eigen refuses, the fused BA assembly does not apply)
   int hx(int v) const { return v < 0 ? -1 : hidx[v]; }  // hessian index of a vertex, -1: fixed or no vertex
@@ -494,6 +514,24 @@ class Engine {
   void ensure_device_state();
   void sync_host_state();
   void setup_edges_device();
+  // the edge groups of the graph on this rank (one per edge set and endpoint vertex type pair, edges in insertion
+  // order); filtered: only the edges of the initialization's level
+  void form_groups(bool filtered, std::vector<EGroup>& out) const;
+  // the device arrays of one group from its edge list: v0 / v1, measurement -> family payload, information -> packed
+  // upper, parameters -> device record, uniform-record detection (ue)
+  void fill_group_device(EGroup& g);
+  // all-edges view of an edge set (every edge in insertion order, inactive ones included) with the outputs of the
+  // classify pass; built on the first edge_chi2 / classify_edges of the type, dropped when edges are added to the set
+  struct EdgeView {
+    EGroup g;
+    DevBuf<double> chi;
+    DevBuf<unsigned char> depth;
+    DevBuf<int> level;
+    DevBuf<long long> part;  // [3 per block | 3 totals]
+  };
+  std::vector<std::unique_ptr<EdgeView>> views_;  // per edge set, null: not built
+  int eval_edges(int type, bool classify, double* chi2, unsigned char* depth, double chi_max, int check_depth,
+                 int inlier, int outlier, long long* counts);
   void compute_errors_async(bool reduce = true);  // reduce: the chi2 all-reduce over landmark shards
   void refresh_host_payload(bool jacobians);  // host-J groups: payload at the current state (callback), upload
   EdgeArgs group_args(const EGroup& g) const;
@@ -526,6 +564,11 @@ class Engine {
     long long nent = 0;
   } so_;
   void so_build_list();
+  // the groups structure-only reads: `groups`, or under a level filter groups of every edge whatever its level
+  // (StructureOnlySolver::calc walks v->edges(), structure_only_solver.h:82), built once per edge setup
+  std::vector<EGroup> so_all_groups_;
+  unsigned long long so_all_key_ = 0;
+  const std::vector<EGroup>& so_groups();
   void so_check_dim() const;  // throws G2OHIP_ERR_UNSUPPORTED: the name's PointDoF against the marginalised vertices
   // dogleg state (optimization_algorithm_dogleg.h): properties, trust region, damping of the not-PD branch
   double dl_user_delta = 1e4, dl_initial_lambda = 1e-7, dl_lambda_factor = 10.0;

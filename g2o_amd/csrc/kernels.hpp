@@ -39,6 +39,22 @@ struct EdgeArgs {
 
 namespace launch {
 void error(int family, const EdgeArgs& a, int ne, double* chi, hipStream_t s);
+// Edge::chi2 (raw e^T Omega e, no robust kernel), isDepthPositive and setLevel of every edge of a set's all-edges view
+// (classify.hip). level == nullptr: chi2 / depth only. With level: bad = chi2 > chi_max || (check_depth && !(z > 0)),
+// level[e] = bad ? outlier : inlier (G2OHIP_LEVEL_KEEP: left as it is), counts = edges over chi_max, edges failing the
+// depth test, bad edges, summed from the per-block partials in part (3 per block of classify_blocks(ne))
+struct ClassifyArgs {
+  double* chi;
+  unsigned char* depth;  // nullptr: not wanted (only the projection families have it: family_has_depth)
+  int* level;
+  double chi_max;
+  int check_depth, inlier, outlier;
+  long long* part;
+  long long* counts;
+};
+bool family_has_depth(int family);
+int classify_blocks(int ne);
+void classify(int family, const EdgeArgs& a, int ne, const ClassifyArgs& c, hipStream_t s);
 // off_dst: destination of each edge's off-diagonal block, an offset into off_base (the Hessian) or, with bit 62
 // set, into off_slot (per-edge slots of blocks several edges share)
 void linearize(int family, const EdgeArgs& a, int ne, const int* h0, const int* h1, double* slot0, double* slot1,

@@ -30,10 +30,28 @@ void Engine::so_check_dim() const {
   }
 }
 
+// The groups calc reads. StructureOnlySolver::calc walks v->edges() (:82): every edge of the landmark whatever its
+// level. Without a level filter these are `groups`; with one, groups of every edge (same per-landmark edge order,
+// same conversion), kept beside the active ones and rebuilt with them
+const std::vector<EGroup>& Engine::so_groups() {
+  if (!level_filtered_) {
+    so_all_groups_.clear();
+    so_all_key_ = 0;
+    return groups;
+  }
+  if (so_all_key_ != edges_ver) {
+    form_groups(false, so_all_groups_);
+    for (EGroup& g : so_all_groups_) fill_group_device(g);
+    so_all_key_ = edges_ver;
+  }
+  return so_all_groups_;
+}
+
 // init() (:214-225): the active vertices with marginalized() set, fixed ones included, in id order; per landmark the
 // edges of v->edges() as (group, edge) entries, by group and then by the group's edge order
 void Engine::so_build_list() {
   if (so_.key == edges_ver) return;
+  const std::vector<EGroup>& groups = so_groups();
   SoList& L = so_;
   L.refuse.clear();
   L.lm_of_vertex.assign(hg.verts.size(), -1);
@@ -144,6 +162,7 @@ int Engine::structure_only_calc(int n, const int* ids, int num_iters, int num_ma
     if (nsel) L.sel.upload(sel, stream);
   }
   if (nsel == 0) return G2OHIP_OK;  // no marginalised vertex: OK and nothing done (:78 loops over an empty set)
+  const std::vector<EGroup>& groups = so_groups();
   std::vector<launch::SoGroup> sg(std::max<size_t>(L.group_of.size(), 1));
   std::memset(sg.data(), 0, sizeof(launch::SoGroup) * sg.size());
   for (size_t k = 0; k < L.group_of.size(); ++k) {

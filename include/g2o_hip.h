@@ -270,8 +270,53 @@ int g2ohip_dogleg_state(g2ohip_graph* g, double* out, int n);
  * marginalised vertices' dimension is not the name's (the reference asserts it, :81). */
 int g2ohip_structure_only_calc(g2ohip_graph* g, int n, const int* ids, int num_iters, int num_max_trials,
                                long long* counts);
-/* SparseOptimizer::initializeOptimization(0): active edges/vertices, index mapping */
+/* SparseOptimizer::initializeOptimization(0): active edges/vertices, index mapping. The same as
+ * g2ohip_initialize_level(g, 0). */
 int g2ohip_initialize(g2ohip_graph* g);
+
+/* ---- edge levels, per-edge chi2, outlier classification (the pose-optimisation / local-BA loop of ORB-SLAM-style
+ * callers: optimise, read every edge's chi2() and isDepthPositive(), setLevel(1) the bad ones,
+ * initializeOptimization(0), optimise again) ---- */
+#define G2OHIP_LEVEL_KEEP (-2147483647 - 1)
+/* OptimizableGraph::Edge::setLevel / level() (optimizable_graph.h), per edge of a type in insertion order. Every edge
+ * starts at level 0. idx == NULL: n must be the type's edge count and levels[k] is edge k's level; otherwise idx[k]
+ * selects the edges. An index out of range or given twice, a negative level, or a type the graph holds no edge of
+ * returns G2OHIP_ERR_ARG and changes nothing. As in the reference a changed level has no effect until the next
+ * g2ohip_initialize*: chi2, optimize, build_system and stage keep the active set of the last initialisation. */
+int g2ohip_set_edge_levels(g2ohip_graph* g, int edge_type, int n, const int* idx, const int* levels);
+/* the levels of the type's edges into out (up to cap of them; out may be NULL); returns the type's edge count */
+int g2ohip_get_edge_levels(g2ohip_graph* g, int edge_type, int* out, int cap);
+/* SparseOptimizer::initializeOptimization(level) (sparse_optimizer.cpp:201-279): an edge is active when level < 0 or
+ * its level equals `level`, and (unary edges) its vertex is not fixed; a vertex is active when it has an active edge
+ * (:228-249), so a landmark whose observations were all set aside leaves the system. Unlike the reference (:241,
+ * allVerticesFixed) a binary edge between two fixed vertices stays active, as it always has here: it adds nothing to the
+ * system and a constant to g2ohip_chi2. The vertex types of every edge are checked, whatever its level
+ * (G2OHIP_ERR_UNSUPPORTED). The handle remembers the level:
+ * g2ohip_update_initialization filters the new edges by it, and a graph grown by g2ohip_add_* is initialised again at
+ * it by the next chi2 / optimize. No active edge: G2OHIP_ERR_STATE; no active free pose: G2OHIP_ERR_UNSUPPORTED (as
+ * g2ohip_initialize on an empty / pose-less graph). Host-Jacobian types take levels like any other (the payload still
+ * covers every edge of the type in insertion order), sharded handles too. g2ohip_structure_only_calc and the
+ * structure_only_* algorithms use every edge of an active landmark whatever its level (v->edges(),
+ * structure_only_solver.h:82); g2ohip_save_g2o writes every edge. */
+int g2ohip_initialize_level(g2ohip_graph* g, int level);
+/* Edge::chi2() = e^T Omega e (base_edge.h; NOT robustified, whatever robust kernel the type has) of EVERY edge of the
+ * type in insertion order, active or not (another level, a unary edge on a fixed vertex, an edge between fixed
+ * vertices), at the estimates the device holds. depth_positive (or NULL): isDepthPositive(), (z > 0) of the point in
+ * the camera frame, for G2OHIP_E_SE3_PROJECT_XYZ, G2OHIP_E_STEREO_SE3_PROJECT_XYZ and the two *_ONLYPOSE types
+ * (types_six_dof_expmap.h:218-222, 248-251, 279-283, 309-312); non-NULL for another type is G2OHIP_ERR_ARG.
+ * G2OHIP_ERR_STATE before g2ohip_initialize* (or after edges or vertices were added and nothing initialised since);
+ * G2OHIP_ERR_UNSUPPORTED (text in g2ohip_last_error) for host-Jacobian types, whose errors the host holds itself, and
+ * on sharded handles (nranks > 1). */
+int g2ohip_edge_chi2(g2ohip_graph* g, int edge_type, double* chi2, unsigned char* depth_positive);
+/* chi2 / depth test and setLevel in one device pass over every edge of the type:
+ * bad = chi2 > chi2_max || (check_depth && !(z > 0)) (a NaN chi2 is not bad by itself, as in the callers' C++);
+ * level = bad ? outlier_level : inlier_level, G2OHIP_LEVEL_KEEP in either place leaves that edge's level as it is.
+ * counts (or NULL): [0] edges with chi2 > chi2_max, [1] edges failing the depth test (0 when not checked), [2] bad
+ * edges. check_depth on a type without the test, or a negative level other than G2OHIP_LEVEL_KEEP: G2OHIP_ERR_ARG.
+ * Refusals as g2ohip_edge_chi2. The new levels are what g2ohip_get_edge_levels and the next g2ohip_initialize_level
+ * see. */
+int g2ohip_classify_edges(g2ohip_graph* g, int edge_type, double chi2_max, int check_depth, int inlier_level,
+                          int outlier_level, long long counts[3]);
 /* SparseOptimizer::updateInitialization(vset, eset) + BlockSolver::updateStructure (sparse_optimizer.cpp:465-502,
  * block_solver.hpp:258-312), online mode: after g2ohip_initialize (and optimizing), vertices and edges added with
  * g2ohip_add_vertices / g2ohip_add_edges join the optimization without re-indexing the existing ones — each new free
