@@ -53,6 +53,12 @@ E_SE3_XYZ, E_SE3_XYZ_DEPTH, E_SE3_XYZ_DISPARITY = 7, 8, 9
 E_SE3_EXPMAP = 10
 
 
+# the sba types (include/g2o_hip.h G2OHIP_V_CAM, G2OHIP_E_PROJECT_P2MC / _P2SC): VertexCam, estimate x y z qx qy qz qw
+# (camera-to-world) fx fy cx cy baseline; v0 the point, v1 the camera; meas u v / u v u_r; params None
+V_CAM = 6
+E_PROJECT_P2MC, E_PROJECT_P2SC = 11, 12
+
+
 # edge types the device does not know: host-supplied error + Jacobians (include/g2o_hip.h G2OHIP_E_HOSTJ)
 def E_HOSTJ(D: int) -> int:
     return 32 + D
@@ -76,6 +82,7 @@ def E_HOSTJ_UNARY(D: int) -> int:
 LOAD_UNARY = 1
 LOAD_SLAM3D = 2
 LOAD_EXPMAP = 4
+LOAD_SBA = 8
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -369,6 +376,10 @@ class SparseOptimizer:
     def add_vertices(self, vs):
         ids = np.ascontiguousarray(vs.ids, np.int32)
         est = np.ascontiguousarray(vs.est, np.float64)
+        ed = synth.EST_DIM.get(vs.vtype)
+        if ed is not None and est.size != len(ids) * ed:  # the C side reads n * ed doubles
+            raise G2OHipError(f"add_vertices: vertex type {vs.vtype} takes {ed} estimate values per vertex, got "
+                              f"{est.size} for {len(ids)} vertices")
         fx = np.ascontiguousarray(vs.fixed, np.int32)
         mg = np.ascontiguousarray(vs.marginalized, np.int32)
         _check(lib().g2ohip_add_vertices(self.h, vs.vtype, len(ids), _p(ids), _p(est), _p(fx), _p(mg)),
@@ -431,12 +442,14 @@ class SparseOptimizer:
         _check(lib().g2ohip_set_estimates(self.h, vtype, _p(est)), "set_estimates")
 
     def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False,
-             expmap: bool = False):
+             expmap: bool = False, sba: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
         EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
         (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
-        PARAMS_CAMERACALIB), expmap=True EDGE_SE3:EXPMAP; all are skipped otherwise."""
-        flags = (LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0)
+        PARAMS_CAMERACALIB), expmap=True EDGE_SE3:EXPMAP, sba=True the sba tags (VERTEX_CAM, EDGE_PROJECT_P2MC,
+        EDGE_PROJECT_P2SC); all are skipped otherwise."""
+        flags = ((LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0) |
+                 (LOAD_SBA if sba else 0))
         _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:

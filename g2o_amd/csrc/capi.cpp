@@ -107,7 +107,7 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
   return guarded([&] { return g->e->load(path, marginalize_xyz); });
 }
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
-  if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP))) return G2OHIP_ERR_ARG;
+  if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP | G2OHIP_LOAD_SBA))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
@@ -128,6 +128,21 @@ int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
               std::to_string(type) + "), which the .g2o format cannot carry (the reference's reader and writer for the "
               "tag leave out the point Xw and the intrinsics)";
       return G2OHIP_ERR_UNSUPPORTED;
+    }
+  // EDGE_PROJECT_P2MC / EDGE_PROJECT_P2SC lines hold the measurement alone and the reader sets the identity
+  // (types_sba.cpp:204-244): any other information would be lost
+  for (int type : {G2OHIP_E_PROJECT_P2MC, G2OHIP_E_PROJECT_P2SC})
+    if (const auto* es = g->e->hg.set_of(type)) {
+      const int D = es->D;
+      for (size_t k = 0; k < es->ev0.size(); ++k)
+        for (int r = 0; r < D; ++r)
+          for (int c = 0; c < D; ++c)
+            if (es->info[k * D * D + r * D + c] != (r == c ? 1.0 : 0.0)) {
+              g_err = "g2ohip_save_g2o: edge " + std::to_string(k) + " of type " + std::to_string(type) +
+                      " has an information matrix other than the identity, which the EDGE_PROJECT_P2MC / "
+                      "EDGE_PROJECT_P2SC lines of the .g2o format cannot carry";
+              return G2OHIP_ERR_UNSUPPORTED;
+            }
     }
   return guarded([&] { return g->e->save(path); });
 }

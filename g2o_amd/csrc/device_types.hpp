@@ -791,6 +791,97 @@ using FamilySE3XYZ = FamilySlam3d<SLAM3D_XYZ>;
 using FamilySE3XYZDepth = FamilySlam3d<SLAM3D_DEPTH>;
 using FamilySE3XYZDisparity = FamilySlam3d<SLAM3D_DISPARITY>;
 
+// ---- EdgeProjectP2MC / EdgeProjectP2SC (types_sba.h:173-250, types_sba.cpp:249-403): v0 = point (3), v1 = VertexCam,
+// an SBACam (sbacam.h:55-175): the camera-to-world pose and the intrinsics in one state record of 12 doubles
+//   tx ty tz qx qy qz qw fx fy cx cy baseline
+// pc = R^T (pw - t); e = (fx pc.x / pc.z + cx - u, fy pc.y / pc.z + cy - v), projected minus measured; the stereo row
+// e2 = fx (pc.x - b) / pc.z + cx - u_r. Under SBACam::update (t += dt, q = q * (dq, sqrt(1 - |dq|^2))) a derivative dp
+// of pc gives the rows (pc.z dp.x - pc.x dp.z) fx / pc.z^2, (pc.z dp.y - pc.y dp.z) fy / pc.z^2 and, stereo,
+// (pc.z dp.x - (pc.x - b) dp.z) fx / pc.z^2, with dp = column k of R^T for the point, its negative for the camera
+// translation and (dRi_k R^T)(pw - t) = dRi_k pc for the camera rotation: dRi_k = -2 [e_k]x, so the three rotation
+// columns are 2 (pc x e_k) = (0, 2 pc.z, -2 pc.y), (-2 pc.z, 0, 2 pc.x), (2 pc.y, -2 pc.x, 0). R^T is built once per
+// edge; there is no parameter record and no depth test (the reference types have no isDepthPositive). ----
+template <bool STEREO>
+struct FamilySBA {
+  static constexpr int D = STEREO ? 3 : 2, DA = 3, DB = 6, MEAS = D, INFO = D * (D + 1) / 2;
+  static constexpr int S0 = 3, S1 = 12;  // state strides
+  // pc = R^T (pw - t); Rt = R^T row-major
+  DI static void to_camera(const double* c, const double* p, double* Rt, double* pc) {
+    double R[9];
+    quat_to_R(c[3], c[4], c[5], c[6], R);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Rt[i * 3 + j] = R[j * 3 + i];
+    const double d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pc[i] = Rt[i * 3] * d0 + Rt[i * 3 + 1] * d1 + Rt[i * 3 + 2] * d2;
+  }
+  DI static void residual(const double* c, const double* pc, const double* m, double* err) {
+    const double iz = 1.0 / pc[2];
+    err[0] = c[7] * pc[0] * iz + c[9] - m[0];
+    err[1] = c[8] * pc[1] * iz + c[10] - m[1];
+    if (STEREO) err[2] = c[7] * (pc[0] - c[11]) * iz + c[9] - m[2];
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    const double* cp = d.s1 + (size_t)d.v1[e] * 12;
+    const double* pp = d.s0 + (size_t)d.v0[e] * 3;
+    const double* mp = d.meas + (size_t)e * MEAS;
+    double c[12], m[MEAS], Rt[9], pc[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) c[k] = cp[k];
+#pragma unroll
+    for (int k = 0; k < MEAS; ++k) m[k] = mp[k];
+    const double p[3] = {pp[0], pp[1], pp[2]};
+    to_camera(c, p, Rt, pc);
+    residual(c, pc, m, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A, double* B) {
+    linearize_at(d, e, d.v0[e], d.v1[e], err, A, B);
+  }
+  // A (D x 3): the point's Jacobian; B (D x 6): the camera's
+  DI static void linearize_at(const EdgeData& d, int e, int v0, int v1, double* err, double* A, double* B) {
+    const double* cp = d.s1 + (size_t)v1 * 12;
+    const double* pp = d.s0 + (size_t)v0 * 3;
+    const double* mp = d.meas + (size_t)e * MEAS;
+    double c[12], m[MEAS], Rt[9], pc[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) c[k] = cp[k];
+#pragma unroll
+    for (int k = 0; k < MEAS; ++k) m[k] = mp[k];
+    const double p[3] = {pp[0], pp[1], pp[2]};
+    to_camera(c, p, Rt, pc);
+    residual(c, pc, m, err);
+    const double ipz2 = 1.0 / (pc[2] * pc[2]);
+    const double fx2 = ipz2 * c[7], fy2 = ipz2 * c[8];
+    const double xs = pc[0] - c[11];  // stereo row numerator
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {  // dp = column k of R^T; the translation columns are its negative
+      const double dx = Rt[k], dy = Rt[3 + k], dz = Rt[6 + k];
+      A[k] = (pc[2] * dx - pc[0] * dz) * fx2;
+      A[3 + k] = (pc[2] * dy - pc[1] * dz) * fy2;
+      if (STEREO) A[6 + k] = (pc[2] * dx - xs * dz) * fx2;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      B[k] = -A[k];
+      B[6 + k] = -A[3 + k];
+      if (STEREO) B[12 + k] = -A[6 + k];
+    }
+    // rotation columns: dp_x = (0, 2 z, -2 y), dp_y = (-2 z, 0, 2 x), dp_z = (2 y, -2 x, 0)
+    const double x2 = 2 * pc[0], y2 = 2 * pc[1], z2 = 2 * pc[2];
+    const double rx[3] = {0.0, -z2, y2}, ry[3] = {z2, 0.0, -x2}, rz[3] = {-y2, x2, 0.0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      B[3 + k] = (pc[2] * rx[k] - pc[0] * rz[k]) * fx2;
+      B[9 + k] = (pc[2] * ry[k] - pc[1] * rz[k]) * fy2;
+      if (STEREO) B[15 + k] = (pc[2] * rx[k] - xs * rz[k]) * fx2;
+    }
+  }
+};
+using FamilySBAMono = FamilySBA<false>;
+using FamilySBAStereo = FamilySBA<true>;
+
 // ---- host-Jacobian edges (an edge type the device does not know): the host's linearizeOplus
 // (base_binary_edge.hpp:198-266 numeric, or the type's own analytic one) supplies, per edge, the error and
 // both Jacobians row-major in the meas payload: [e (D) | Ji (D x DA) | Jj (D x DB)] ----

@@ -33,10 +33,13 @@ static double wall() {
 }
 
 int vertex_dim(int t) {
-  return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT ? 6
+  return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT || t == G2OHIP_V_CAM ? 6
          : (t == G2OHIP_V_XYZ || t == G2OHIP_V_SE2 ? 3 : (t == G2OHIP_V_XY ? 2 : -1));
 }
-int vertex_est_dim(int t) { return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT ? 7 : (t == G2OHIP_V_XY ? 2 : 3); }
+int vertex_est_dim(int t) {
+  if (t == G2OHIP_V_CAM) return 12;  // the VERTEX_CAM line: x y z qx qy qz qw fx fy cx cy baseline
+  return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT ? 7 : (t == G2OHIP_V_XY ? 2 : 3);
+}
 int vertex_state_stride(int t) {
   switch (t) {
     case G2OHIP_V_SE3_EXPMAP: return 8;
@@ -44,6 +47,7 @@ int vertex_state_stride(int t) {
     case G2OHIP_V_SE3_QUAT: return 12;
     case G2OHIP_V_SE2: return 3;
     case G2OHIP_V_XY: return 2;
+    case G2OHIP_V_CAM: return 12;
   }
   return 0;
 }
@@ -53,6 +57,8 @@ static bool is_hostj_unary(int e) { return e > G2OHIP_E_HOSTJ_UNARY(0) && e <= G
 static bool is_hostj(int e) { return is_hostj_binary(e) || is_hostj_unary(e); }
 // the slam3d landmark edges: EdgeSE3PointXYZ, ...Depth, ...Disparity
 static bool is_slam3d_type(int e) { return e >= G2OHIP_E_SE3_XYZ && e <= G2OHIP_E_SE3_XYZ_DISPARITY; }
+// the sba types on a VertexCam: EdgeProjectP2MC, EdgeProjectP2SC
+static bool is_sba_type(int e) { return e == G2OHIP_E_PROJECT_P2MC || e == G2OHIP_E_PROJECT_P2SC; }
 // BaseUnaryEdge types: the five priors, the two pose-only projections (EdgeSE3ProjectXYZOnlyPose and its stereo
 // sibling, on a VertexSE3Expmap) and the unary host-J escape
 static bool is_unary_type(int e) {
@@ -64,7 +70,8 @@ int edge_dim(int e) {
   switch (e) {
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: case G2OHIP_E_SE2_PRIOR: case G2OHIP_E_XYZ_PRIOR: return 3;
     case G2OHIP_E_SE3_XYZ: case G2OHIP_E_SE3_XYZ_DEPTH: case G2OHIP_E_SE3_XYZ_DISPARITY: return 3;
-    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: return 3;
+    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: case G2OHIP_E_PROJECT_P2SC: return 3;
+    case G2OHIP_E_PROJECT_P2MC: return 2;
     case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: return 2;
     case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: return 6;
   }
@@ -75,6 +82,7 @@ int edge_meas_dim(int e) {
   if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR || e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 2;
   if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_EXPMAP) return 7;
   if (is_slam3d_type(e)) return 3;
+  if (is_sba_type(e)) return e == G2OHIP_E_PROJECT_P2MC ? 2 : 3;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
 }
 // doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
@@ -171,6 +179,14 @@ void set_state_from_est(int vt, const double* est, double* st) {
       break;
     case G2OHIP_V_SE2: st[0] = est[0]; st[1] = est[1]; st[2] = est[2]; break;
     case G2OHIP_V_XY: st[0] = est[0]; st[1] = est[1]; break;
+    case G2OHIP_V_CAM: {  // VertexCam::read (types_sba.cpp:74-112) + SE3Quat(q, t) (se3quat.h:57-59): unit q, w >= 0
+      double q[4] = {est[3], est[4], est[5], est[6]};
+      qnorm_pos(q);
+      st[0] = est[0]; st[1] = est[1]; st[2] = est[2];
+      st[3] = q[0]; st[4] = q[1]; st[5] = q[2]; st[6] = q[3];
+      for (int k = 7; k < 12; ++k) st[k] = est[k];
+      break;
+    }
   }
 }
 void est_from_state(int vt, const double* st, double* est) {
@@ -1202,6 +1218,7 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   if (unary != (v1 == nullptr) && (n > 0 || v1)) return G2OHIP_ERR_ARG;  // v1 is NULL for the unary types, only for them
   const int np = edge_param_dim(type);
   if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ) return G2OHIP_ERR_ARG;
+  if (is_sba_type(type) && params) return G2OHIP_ERR_ARG;  // the intrinsics live in the VertexCam
   const int nm = edge_meas_dim(type);
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
@@ -1278,7 +1295,7 @@ int Engine::set_host_callback(g2ohip_host_edge_fn fn, void* user) {
 // into typed records, and the records added in file order with batched add_vertices / add_edges. Unknown tags
 // are skipped with one warning per tag (:455-460); FIX lines fix vertices after loading (:409-417).
 namespace {
-struct ParsedVertex { int type, id; double est[7]; };
+struct ParsedVertex { int type, id; double est[12]; };  // (12: VERTEX_CAM)
 // unary: b = -1, or the SE3 prior's parameter id; pid: the slam3d landmark edges' parameter id
 struct ParsedEdge { int type, a, b; double m[7], info[36], p[11]; int pid = -1; };
 // PARAMS_SE3OFFSET id x y z qx qy qz qw; camera: PARAMS_CAMERACALIB, the same followed by fx fy cx cy
@@ -1317,8 +1334,8 @@ struct Cursor {
 };
 // unary: the unary edge tags and PARAMS_SE3OFFSET are parsed (G2OHIP_LOAD_UNARY), else skipped as unknown tags;
 // slam3d: VERTEX_TRACKXYZ, PARAMS_SE3OFFSET, PARAMS_CAMERACALIB and the three landmark edge tags (G2OHIP_LOAD_SLAM3D)
-// expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP)
-void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, ParsedChunk& out) {
+// expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP); sba: VERTEX_CAM, EDGE_PROJECT_P2MC, EDGE_PROJECT_P2SC (G2OHIP_LOAD_SBA)
+void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, bool sba, ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1331,7 +1348,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
     if (tag.empty() || tag[0] == '#') continue;
     if (tag == "VERTEX_SE3:EXPMAP" || tag == "VERTEX_SE3:QUAT") {
       ParsedVertex v{tag == "VERTEX_SE3:EXPMAP" ? G2OHIP_V_SE3_EXPMAP : G2OHIP_V_SE3_QUAT, c.i(), {}};
-      for (double& x : v.est) x = c.d();
+      for (int k = 0; k < 7; ++k) v.est[k] = c.d();
       if (v.type == G2OHIP_V_SE3_EXPMAP) {  // the file holds cam2world (types_six_dof_expmap.cpp:93-101)
         double w[7];
         se3quat_inverse(v.est, w);
@@ -1347,6 +1364,30 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       ParsedVertex v{G2OHIP_V_XY, c.i(), {}};
       for (int k = 0; k < 2; ++k) v.est[k] = c.d();
       out.verts.push_back(v);
+    } else if (sba && tag == "VERTEX_CAM") {
+      // VertexCam::read (types_sba.cpp:74-112): x y z qx qy qz qw, then fx fy cx cy baseline or, when the line ends
+      // after the pose, the defaults 300 300 320 320 0.1. Any other length fails the load.
+      ParsedVertex v{G2OHIP_V_CAM, c.i(), {}};
+      int nv = 0;
+      while (c.ok && c.more()) {
+        const double x = c.d();
+        if (c.ok && nv < 12) v.est[nv] = x;
+        ++nv;
+      }
+      if (nv == 7) {
+        const double def[5] = {300, 300, 320, 320, 0.1};
+        std::memcpy(v.est + 7, def, sizeof def);
+      } else if (nv != 12) {
+        c.ok = false;
+      }
+      out.verts.push_back(v);
+    } else if (sba && (tag == "EDGE_PROJECT_P2MC" || tag == "EDGE_PROJECT_P2SC")) {
+      // types_sba.cpp:204-237: point, camera, the measurement; the information is the identity
+      const int D = tag == "EDGE_PROJECT_P2MC" ? 2 : 3;
+      ParsedEdge ed{D == 2 ? G2OHIP_E_PROJECT_P2MC : G2OHIP_E_PROJECT_P2SC, c.i(), c.i(), {}, {}, {}};
+      for (int k = 0; k < D; ++k) ed.m[k] = c.d();
+      for (int k = 0; k < D; ++k) ed.info[k * D + k] = 1.0;
+      out.edges.push_back(ed);
     } else if (tag == "FIX") {
       while (c.more()) {
         const int id = c.i();
@@ -1432,7 +1473,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
 
 int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0,
-             expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0;
+             expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0, sba = (flags & G2OHIP_LOAD_SBA) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1460,7 +1501,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
-      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, chunks[t]); });
+      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1541,6 +1582,18 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                   std::to_string(ed.b) + ": vertex " + std::to_string(id) +
                                                   " is missing or no VERTEX_SE3:EXPMAP");
         }
+      if (is_sba_type(ed.type)) {  // v0 a VERTEX_XYZ point, v1 a VERTEX_CAM
+        const char* tg = ed.type == G2OHIP_E_PROJECT_P2MC ? "EDGE_PROJECT_P2MC " : "EDGE_PROJECT_P2SC ";
+        auto ia = hg.idmap.find(ed.a), ib = hg.idmap.find(ed.b);
+        if (ia == hg.idmap.end() || hg.verts[ia->second].type != G2OHIP_V_XYZ)
+          throw StatusError(G2OHIP_ERR_ARG, std::string("g2o_hip load: ") + tg + std::to_string(ed.a) + " -> " +
+                                                std::to_string(ed.b) + ": vertex " + std::to_string(ed.a) +
+                                                " is missing or no VERTEX_XYZ");
+        if (ib == hg.idmap.end() || hg.verts[ib->second].type != G2OHIP_V_CAM)
+          throw StatusError(G2OHIP_ERR_ARG, std::string("g2o_hip load: ") + tg + std::to_string(ed.a) + " -> " +
+                                                std::to_string(ed.b) + ": vertex " + std::to_string(ed.b) +
+                                                " is missing or no VERTEX_CAM");
+      }
       if (is_slam3d_type(ed.type)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
         const bool cam = ed.type != G2OHIP_E_SE3_XYZ;
         auto po = offsets.find(ed.pid);
@@ -1651,7 +1704,7 @@ int Engine::save(const char* path) {
     for (size_t k = lo; k < hi; ++k) {
       const HVertex& v = hg.verts[k];
       const double* st = hg.st[v.type].data() + (size_t)v.local * vertex_state_stride(v.type);
-      double e[7], c[7];
+      double e[12], c[7];
       est_from_state(v.type, st, e);
       int ne = 3;
       switch (v.type) {
@@ -1660,6 +1713,7 @@ int Engine::save(const char* path) {
         case G2OHIP_V_SE3_QUAT: L.tag("VERTEX_SE3:QUAT"); ne = 7; break;
         case G2OHIP_V_SE2: L.tag("VERTEX_SE2"); break;
         case G2OHIP_V_XY: L.tag("VERTEX_XY"); ne = 2; break;
+        case G2OHIP_V_CAM: L.tag("VERTEX_CAM"); ne = 12; break;  // types_sba.cpp:114-131
       }
       L.i(v.id);
       for (int q = 0; q < ne; ++q) L.d(e[q]);
@@ -1706,6 +1760,10 @@ int Engine::save(const char* path) {
           L.tag("EDGE_SE3:EXPMAP"); L.i(a); L.i(b);
           for (int q = 0; q < 7; ++q) L.d(w[q]);
           for (int r = 0; r < 6; ++r) for (int q = r; q < 6; ++q) L.d(I[r * 6 + q]);
+        } else if (is_sba_type(es.type)) {  // types_sba.cpp:215-244: the measurement alone (g2ohip_save_g2o has
+                                            // refused a graph whose information is not the identity)
+          L.tag(es.type == G2OHIP_E_PROJECT_P2MC ? "EDGE_PROJECT_P2MC" : "EDGE_PROJECT_P2SC"); L.i(a); L.i(b);
+          for (int q = 0; q < nm; ++q) L.d(m[q]);
         } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
           L.tag("EDGE_SE2_XY"); L.i(a); L.i(b);
           L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
@@ -1825,7 +1883,7 @@ void Engine::sync_host_state() {
 }
 
 int Engine::get_estimates(int type, double* out, int* ids) {
-  if (type < 1 || type >= NVT) return G2OHIP_ERR_ARG;  // G2OHIP_V_XY (5) included: structure_only_2's landmarks
+  if (type < 1 || type >= NVT) return G2OHIP_ERR_ARG;  // every vertex type (G2OHIP_V_XY: structure_only_2's landmarks)
   sync_host_state();
   const int ed = vertex_est_dim(type), sd = vertex_state_stride(type);
   const auto& lst = hg.by_type[type];
@@ -1837,7 +1895,7 @@ int Engine::get_estimates(int type, double* out, int* ids) {
 }
 
 int Engine::set_estimates(int type, const double* est) {
-  if (type < 1 || type >= NVT) return G2OHIP_ERR_ARG;  // G2OHIP_V_XY (5) included: structure_only_2's landmarks
+  if (type < 1 || type >= NVT) return G2OHIP_ERR_ARG;  // every vertex type (G2OHIP_V_XY: structure_only_2's landmarks)
   sync_host_state();
   const int ed = vertex_est_dim(type), sd = vertex_state_stride(type);
   for (size_t k = 0; k < hg.by_type[type].size(); ++k) set_state_from_est(type, est + k * ed, hg.st[type].data() + k * sd);
@@ -1873,6 +1931,8 @@ static int family_of(int etype, int& vtA, int& vtB) {
     case G2OHIP_E_SE3_XYZ_DEPTH: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DEPTH;
     case G2OHIP_E_SE3_XYZ_DISPARITY: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DISPARITY;
     case G2OHIP_E_SE3_EXPMAP: vtA = vtB = G2OHIP_V_SE3_EXPMAP; return FAM_EXPMAP;
+    case G2OHIP_E_PROJECT_P2MC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_CAM; return FAM_SBA_MONO;
+    case G2OHIP_E_PROJECT_P2SC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_CAM; return FAM_SBA_STEREO;
     // unary types: vtB = 0 (no second vertex)
     case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
     case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
@@ -2256,6 +2316,8 @@ void Engine::fill_group_device(EGroup& g) {
     case FAM_EXPMAP: mmeas = 8; break;              // the measurement as an SE3Quat, padded to a 64-byte record
     case FAM_U_POSE_ONLY: mmeas = 5; break;         // u v | Xw
     case FAM_U_STEREO_POSE_ONLY: mmeas = 6; break;  // u_l v u_r | Xw
+    case FAM_SBA_MONO: mmeas = 2; break;
+    case FAM_SBA_STEREO: mmeas = 3; break;
   }
   // device parameter record: the BA intrinsics as given; slam3d: the inverse offset as an isometry (12), the camera
   // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
@@ -2306,6 +2368,8 @@ void Engine::fill_group_device(EGroup& g) {
       mo[2] = th;
     } else if (g.family == FAM_SE2XY) {
       mo[0] = m[0]; mo[1] = m[1];
+    } else if (is_sba_family(g.family)) {
+      for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
     } else if (g.family == FAM_EXPMAP) {  // SE3Quat(Vector7), se3quat.h:81-88: normalizeRotation (w >= 0, unit)
       double q[4] = {m[3], m[4], m[5], m[6]};
       const double sn = q[3] < 0 ? -1.0 : 1.0;
@@ -2340,15 +2404,15 @@ void Engine::fill_group_device(EGroup& g) {
      // record instead of 24 + 32 bytes per edge (G2OHIP_UNIFORM_RECORDS=0 keeps per-edge records, A/B)
     const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
     g.ue = 0;
-    if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family)) && gne > 1 &&
-        !(ev && atoi(ev) == 0)) {
+    if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family) ||
+         is_sba_family(g.family)) && gne > 1 && !(ev && atoi(ev) == 0)) {
       auto uniform = [&](const std::vector<double>& v, int st) {
         for (int k = 1; k < gne; ++k)
           if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
         return true;
       };
       if (uniform(info, minfo)) { g.ue |= 1; info.resize(minfo); }
-      if (uniform(params, mpar)) { g.ue |= 2; params.resize(mpar); }
+      if (mpar && uniform(params, mpar)) { g.ue |= 2; params.resize(mpar); }  // (the sba types have no record)
     }
   }
   g.info.upload(info, stream);
@@ -2799,6 +2863,12 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
         throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                           "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the slam3d "
                           "landmark edges (edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
+  if (use_cgls())
+    for (const HEdgeSet& es : hg.esets)
+      if (is_sba_type(es.type) && !es.ev0.empty())
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the sba types on "
+                          "a VertexCam (edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
   if (use_cgls())
     for (const HEdgeSet& es : hg.esets)
       if (es.type == G2OHIP_E_SE3_EXPMAP && !es.ev0.empty())
@@ -3833,6 +3903,10 @@ void Engine::update_async(const double* x) {  // sparse_optimizer.cpp:441-454
   for (int t = 1; t < NVT; ++t) {
     const int n = (int)hg.by_type[t].size();
     if (!n) continue;
+    if (L.cnt == 5) {  // the list is full (a graph with every vertex type): a launch of its own for the rest
+      launch::oplus_multi(L, x ? x : dx.get(), stream);
+      L.cnt = 0;
+    }
     L.vt[L.cnt] = t;
     L.n[L.cnt] = n;
     L.xoff[L.cnt] = d_xoff[t].get();
@@ -3879,6 +3953,10 @@ int Engine::push_set_lambda(bool with_lambda, double lam) {
   launch::CopyList cl{};
   for (int t = 1; t < NVT; ++t) {
     if (!dstate[t].size()) continue;
+    if (cl.n == 4) {  // the list is full: the rest goes in a launch of its own
+      launch::copy_multi(cl, stream);
+      cl.n = 0;
+    }
     lvl[t].resize(dstate[t].size());
     cl.src[cl.n] = dstate[t].get();
     cl.dst[cl.n] = lvl[t].get();
@@ -3899,6 +3977,10 @@ int Engine::pop() {
   launch::CopyList cl{};
   for (int t = 1; t < NVT; ++t)
     if (lvl[t].size()) {
+      if (cl.n == 4) {
+        launch::copy_multi(cl, stream);
+        cl.n = 0;
+      }
       cl.src[cl.n] = lvl[t].get();
       cl.dst[cl.n] = dstate[t].get();
       cl.len[cl.n++] = (long long)lvl[t].size();
@@ -4691,6 +4773,10 @@ double Engine::kernel_bytes(const std::string& name) const {
         // parameter record 12 / 16 (likewise), two vertex indices, the pose slot 27, the point slot 9, the Hpl block
         const int np = g.family == FAM_SE3_XYZ ? 12 : 16;
         by += g.ne * ((3 + ((g.ue & 1) ? 0 : 6) + ((g.ue & 2) ? 0 : np)) * 8.0 + 8 + (27.0 + 9.0) * 8 + pb);
+      } else if (is_sba_family(g.family)) {
+        // sba types (slot path): measurement D + packed information (one record when uniform), two vertex indices, the
+        // point slot 9, the camera slot 27, the Hpl block
+        by += g.ne * ((g.D + ((g.ue & 1) ? 0 : g.D * (g.D + 1) / 2)) * 8.0 + 8 + (9.0 + 27.0) * 8 + pb);
       }
     return by;
   }
@@ -4707,7 +4793,7 @@ double Engine::kernel_bytes(const std::string& name) const {
       by += g.ne * (8.0 + (g.vtB ? 4.0 : 0.0) + g.D * 8.0 + ((g.ue & 1) ? 0.0 : g.D * (g.D + 1) / 2 * 8.0) +
                     ((g.ue & 2) ? 0.0 : np * 8.0));
     }
-    for (int t : {G2OHIP_V_SE3_EXPMAP, G2OHIP_V_SE3_QUAT, G2OHIP_V_SE2}) by += dstate[t].bytes();
+    for (int t : {G2OHIP_V_SE3_EXPMAP, G2OHIP_V_SE3_QUAT, G2OHIP_V_SE2, G2OHIP_V_CAM}) by += dstate[t].bytes();
     return by;
   }
   if (name == "backsub") return local_lm.size() * (3 * 8.0 * 2 + 72) + npl * (pb + 4) + size_poses * 8.0;

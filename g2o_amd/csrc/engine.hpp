@@ -21,7 +21,7 @@
 
 namespace g2ohip {
 
-constexpr int NVT = 6;  // vertex type codes 1..5 (G2OHIP_V_*)
+constexpr int NVT = 7;  // vertex type codes 1..6 (G2OHIP_V_*)
 int vertex_dim(int vtype);
 int vertex_est_dim(int vtype);
 int vertex_state_stride(int vtype);

@@ -1282,6 +1282,23 @@ __device__ __forceinline__ void d_oplus_xy(int v, const int* __restrict__ xoff, 
   s[1] += u[1];
 }
 
+// VertexCam: SBACam::update (sbacam.h:95-111): t += u[0:3]; q = q * (u[3:6], sqrt(1 - |u[3:6]|^2)), normalised. No sign
+// flip of w and no identity fallback: for |u[3:6]|^2 > 1 the square root is NaN and so is the rotation, as in the
+// reference. The intrinsics behind the pose (state[7:12]) are left as they are.
+__device__ __forceinline__ void d_oplus_cam(int v, const int* __restrict__ xoff, const double* __restrict__ x,
+                                            double* __restrict__ st, int* __restrict__ nopl) {
+  if (xoff[v] < 0) return;
+  const double* u = x + xoff[v];
+  double* s = st + (size_t)v * 12;
+  const double q[4] = {s[3], s[4], s[5], s[6]};
+  const double qr[4] = {u[3], u[4], u[5], sqrt(1.0 - (u[3] * u[3] + u[4] * u[4] + u[5] * u[5]))};
+  double qn[4];
+  qmul(q, qr, qn);  // post-multiply
+  const double n = sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
+  s[0] += u[0]; s[1] += u[1]; s[2] += u[2];
+  s[3] = qn[0] / n; s[4] = qn[1] / n; s[5] = qn[2] / n; s[6] = qn[3] / n;
+}
+
 // SparseOptimizer::update (sparse_optimizer.cpp:441-454) over every vertex type in one launch: block ranges per type
 __global__ void __launch_bounds__(256) k_oplus_multi(launch::OplusList L, const double* __restrict__ x) {
   int t = 0;
@@ -1294,6 +1311,7 @@ __global__ void __launch_bounds__(256) k_oplus_multi(launch::OplusList L, const 
     case 3: d_oplus_se3quat(v, L.xoff[t], x, L.st[t], L.nopl); break;
     case 4: d_oplus_se2(v, L.xoff[t], x, L.st[t], L.nopl); break;
     case 5: d_oplus_xy(v, L.xoff[t], x, L.st[t], L.nopl); break;
+    case 6: d_oplus_cam(v, L.xoff[t], x, L.st[t], L.nopl); break;
   }
 }
 
@@ -1841,6 +1859,8 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_SE3_XYZ_DEPTH: fn(FamilySE3XYZDepth{}); break;
     case FAM_SE3_XYZ_DISPARITY: fn(FamilySE3XYZDisparity{}); break;
     case FAM_EXPMAP: fn(FamilyExpmap{}); break;
+    case FAM_SBA_MONO: fn(FamilySBAMono{}); break;
+    case FAM_SBA_STEREO: fn(FamilySBAStereo{}); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;

@@ -13,6 +13,8 @@ enum Family {
   FAM_SE3_XYZ = 7, FAM_SE3_XYZ_DEPTH = 8, FAM_SE3_XYZ_DISPARITY = 9,
   // EdgeSE3Expmap between two VertexSE3Expmap cameras
   FAM_EXPMAP = 10,
+  // sba types (point, VertexCam): EdgeProjectP2MC, EdgeProjectP2SC
+  FAM_SBA_MONO = 11, FAM_SBA_STEREO = 12,
   // unary families (BaseUnaryEdge: one vertex, EdgeArgs::v1 / s1 null, DB = 0)
   FAM_U_SE2 = 16, FAM_U_SE2XY = 17, FAM_U_XY = 18, FAM_U_SE3 = 19, FAM_U_XYZ = 20, FAM_U_HOSTJ = 21,
   // pose-only projections on a VertexSE3Expmap camera: EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose
@@ -22,6 +24,7 @@ inline bool is_unary_family(int f) { return f >= FAM_U_SE2 && f <= FAM_U_STEREO_
 inline bool is_pose_only_family(int f) { return f == FAM_U_POSE_ONLY || f == FAM_U_STEREO_POSE_ONLY; }
 inline bool is_hostj_family(int f) { return f == FAM_HOSTJ || f == FAM_U_HOSTJ; }
 inline bool is_slam3d_family(int f) { return f >= FAM_SE3_XYZ && f <= FAM_SE3_XYZ_DISPARITY; }
+inline bool is_sba_family(int f) { return f == FAM_SBA_MONO || f == FAM_SBA_STEREO; }
 
 struct EdgeArgs {
   const int* v0;

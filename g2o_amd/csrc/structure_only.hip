@@ -139,6 +139,38 @@ template <> struct PointEdge<FAM_SE3_XYZ> : PointSlam3d<SLAM3D_XYZ> {};
 template <> struct PointEdge<FAM_SE3_XYZ_DEPTH> : PointSlam3d<SLAM3D_DEPTH> {};
 template <> struct PointEdge<FAM_SE3_XYZ_DISPARITY> : PointSlam3d<SLAM3D_DISPARITY> {};
 
+template <bool STEREO>
+struct PointSBA {  // FamilySBA<STEREO>::linearize_at, the point's Jacobian alone
+  static constexpr int D = STEREO ? 3 : 2, LD = 3;
+  using F = FamilySBA<STEREO>;
+  template <bool JAC>
+  DI static void eval(const SoGroup& g, int e, const double* p, double* err, double* A) {
+    const double* cp = g.so + (size_t)g.vo[e] * 12;
+    const double* mp = g.meas + (size_t)e * D;
+    double c[12], m[D], Rt[9], pc[3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) c[k] = cp[k];
+#pragma unroll
+    for (int k = 0; k < D; ++k) m[k] = mp[k];
+    F::to_camera(c, p, Rt, pc);
+    F::residual(c, pc, m, err);
+    if (JAC) {
+      const double ipz2 = 1.0 / (pc[2] * pc[2]);
+      const double fx2 = ipz2 * c[7], fy2 = ipz2 * c[8];
+      const double xs = pc[0] - c[11];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double dx = Rt[k], dy = Rt[3 + k], dz = Rt[6 + k];
+        A[k] = (pc[2] * dx - pc[0] * dz) * fx2;
+        A[3 + k] = (pc[2] * dy - pc[1] * dz) * fy2;
+        if (STEREO) A[6 + k] = (pc[2] * dx - xs * dz) * fx2;
+      }
+    }
+  }
+};
+template <> struct PointEdge<FAM_SBA_MONO> : PointSBA<false> {};
+template <> struct PointEdge<FAM_SBA_STEREO> : PointSBA<true> {};
+
 template <>
 struct PointEdge<FAM_SE2XY> {  // FamilySE2XY::linearize, Jj
   static constexpr int D = 2, LD = 2;
@@ -241,6 +273,8 @@ DI void edge_any(const SoGroup* groups, int2 en, const double* p, double& chi, d
       case FAM_SE3_XYZ: edge_term<FAM_SE3_XYZ, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_SE3_XYZ_DEPTH: edge_term<FAM_SE3_XYZ_DEPTH, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_SE3_XYZ_DISPARITY: edge_term<FAM_SE3_XYZ_DISPARITY, JAC>(g, en.y, p, chi, H, b); break;
+      case FAM_SBA_MONO: edge_term<FAM_SBA_MONO, JAC>(g, en.y, p, chi, H, b); break;
+      case FAM_SBA_STEREO: edge_term<FAM_SBA_STEREO, JAC>(g, en.y, p, chi, H, b); break;
       default: edge_term<FAM_U_XYZ, JAC>(g, en.y, p, chi, H, b); break;
     }
   } else {

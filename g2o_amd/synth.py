@@ -21,6 +21,8 @@ Recipes:
     EDGE_SE3:EXPMAP odometry and loop closures).
   * ``pose_only`` / ``with_pose_only`` - pose optimisation: cameras observing points held in the edges
     (EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose), alone or beside a BA problem's edges.
+  * ``sba``     - the scene of ``ba`` in the sba vocabulary of ``g2o/examples/sba/sba_demo.cpp`` (VERTEX_CAM cameras
+    holding their intrinsics, VERTEX_XYZ points, EDGE_PROJECT_P2MC or EDGE_PROJECT_P2SC).
   * ``slam3d_landmarks`` - 3D SLAM with landmarks (VERTEX_SE3:QUAT poses with EDGE_SE3:QUAT odometry, VERTEX_TRACKXYZ
     points seen through EDGE_SE3_TRACKXYZ / EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY), the shape of
     g2o_simulator3d's output.
@@ -37,6 +39,8 @@ SEED = 20261015
 
 # vertex / edge type codes (include/g2o_hip.h)
 V_SE3_EXPMAP, V_XYZ, V_SE3_QUAT, V_SE2, V_XY = 1, 2, 3, 4, 5
+# VertexCam (types_sba): x y z qx qy qz qw (camera-to-world) fx fy cx cy baseline
+V_CAM = 6
 E_SE3_PROJECT_XYZ, E_SE3_QUAT, E_SE2, E_SE2_XY = 1, 2, 3, 5
 E_STEREO_SE3_PROJECT_XYZ = 6
 # slam3d landmark edges: v0 a V_SE3_QUAT pose, v1 a V_XYZ point
@@ -47,15 +51,19 @@ E_SE2_PRIOR, E_SE2_XY_PRIOR, E_XY_PRIOR, E_SE3_PRIOR, E_XYZ_PRIOR = 16, 17, 18, 
 # Xw fx fy cx cy, stereo + bf)
 E_SE3_EXPMAP = 10
 E_SE3_PROJECT_XYZ_ONLYPOSE, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE = 21, 22
-EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2}
+# the sba types: v0 a V_XYZ point, v1 a V_CAM camera; no params (the intrinsics live in the vertex)
+E_PROJECT_P2MC, E_PROJECT_P2SC = 11, 12
+EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
             E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
-            E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3}
+            E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
+            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
-           E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3}
+           E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
+           E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3}
 # the vertex type a unary edge type attaches to
 PRIOR_VERTEX = {E_SE2_PRIOR: V_SE2, E_SE2_XY_PRIOR: V_SE2, E_XY_PRIOR: V_XY, E_SE3_PRIOR: V_SE3_QUAT, E_XYZ_PRIOR: V_XYZ}
 # the same for the pose-only projections, and the binary projection each of them is the pose-only form of
@@ -508,6 +516,49 @@ def ba_stereo(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point:
         edges.append(EdgeSet(E_SE3_PROJECT_XYZ, mono.v0[~st].copy(), mono.v1[~st].copy(), mono.meas[~st].copy(),
                              mono.info[~st].copy(), mono.params[~st].copy()))
     return Problem(prob.name + f"_stereo{stereo_fraction:g}", prob.vertices, edges, 6, 3)
+
+
+def sba(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point: int = 10, window: int = 64,
+        stereo: bool = False, pixel_noise: float = 1.0, cam_rot_noise: float = 0.002, cam_trans_noise: float = 0.01,
+        point_noise: float = 0.05, fixed_cameras: int | None = None, seed: int = SEED, baseline: float = 0.1,
+        disparity_noise: float = 1.0) -> Problem:
+    """The scene of :func:`ba` in the sba types: V_CAM cameras (the camera-to-world inverse of ba()'s estimates, with
+    fx fy cx cy and ``baseline`` in the vertex), the same points and left-image measurements, observed through
+    EdgeProjectP2MC or, with ``stereo``, EdgeProjectP2SC (u_r = u_true - fx * baseline / z_true + noise, the noise from
+    an rng stream of its own).  Omega = I.  Two cameras are fixed for monocular graphs, one for stereo ones (a stereo
+    rig observes the scale), unless ``fixed_cameras`` says otherwise."""
+    nf = (1 if stereo else 2) if fixed_cameras is None else fixed_cameras
+    prob, pc, uv_true = _ba_scene(num_cameras, num_points, obs_per_point, window, pixel_noise, cam_rot_noise,
+                                  cam_trans_noise, point_noise, nf, seed)
+    cams, pts = prob.vertices
+    mono = prob.edges[0]
+    fx, fy, cx, cy = mono.params[0]
+    # world->cam (t, q) -> cam->world: R^T, -R^T t
+    Rcw = np.transpose(quat_to_rot(cams.est[:, 3:7]), (0, 2, 1))
+    tcw = -np.einsum("nij,nj->ni", Rcw, cams.est[:, 0:3])
+    C = len(cams.ids)
+    est = np.concatenate([tcw, rot_to_quat(Rcw), np.broadcast_to([fx, fy, cx, cy, float(baseline)], (C, 5))], axis=1)
+    cams_v = VertexSet(V_CAM, cams.ids, est, cams.fixed, cams.marginalized)
+    m = len(mono.v0)
+    if stereo:
+        ur = uv_true[:, 0] - fx * baseline / pc[:, 2] + _rng(seed, 5).standard_normal(m) * disparity_noise
+        meas = np.stack([mono.meas[:, 0], mono.meas[:, 1], ur], axis=1)
+        edges = EdgeSet(E_PROJECT_P2SC, mono.v0, mono.v1, meas, np.broadcast_to(np.eye(3), (m, 3, 3)).copy(), None)
+    else:
+        edges = EdgeSet(E_PROJECT_P2MC, mono.v0, mono.v1, mono.meas, mono.info, None)
+    return Problem("s" + prob.name + ("_stereo" if stereo else ""), [cams_v, pts], [edges], 6, 3)
+
+
+def sba_twin(prob: Problem) -> Problem:
+    """The host-Jacobian twin of a graph with sba edges: every E_PROJECT_P2MC / E_PROJECT_P2SC set as an E_HOSTJ(2) /
+    E_HOSTJ(3) set (32 + D) between the same vertices with the same information; the caller supplies the payload."""
+    edges = []
+    for es in prob.edges:
+        if es.etype in (E_PROJECT_P2MC, E_PROJECT_P2SC):
+            edges.append(EdgeSet(32 + ERR_DIM[es.etype], es.v0.copy(), es.v1.copy(), None, es.info.copy(), None))
+        else:
+            edges.append(es)
+    return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)
 
 
 def by_name(name: str, scale: str = "full") -> Problem:

@@ -37,6 +37,15 @@ extern "C" {
 #define G2OHIP_V_SE3_QUAT 3   /* VertexSE3, vertex_se3.h:50: x y z qx qy qz qw (toVectorQT) */
 #define G2OHIP_V_SE2 4        /* VertexSE2, vertex_se2.h:40: x y theta */
 #define G2OHIP_V_XY 5         /* VertexPointXY, vertex_point_xy.h:39-88: x y (a BlockSolver_3_2 landmark) */
+#define G2OHIP_V_CAM 6        /* VertexCam, types_sba.h:71-130: an SBACam (sbacam.h:55-175), dimension 6. The estimate is
+                                 the VERTEX_CAM line, 12 doubles: x y z qx qy qz qw fx fy cx cy baseline, t the camera
+                                 position in the world and q camera-to-world; g2ohip_add_vertices, g2ohip_get_estimates
+                                 and g2ohip_set_estimates take and give 12 per vertex. On entry q is normalised to
+                                 unit length with w >= 0 (VertexCam::read, SE3Quat(q, t)). g2ohip_minimal_state gives
+                                 x y z qx qy qz (toMinimalVector, no sign change). oplus is SBACam::update: t += u[0:3],
+                                 q = q * (u[3:6], sqrt(1 - |u[3:6]|^2)), normalised; no sign flip of w, no identity
+                                 fallback: for |u[3:6]|^2 > 1 the square root and with it the rotation are NaN, as in
+                                 the reference (the LM / GN / dogleg decisions reject the non-finite chi2) */
 /* ---- edge types ---- */
 #define G2OHIP_E_SE3_PROJECT_XYZ 1 /* EdgeSE3ProjectXYZ, types_six_dof_expmap.h:201-229: v0 point, v1 camera;
                                       meas u v; info 2x2; params fx fy cx cy */
@@ -70,6 +79,19 @@ extern "C" {
                                   log(Tj^-1 * C * Ti); the Jacobians are the reference's adjoints (.cpp:278-293), exact
                                   at zero error only. Generic slot path; lm_pcg6_3_eigen refuses a graph that holds
                                   these edges (g2ohip_last_error says so) */
+/* The sba types on a VertexCam (types_sba.h:173-250, what sba_demo builds): v0 the point (G2OHIP_V_XYZ), v1 the camera
+ * (G2OHIP_V_CAM); params must be NULL (the intrinsics and the baseline live in the vertex; non-NULL is G2OHIP_ERR_ARG).
+ * With pc = R^T (pw - t) the error is projected minus measured, the opposite sign of the expmap projections; the
+ * Jacobians are the reference's analytic ones (types_sba.cpp:249-403), exact first derivatives under the vertex's
+ * oplus. Robust kernels, edge levels, g2ohip_edge_chi2 and g2ohip_classify_edges take them like any device type; the
+ * reference types have no isDepthPositive, so depth_positive != NULL or check_depth is G2OHIP_ERR_ARG. Generic slot
+ * path with the 6/3 Schur kernels; lm_pcg6_3_eigen refuses a graph that holds them (g2ohip_last_error says so).
+ * EdgeSBACam and EdgeSBAScale, which have no analytic Jacobian in the reference, enter as G2OHIP_E_HOSTJ(6) /
+ * G2OHIP_E_HOSTJ(1) between G2OHIP_V_CAM vertices. */
+#define G2OHIP_E_PROJECT_P2MC 11 /* EdgeProjectP2MC (EDGE_PROJECT_P2MC): meas u v; info 2x2;
+                                    e = (fx pc.x / pc.z + cx - u, fy pc.y / pc.z + cy - v) */
+#define G2OHIP_E_PROJECT_P2SC 12 /* EdgeProjectP2SC (EDGE_PROJECT_P2SC): meas u v u_r; info 3x3; rows 0-1 as
+                                    G2OHIP_E_PROJECT_P2MC, e2 = fx (pc.x - baseline) / pc.z + cx - u_r */
 /* An edge type the device does not know (any BaseBinaryEdge<D, E, Vi, Vj> between registered vertices of
  * dimension 2, 3 or 6): the host's own linearizeOplus (the type's analytic one, or BaseBinaryEdge's numeric
  * central differences, base_binary_edge.hpp:198-266) supplies the error and both Jacobians, see
@@ -190,6 +212,13 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * is skipped like any unknown one. The pose-only projection tags (EDGE_SE3_PROJECT_XYZONLYPOSE:EXPMAP,
  * EDGE_STEREO_SE3_PROJECT_XYZONLYPOSE:EXPMAP) are always skipped: see G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE. */
 #define G2OHIP_LOAD_EXPMAP 4u
+/* G2OHIP_LOAD_SBA (may be combined with the other flags): VERTEX_CAM id and 12 values loads as G2OHIP_V_CAM; a line
+ * with exactly 7 values takes the reference's defaults 300 300 320 320 0.1 for fx fy cx cy baseline (VertexCam::read,
+ * types_sba.cpp:74-112); any other length fails the load, g2ohip_last_error naming the tag. EDGE_PROJECT_P2MC v0 v1 u v
+ * and EDGE_PROJECT_P2SC v0 v1 u v u_r load as G2OHIP_E_PROJECT_P2MC / _P2SC with identity information (the reference
+ * reads none); an endpoint that is missing or of the wrong type fails the load. Without the flag the three tags are
+ * skipped like any unknown one. */
+#define G2OHIP_LOAD_SBA 8u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
@@ -199,7 +228,11 @@ int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, u
  * per distinct record, in one id space with the prior offsets; a G2OHIP_V_XYZ vertex one of these edges touches is
  * written as VERTEX_TRACKXYZ. G2OHIP_E_SE3_EXPMAP edges are written as EDGE_SE3:EXPMAP with the inverse of the
  * measurement and the upper triangle of the information (types_six_dof_expmap.cpp:131-140). A graph holding pose-only
- * projection edges is not written: G2OHIP_ERR_UNSUPPORTED, as for G2OHIP_E_STEREO_SE3_PROJECT_XYZ. */
+ * projection edges is not written: G2OHIP_ERR_UNSUPPORTED, as for G2OHIP_E_STEREO_SE3_PROJECT_XYZ. G2OHIP_V_CAM
+ * vertices are written as VERTEX_CAM with their 12 values, G2OHIP_E_PROJECT_P2MC / _P2SC as EDGE_PROJECT_P2MC /
+ * EDGE_PROJECT_P2SC with the measurement alone (types_sba.cpp:114-131, 215-244); the points they touch stay
+ * VERTEX_XYZ. These lines cannot carry an information matrix: a graph holding such an edge whose information is not
+ * the identity is not written (G2OHIP_ERR_UNSUPPORTED, nothing written). */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
