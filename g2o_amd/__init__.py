@@ -59,6 +59,14 @@ V_CAM = 6
 E_PROJECT_P2MC, E_PROJECT_P2SC = 11, 12
 
 
+# offset and bearing edges (include/g2o_hip.h G2OHIP_E_SE3_OFFSET, _SE2_OFFSET, _SE2_XY_BEARING): EdgeSE3Offset between
+# two V_SE3_QUAT (meas x y z qx qy qz qw, params [n, 14]: the from vertex's offset, then the to vertex's, or None),
+# EdgeSE2Offset between two V_SE2 (meas x y theta, params [n, 6] or None), EdgeSE2PointXYBearing from a V_SE2 pose to a
+# V_XY point (meas one angle, info 1x1, params None); EDGE_TAGS: their .g2o tags
+E_SE3_OFFSET, E_SE2_OFFSET, E_SE2_XY_BEARING = 13, 14, 15
+EDGE_TAGS = {E_SE3_OFFSET: "EDGE_SE3_OFFSET", E_SE2_OFFSET: "EDGE_SE2_OFFSET", E_SE2_XY_BEARING: "EDGE_BEARING_SE2_XY"}
+
+
 # edge types the device does not know: host-supplied error + Jacobians (include/g2o_hip.h G2OHIP_E_HOSTJ)
 def E_HOSTJ(D: int) -> int:
     return 32 + D
@@ -83,6 +91,7 @@ LOAD_UNARY = 1
 LOAD_SLAM3D = 2
 LOAD_EXPMAP = 4
 LOAD_SBA = 8
+LOAD_OFFSET = 16
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -391,6 +400,10 @@ class SparseOptimizer:
         meas = None if es.meas is None else np.ascontiguousarray(es.meas, np.float64)
         info = np.ascontiguousarray(es.info, np.float64)
         par = None if es.params is None else np.ascontiguousarray(es.params, np.float64)
+        pd = synth.PARAM_DIM.get(es.etype)
+        if par is not None and pd is not None and par.size != len(v0) * pd:  # the C side reads n * pd doubles
+            raise G2OHipError(f"add_edges: edge type {es.etype} takes {pd} parameter values per edge, got {par.size} "
+                              f"for {len(v0)} edges")
         _check(lib().g2ohip_add_edges(self.h, es.etype, len(v0), _p(v0), _p(v1), _p(meas), _p(info), _p(par)),
                "add_edges")
 
@@ -442,14 +455,15 @@ class SparseOptimizer:
         _check(lib().g2ohip_set_estimates(self.h, vtype, _p(est)), "set_estimates")
 
     def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False,
-             expmap: bool = False, sba: bool = False):
+             expmap: bool = False, sba: bool = False, offset: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
         EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
         (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
         PARAMS_CAMERACALIB), expmap=True EDGE_SE3:EXPMAP, sba=True the sba tags (VERTEX_CAM, EDGE_PROJECT_P2MC,
-        EDGE_PROJECT_P2SC); all are skipped otherwise."""
+        EDGE_PROJECT_P2SC), offset=True the offset and bearing tags (EDGE_SE3_OFFSET, EDGE_SE2_OFFSET,
+        EDGE_BEARING_SE2_XY + PARAMS_SE3OFFSET, PARAMS_SE2OFFSET); all are skipped otherwise."""
         flags = ((LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0) |
-                 (LOAD_SBA if sba else 0))
+                 (LOAD_SBA if sba else 0) | (LOAD_OFFSET if offset else 0))
         _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:

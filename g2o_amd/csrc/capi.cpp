@@ -107,7 +107,8 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
   return guarded([&] { return g->e->load(path, marginalize_xyz); });
 }
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
-  if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP | G2OHIP_LOAD_SBA))) return G2OHIP_ERR_ARG;
+  if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP | G2OHIP_LOAD_SBA |
+                                    G2OHIP_LOAD_OFFSET))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {

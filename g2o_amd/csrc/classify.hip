@@ -129,6 +129,9 @@ void classify(int family, const EdgeArgs& a, int ne, const ClassifyArgs& c, hipS
     case FAM_EXPMAP: classify_launch<FamilyExpmap>(d, ne, c, s); break;
     case FAM_SBA_MONO: classify_launch<FamilySBAMono>(d, ne, c, s); break;
     case FAM_SBA_STEREO: classify_launch<FamilySBAStereo>(d, ne, c, s); break;
+    case FAM_SE3_OFFSET: classify_launch<FamilySE3Offset>(d, ne, c, s); break;
+    case FAM_SE2_OFFSET: classify_launch<FamilySE2Offset>(d, ne, c, s); break;
+    case FAM_SE2XY_BEARING: classify_launch<FamilySE2XYBearing>(d, ne, c, s); break;
     case FAM_U_SE2: classify_launch<FamilyUnarySE2>(d, ne, c, s); break;
     case FAM_U_SE2XY: classify_launch<FamilyUnarySE2XY>(d, ne, c, s); break;
     case FAM_U_XY: classify_launch<FamilyUnaryXY>(d, ne, c, s); break;

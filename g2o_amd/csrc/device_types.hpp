@@ -8,6 +8,9 @@
 //   EdgeSE3PointXYZ, ...Depth, ...Disparity  types/slam3d/edge_se3_pointxyz.cpp:100-135 and its two siblings
 //   EdgeSE3Expmap      types/sba/types_six_dof_expmap.h:117-124, .cpp:278-293, slam3d/se3quat.h:99-130, 173-210, 259-268
 //   EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose  types_six_dof_expmap.h:242-246, 303-307, .cpp:569-665
+//   EdgeSE3Offset      types/slam3d/edge_se3_offset.cpp:102-132, isometry3d_gradients.h:84-189 (the Pi / Pj overload)
+//   EdgeSE2Offset      types/slam2d/edge_se2_offset.cpp:102-106, parameter_se2_offset.cpp:76-86 (no analytic Jacobian)
+//   EdgeSE2PointXYBearing  types/slam2d/edge_se2_pointxy_bearing.h:43-50 (no analytic Jacobian)
 //   unary priors       types/slam2d/edge_se2_prior.h:39-77, edge_se2_xyprior.h:39-71, edge_xy_prior.h,
 //                      types/slam3d/edge_se3_prior.cpp:89-102 (isometry3d_gradients.h:265-325), edge_xyz_prior.cpp:63-70
 //   oplus             types_six_dof_expmap.h:97-100 (SE3Quat::exp * T, se3quat.h:217-257),
@@ -881,6 +884,259 @@ struct FamilySBA {
 };
 using FamilySBAMono = FamilySBA<false>;
 using FamilySBAStereo = FamilySBA<true>;
+
+// ---- EdgeSE3Offset (types/slam3d/edge_se3_offset.cpp:102-132, CacheSE3Offset::updateImpl parameter_se3_offset.cpp,
+// isometry3d_gradients.h:84-189): a pose constraint between the sensor frames Xi Pi and Xj Pj. meas payload = Z^-1 [12]
+// (as FamilySE3), info packed upper 21, parameter record [Pi (12) | Pj (12)], both isometries made on the host (one
+// shared record when EdgeData::ue bit 1 is set). error = toVectorMQT((Z^-1 * w2n_i) * n2w_j) with n2w = X P and
+// w2n = n2w^-1, computeError's association. Jacobians: the Pi / Pj overload of computeEdgeSE3Gradient, its
+// non-__clang__ branch (Ra * Sxt, Ra * Syt, Ra * Szt; the __clang__ branch multiplies Sxt by Rab), which is what
+// FamilySE3 restates for identity offsets. With A = Z^-1 Pi^-1, B = Xi^-1 Xj, C = Pj, E = A B C:
+//   dte/dti = -Ra, dte/dtj = Rab, dte/dqi = Ra skewT(t_bc), dte/dqj = Rab skew(t_c),
+//   dre/dqi = dq_dR(Re) [Ra skewT(Rbc)], dre/dqj = dq_dR(Re) [Rab skew(Rc)].
+// The work is ordered so that the temporaries of one part are dead before the next starts: the error first, then the
+// translation rows, then the rotation rows, which alone need dq_dR. ----
+struct FamilySE3Offset {
+  static constexpr int D = 6, DA = 6, DB = 6, MEAS = 12, INFO = 21, PAR = 24;
+  // the record of a group whose records are all equal is read at a wave-uniform address (scalar loads where the
+  // compiler takes them)
+  DI static void load_par(const EdgeData& d, int e, double* Pi, double* Pj) {
+    if (d.ue & 2) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) { Pi[k] = d.params[k]; Pj[k] = d.params[12 + k]; }
+    } else {
+      const double* p = d.params + (size_t)e * PAR;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) { Pi[k] = p[k]; Pj[k] = p[12 + k]; }
+    }
+  }
+  DI static void load(const EdgeData& d, int e, double* Xi, double* Xj, double* Zi) {
+    const double* xi = d.s0 + (size_t)d.v0[e] * 12;
+    const double* xj = d.s1 + (size_t)d.v1[e] * 12;
+    const double* zi = d.meas + (size_t)e * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { Xi[k] = xi[k]; Xj[k] = xj[k]; Zi[k] = zi[k]; }
+  }
+  DI static void error_of(const double* Xi, const double* Xj, const double* Zi, const double* Pi, const double* Pj,
+                          double* err) {
+    double N[12], W[12], T[12];
+    iso_mul(Xi, Pi, N);  // n2w_i
+    iso_inv(N, W);       // w2n_i
+    iso_mul(Zi, W, T);
+    iso_mul(Xj, Pj, N);  // n2w_j
+    iso_mul(T, N, W);    // delta
+    err[0] = W[9]; err[1] = W[10]; err[2] = W[11];
+    compact_quat(W, err + 3);
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double Xi[12], Xj[12], Zi[12], Pi[12], Pj[12];
+    load(d, e, Xi, Xj, Zi);
+    load_par(d, e, Pi, Pj);
+    error_of(Xi, Xj, Zi, Pi, Pj, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    double Xi[12], Xj[12], A[12], Pi[12], Pj[12];  // A holds Z^-1 until the error is done
+    load(d, e, Xi, Xj, A);
+    load_par(d, e, Pi, Pj);
+    error_of(Xi, Xj, A, Pi, Pj, err);
+    double AB[12], BC[12];
+    {
+      double T[12], B[12];
+      iso_inv(Pi, T);
+      iso_mul(A, T, B);
+#pragma unroll
+      for (int k = 0; k < 12; ++k) A[k] = B[k];  // A = Z^-1 Pi^-1
+      iso_inv(Xi, T);
+      iso_mul(T, Xj, B);  // B = Xi^-1 Xj
+      iso_mul(A, B, AB);
+      iso_mul(B, Pj, BC);
+    }
+    const double* Ra = A;
+    const double* Rab = AB;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) { Ji[k] = 0; Jj[k] = 0; }
+    // ---- translation rows
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        Ji[r * 6 + c] = -Ra[r * 3 + c];
+        Jj[r * 6 + c] = Rab[r * 3 + c];
+      }
+    {  // dte/dqi = Ra * skewT(t_bc)
+      const double X = 2 * BC[9], Y = 2 * BC[10], Z = 2 * BC[11];
+      const double S[9] = {0, -Z, Y, Z, 0, -X, -Y, X, 0};
+      double M[9];
+      mat3mul(Ra, S, M);
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Ji[r * 6 + 3 + c] = M[r * 3 + c];
+    }
+    {  // dte/dqj = Rab * skew(t_c)
+      const double x = 2 * Pj[9], y = 2 * Pj[10], z = 2 * Pj[11];
+      const double S[9] = {0, z, -y, -z, 0, x, y, -x, 0};
+      double M[9];
+      mat3mul(Rab, S, M);
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Jj[r * 6 + 3 + c] = M[r * 3 + c];
+    }
+    // ---- rotation rows
+    double dq[27];
+    {
+      double Re[9];
+      mat3mul(Rab, Pj, Re);  // E = AB C
+      dq_dR(Re, dq);
+    }
+    {  // dre/dqi = dq * [vec(Ra*Sxt) vec(Ra*Syt) vec(Ra*Szt)], skewT of Rbc
+      const double r11 = 2 * BC[0], r12 = 2 * BC[1], r13 = 2 * BC[2];
+      const double r21 = 2 * BC[3], r22 = 2 * BC[4], r23 = 2 * BC[5];
+      const double r31 = 2 * BC[6], r32 = 2 * BC[7], r33 = 2 * BC[8];
+      const double Sx[9] = {0, 0, 0, r31, r32, r33, -r21, -r22, -r23};
+      const double Sy[9] = {-r31, -r32, -r33, 0, 0, 0, r11, r12, r13};
+      const double Sz[9] = {r21, r22, r23, -r11, -r12, -r13, 0, 0, 0};
+      double Mx[9], My[9], Mz[9];
+      mat3mul(Ra, Sx, Mx);
+      mat3mul(Ra, Sy, My);
+      mat3mul(Ra, Sz, Mz);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        double s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {  // k: column-major index of the 3x3 -> (k%3, k/3)
+          const int rr = k % 3, cc = k / 3;
+          s0 += dq[r * 9 + k] * Mx[rr * 3 + cc];
+          s1 += dq[r * 9 + k] * My[rr * 3 + cc];
+          s2 += dq[r * 9 + k] * Mz[rr * 3 + cc];
+        }
+        Ji[(3 + r) * 6 + 3] = s0; Ji[(3 + r) * 6 + 4] = s1; Ji[(3 + r) * 6 + 5] = s2;
+      }
+    }
+    {  // dre/dqj = dq * [vec(Rab*Sx) vec(Rab*Sy) vec(Rab*Sz)], skew of Rc
+      const double r11 = 2 * Pj[0], r12 = 2 * Pj[1], r13 = 2 * Pj[2];
+      const double r21 = 2 * Pj[3], r22 = 2 * Pj[4], r23 = 2 * Pj[5];
+      const double r31 = 2 * Pj[6], r32 = 2 * Pj[7], r33 = 2 * Pj[8];
+      const double Sx[9] = {0, 0, 0, -r31, -r32, -r33, r21, r22, r23};
+      const double Sy[9] = {r31, r32, r33, 0, 0, 0, -r11, -r12, -r13};
+      const double Sz[9] = {-r21, -r22, -r23, r11, r12, r13, 0, 0, 0};
+      double Mx[9], My[9], Mz[9];
+      mat3mul(Rab, Sx, Mx);
+      mat3mul(Rab, Sy, My);
+      mat3mul(Rab, Sz, Mz);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        double s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          const int rr = k % 3, cc = k / 3;
+          s0 += dq[r * 9 + k] * Mx[rr * 3 + cc];
+          s1 += dq[r * 9 + k] * My[rr * 3 + cc];
+          s2 += dq[r * 9 + k] * Mz[rr * 3 + cc];
+        }
+        Jj[(3 + r) * 6 + 3] = s0; Jj[(3 + r) * 6 + 4] = s1; Jj[(3 + r) * 6 + 5] = s2;
+      }
+    }
+  }
+};
+
+// ---- EdgeSE2Offset (types/slam2d/edge_se2_offset.cpp:102-106, CacheSE2Offset::updateImpl parameter_se2_offset.cpp:
+// 76-86): meas payload = inverse measurement (x y theta, as FamilySE2), info packed 6, parameter record
+// [Pi (x y theta) | Pj (x y theta)] (shared when EdgeData::ue bit 1 is set). With Ni = Xi * Pi, Nj = Xj * Pj:
+// error = ((Z^-1 * Ni^-1) * Nj) as (x, y, normalised angle), computeError's association. The reference has no analytic
+// Jacobian (numeric default); these are the exact ones: FamilySE2's at (Ni, Nj), each times the chain factor of
+// N = X * P under VertexSE2's additive oplus, the identity with its last column (R'(theta) p, 1),
+// R'(theta) = [[-s, -c], [c, -s]], p the offset's translation. Only the third column of each Jacobian changes. ----
+struct FamilySE2Offset {
+  static constexpr int D = 3, DA = 3, DB = 3, MEAS = 3, INFO = 6, PAR = 6;
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double Ji[9], Jj[9];
+    eval<false>(d, e, err, Ji, Jj);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    eval<true>(d, e, err, Ji, Jj);
+  }
+  template <bool JAC>
+  DI static void eval(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    const double* xi = d.s0 + (size_t)d.v0[e] * 3;
+    const double* xj = d.s1 + (size_t)d.v1[e] * 3;
+    const double* mi = d.meas + (size_t)e * 3;
+    const double* P = param_rec(d, e, PAR);
+    const double a[3] = {xi[0], xi[1], xi[2]}, b[3] = {xj[0], xj[1], xj[2]}, m[3] = {mi[0], mi[1], mi[2]};
+    const double pi[3] = {P[0], P[1], P[2]}, pj[3] = {P[3], P[4], P[5]};
+    // SE2::operator* and SE2::inverse (se2.h:60-87) spelled out: each angle's sine and cosine is taken once and
+    // serves the error and the Jacobians (five pairs; through FamilySE2's helpers it would be eleven)
+    const double sa = sin(a[2]), ca = cos(a[2]), sb = sin(b[2]), cb = cos(b[2]);
+    const double ni[3] = {a[0] + (ca * pi[0] - sa * pi[1]), a[1] + (sa * pi[0] + ca * pi[1]), normalize_theta(a[2] + pi[2])};
+    const double nj[3] = {b[0] + (cb * pj[0] - sb * pj[1]), b[1] + (sb * pj[0] + cb * pj[1]), normalize_theta(b[2] + pj[2])};
+    const double si = sin(ni[2]), ci = cos(ni[2]);
+    // w = Ni^-1: the angle -theta, t = R(-theta) (-t)
+    const double w[3] = {ci * (-ni[0]) + si * (-ni[1]), -si * (-ni[0]) + ci * (-ni[1]), normalize_theta(-ni[2])};
+    const double rc = cos(m[2]), rs = sin(m[2]);
+    const double t[3] = {m[0] + (rc * w[0] - rs * w[1]), m[1] + (rs * w[0] + rc * w[1]), normalize_theta(m[2] + w[2])};
+    const double st = sin(t[2]), ct = cos(t[2]);
+    err[0] = t[0] + (ct * nj[0] - st * nj[1]);
+    err[1] = t[1] + (st * nj[0] + ct * nj[1]);
+    err[2] = normalize_theta(t[2] + nj[2]);
+    if (JAC) {
+      const double dtx = nj[0] - ni[0], dty = nj[1] - ni[1];
+      const double A[9] = {-ci, -si, -si * dtx + ci * dty, si, -ci, -ci * dtx - si * dty, 0, 0, -1};
+      const double B[9] = {ci, si, 0, -si, ci, 0, 0, 0, 1};
+      const double Z[9] = {rc, -rs, 0, rs, rc, 0, 0, 0, 1};
+      mat3mul(Z, A, Ji);
+      mat3mul(Z, B, Jj);
+      // chain factors: column 2 += columns 0-1 times R'(theta) p
+      const double ui = -sa * pi[0] - ca * pi[1], vi = ca * pi[0] - sa * pi[1];
+      const double uj = -sb * pj[0] - cb * pj[1], vj = cb * pj[0] - sb * pj[1];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        Ji[r * 3 + 2] += Ji[r * 3] * ui + Ji[r * 3 + 1] * vi;
+        Jj[r * 3 + 2] += Jj[r * 3] * uj + Jj[r * 3 + 1] * vj;
+      }
+    }
+  }
+};
+
+// ---- EdgeSE2PointXYBearing (types/slam2d/edge_se2_pointxy_bearing.h:43-50): v0 = SE2 pose (3), v1 = XY point (2);
+// meas one angle, info one scalar, no parameter record. d = v0^-1 * l (SE2::inverse, then t + R v, as FamilySE2XY),
+// error = normalize_theta(z - atan2(d.y, d.x)). The reference has no analytic Jacobian; these are the exact ones: with
+// g = (-d.y, d.x) / |d|^2, Ji = [ g R(theta)^T | 1 ], Jj = -g R(theta)^T. Singular at d = 0, as the reference. ----
+struct FamilySE2XYBearing {
+  static constexpr int D = 1, DA = 3, DB = 2, MEAS = 1, INFO = 1;
+  // d = v0^-1 * l
+  DI static void to_sensor(const double* xi, const double* l, double* dd) {
+    const double a[3] = {xi[0], xi[1], xi[2]};
+    double ai[3];
+    FamilySE2::inverse(a, ai);
+    const double c = cos(ai[2]), s = sin(ai[2]), l0 = l[0], l1 = l[1];
+    dd[0] = ai[0] + (c * l0 - s * l1);
+    dd[1] = ai[1] + (s * l0 + c * l1);
+  }
+  // Jj = -g R^T (1 x 2); the pose's is [-Jj | 1]
+  DI static void point_jacobian(double theta, const double* dd, double* Jj) {
+    const double n2 = dd[0] * dd[0] + dd[1] * dd[1];
+    const double g0 = -dd[1] / n2, g1 = dd[0] / n2;
+    const double c = cos(theta), s = sin(theta);
+    Jj[0] = -(g0 * c - g1 * s);  // g R^T = (g0 c - g1 s, g0 s + g1 c)
+    Jj[1] = -(g0 * s + g1 * c);
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double dd[2];
+    to_sensor(d.s0 + (size_t)d.v0[e] * 3, d.s1 + (size_t)d.v1[e] * 2, dd);
+    err[0] = normalize_theta(d.meas[e] - atan2(dd[1], dd[0]));
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    const double* xi = d.s0 + (size_t)d.v0[e] * 3;
+    double dd[2];
+    to_sensor(xi, d.s1 + (size_t)d.v1[e] * 2, dd);
+    err[0] = normalize_theta(d.meas[e] - atan2(dd[1], dd[0]));
+    point_jacobian(xi[2], dd, Jj);
+    Ji[0] = -Jj[0];
+    Ji[1] = -Jj[1];
+    Ji[2] = 1.0;
+  }
+};
 
 // ---- host-Jacobian edges (an edge type the device does not know): the host's linearizeOplus
 // (base_binary_edge.hpp:198-266 numeric, or the type's own analytic one) supplies, per edge, the error and

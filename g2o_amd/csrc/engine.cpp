@@ -59,6 +59,8 @@ static bool is_hostj(int e) { return is_hostj_binary(e) || is_hostj_unary(e); }
 static bool is_slam3d_type(int e) { return e >= G2OHIP_E_SE3_XYZ && e <= G2OHIP_E_SE3_XYZ_DISPARITY; }
 // the sba types on a VertexCam: EdgeProjectP2MC, EdgeProjectP2SC
 static bool is_sba_type(int e) { return e == G2OHIP_E_PROJECT_P2MC || e == G2OHIP_E_PROJECT_P2SC; }
+// the edges between two sensor frames, with two offset parameters: EdgeSE3Offset, EdgeSE2Offset
+static bool is_offset_type(int e) { return e == G2OHIP_E_SE3_OFFSET || e == G2OHIP_E_SE2_OFFSET; }
 // BaseUnaryEdge types: the five priors, the two pose-only projections (EdgeSE3ProjectXYZOnlyPose and its stereo
 // sibling, on a VertexSE3Expmap) and the unary host-J escape
 static bool is_unary_type(int e) {
@@ -73,22 +75,28 @@ int edge_dim(int e) {
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: case G2OHIP_E_PROJECT_P2SC: return 3;
     case G2OHIP_E_PROJECT_P2MC: return 2;
     case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: return 2;
-    case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: return 6;
+    case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: case G2OHIP_E_SE3_OFFSET: return 6;
+    case G2OHIP_E_SE2_OFFSET: return 3;
+    case G2OHIP_E_SE2_XY_BEARING: return 1;
   }
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 6 : (e == G2OHIP_E_SE2 ? 3 : -1));
 }
 int edge_meas_dim(int e) {
   if (is_hostj(e)) return 0;
   if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR || e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 2;
-  if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_EXPMAP) return 7;
+  if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_EXPMAP || e == G2OHIP_E_SE3_OFFSET) return 7;
+  if (e == G2OHIP_E_SE2_XY_BEARING) return 1;  // (G2OHIP_E_SE2_OFFSET: x y theta, the default below)
   if (is_slam3d_type(e)) return 3;
   if (is_sba_type(e)) return e == G2OHIP_E_PROJECT_P2MC ? 2 : 3;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
 }
 // doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
 // sensor offset x y z qx qy qz qw (optional: NULL = identity), as EdgeSE3PointXYZ's; the slam3d camera types' offset
-// followed by fx fy cx cy; the pose-only projections' Xw fx fy cx cy (stereo + bf)
+// followed by fx fy cx cy; the pose-only projections' Xw fx fy cx cy (stereo + bf); EdgeSE3Offset / EdgeSE2Offset: the
+// offset of the from vertex, then of the to vertex (2 x 7 / 2 x 3, optional: NULL = both the identity)
 int edge_param_dim(int e) {
+  if (e == G2OHIP_E_SE3_OFFSET) return 14;
+  if (e == G2OHIP_E_SE2_OFFSET) return 6;
   if (e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 7;
   if (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE) return 8;
   if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_XYZ) return 7;
@@ -1217,8 +1225,9 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   const bool unary = is_unary_type(type);
   if (unary != (v1 == nullptr) && (n > 0 || v1)) return G2OHIP_ERR_ARG;  // v1 is NULL for the unary types, only for them
   const int np = edge_param_dim(type);
-  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ) return G2OHIP_ERR_ARG;
+  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ && !is_offset_type(type)) return G2OHIP_ERR_ARG;
   if (is_sba_type(type) && params) return G2OHIP_ERR_ARG;  // the intrinsics live in the VertexCam
+  if (type == G2OHIP_E_SE2_XY_BEARING && params) return G2OHIP_ERR_ARG;  // EdgeSE2PointXYBearing has no parameter
   const int nm = edge_meas_dim(type);
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
@@ -1241,7 +1250,9 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   if (np > 0 && params) es->params.insert(es->params.end(), params, params + (size_t)n * np);
   if (np > 0 && !params) {  // EdgeSE3Prior / EdgeSE3PointXYZ without an offset parameter: the identity
     const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
-    for (int k = 0; k < n; ++k) es->params.insert(es->params.end(), ident, ident + 7);
+    if (type == G2OHIP_E_SE2_OFFSET) es->params.insert(es->params.end(), (size_t)n * 6, 0.0);
+    else
+      for (int k = 0; k < n * (np / 7); ++k) es->params.insert(es->params.end(), ident, ident + 7);
   }
   es->payload.clear();
   if (!es->level.empty()) es->level.resize(es->ev0.size(), 0);  // new edges arrive at level 0
@@ -1297,9 +1308,11 @@ int Engine::set_host_callback(g2ohip_host_edge_fn fn, void* user) {
 namespace {
 struct ParsedVertex { int type, id; double est[12]; };  // (12: VERTEX_CAM)
 // unary: b = -1, or the SE3 prior's parameter id; pid: the slam3d landmark edges' parameter id
-struct ParsedEdge { int type, a, b; double m[7], info[36], p[11]; int pid = -1; };
-// PARAMS_SE3OFFSET id x y z qx qy qz qw; camera: PARAMS_CAMERACALIB, the same followed by fx fy cx cy
-struct ParsedParam { int id; double v[11]; bool camera = false; };
+// (the offset edges: pid the from vertex's parameter id, pid2 the to vertex's; p the two records)
+struct ParsedEdge { int type, a, b; double m[7], info[36], p[14]; int pid = -1, pid2 = -1; };
+// PARAMS_SE3OFFSET id x y z qx qy qz qw; camera: PARAMS_CAMERACALIB, the same followed by fx fy cx cy; se2:
+// PARAMS_SE2OFFSET id x y theta
+struct ParsedParam { int id; double v[11]; bool camera = false, se2 = false; };
 struct ParsedChunk {
   std::vector<ParsedVertex> verts;
   std::vector<ParsedEdge> edges;
@@ -1335,7 +1348,9 @@ struct Cursor {
 // unary: the unary edge tags and PARAMS_SE3OFFSET are parsed (G2OHIP_LOAD_UNARY), else skipped as unknown tags;
 // slam3d: VERTEX_TRACKXYZ, PARAMS_SE3OFFSET, PARAMS_CAMERACALIB and the three landmark edge tags (G2OHIP_LOAD_SLAM3D)
 // expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP); sba: VERTEX_CAM, EDGE_PROJECT_P2MC, EDGE_PROJECT_P2SC (G2OHIP_LOAD_SBA)
-void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, bool sba, ParsedChunk& out) {
+// offset: PARAMS_SE3OFFSET, PARAMS_SE2OFFSET, EDGE_SE3_OFFSET, EDGE_SE2_OFFSET, EDGE_BEARING_SE2_XY (G2OHIP_LOAD_OFFSET)
+void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, bool sba, bool offset,
+                 ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1425,7 +1440,28 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       for (int r = 0; r < 6; ++r)
         for (int q = r; q < 6; ++q) ed.info[r * 6 + q] = ed.info[q * 6 + r] = c.d();
       out.edges.push_back(ed);
-    } else if ((unary || slam3d) && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
+    } else if (offset && tag == "PARAMS_SE2OFFSET") {  // parameter_se2_offset.cpp:50-57: id x y theta
+      ParsedParam pp{c.i(), {}, false, true};
+      for (int k = 0; k < 3; ++k) pp.v[k] = c.d();
+      out.params.push_back(pp);
+    } else if (offset && (tag == "EDGE_SE3_OFFSET" || tag == "EDGE_SE2_OFFSET")) {
+      // edge_se3_offset.cpp:59-88, edge_se2_offset.cpp:59-84: the two parameter ids, the measurement, the upper
+      // triangle of the information row-wise
+      const bool se3 = tag == "EDGE_SE3_OFFSET";
+      const int D = se3 ? 6 : 3, nm = se3 ? 7 : 3;
+      ParsedEdge ed{se3 ? G2OHIP_E_SE3_OFFSET : G2OHIP_E_SE2_OFFSET, c.i(), c.i(), {}, {}, {}};
+      ed.pid = c.i();
+      ed.pid2 = c.i();
+      for (int k = 0; k < nm; ++k) ed.m[k] = c.d();
+      for (int r = 0; r < D; ++r)
+        for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
+      out.edges.push_back(ed);
+    } else if (offset && tag == "EDGE_BEARING_SE2_XY") {  // edge_se2_pointxy_bearing.cpp:56-60: angle, information
+      ParsedEdge ed{G2OHIP_E_SE2_XY_BEARING, c.i(), c.i(), {}, {}, {}};
+      ed.m[0] = c.d();
+      ed.info[0] = c.d();
+      out.edges.push_back(ed);
+    } else if ((unary || slam3d || offset) && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
       ParsedParam pp{c.i(), {}};
       for (int k = 0; k < 7; ++k) pp.v[k] = c.d();
       out.params.push_back(pp);
@@ -1473,7 +1509,8 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
 
 int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0,
-             expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0, sba = (flags & G2OHIP_LOAD_SBA) != 0;
+             expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0, sba = (flags & G2OHIP_LOAD_SBA) != 0,
+             offset = (flags & G2OHIP_LOAD_OFFSET) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1501,7 +1538,8 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
-      th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, chunks[t]); });
+      th.emplace_back(
+          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1567,7 +1605,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                 std::to_string(ed.a) + ", which is missing or of the wrong type");
         if (ed.type == G2OHIP_E_SE3_PRIOR) {
           auto po = offsets.find(ed.b);
-          if (po == offsets.end() || po->second->camera)
+          if (po == offsets.end() || po->second->camera || po->second->se2)
             throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: EDGE_SE3_PRIOR on vertex " + std::to_string(ed.a) +
                                                   " names parameter id " + std::to_string(ed.b) +
                                                   ", which no PARAMS_SE3OFFSET line defines");
@@ -1594,10 +1632,38 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                 std::to_string(ed.b) + ": vertex " + std::to_string(ed.b) +
                                                 " is missing or no VERTEX_CAM");
       }
+      if (is_offset_type(ed.type) || ed.type == G2OHIP_E_SE2_XY_BEARING) {
+        const bool se3 = ed.type == G2OHIP_E_SE3_OFFSET;
+        const std::string tg = se3 ? "EDGE_SE3_OFFSET " : ed.type == G2OHIP_E_SE2_OFFSET ? "EDGE_SE2_OFFSET " : "EDGE_BEARING_SE2_XY ";
+        const std::string where = "g2o_hip load: " + tg + std::to_string(ed.a) + " -> " + std::to_string(ed.b);
+        int vtA, vtB;
+        family_of(ed.type, vtA, vtB);
+        const char* vname[2] = {se3 ? "VERTEX_SE3:QUAT" : "VERTEX_SE2", vtB == G2OHIP_V_XY ? "VERTEX_XY" : (se3 ? "VERTEX_SE3:QUAT" : "VERTEX_SE2")};
+        const int want[2] = {vtA, vtB}, end[2] = {ed.a, ed.b};
+        for (int h = 0; h < 2; ++h) {
+          auto it = hg.idmap.find(end[h]);
+          if (it == hg.idmap.end() || hg.verts[it->second].type != want[h])
+            throw StatusError(G2OHIP_ERR_ARG, where + ": vertex " + std::to_string(end[h]) + " is missing or no " + vname[h]);
+        }
+        if (is_offset_type(ed.type)) {
+          const int pid[2] = {ed.pid, ed.pid2}, np = se3 ? 7 : 3;
+          const char* pname = se3 ? "PARAMS_SE3OFFSET" : "PARAMS_SE2OFFSET";
+          for (int h = 0; h < 2; ++h) {
+            auto po = offsets.find(pid[h]);
+            if (po == offsets.end())
+              throw StatusError(G2OHIP_ERR_ARG, where + " names parameter id " + std::to_string(pid[h]) + ", which no " +
+                                                    pname + " line defines");
+            if (po->second->camera || po->second->se2 == se3)
+              throw StatusError(G2OHIP_ERR_ARG, where + " names parameter id " + std::to_string(pid[h]) +
+                                                    ", which is of another kind than " + pname);
+            std::memcpy(ed.p + h * np, po->second->v, sizeof(double) * np);
+          }
+        }
+      }
       if (is_slam3d_type(ed.type)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
         const bool cam = ed.type != G2OHIP_E_SE3_XYZ;
         auto po = offsets.find(ed.pid);
-        if (po == offsets.end() || po->second->camera != cam)
+        if (po == offsets.end() || po->second->camera != cam || po->second->se2)
           throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: landmark edge (type " + std::to_string(ed.type) + ") " +
                                                 std::to_string(ed.a) + " -> " + std::to_string(ed.b) +
                                                 " names parameter id " + std::to_string(ed.pid) + ", which no " +
@@ -1671,10 +1737,11 @@ int Engine::save(const char* path) {
   std::vector<char> track(hg.verts.size(), 0);
   {
     std::vector<std::pair<const double*, int>> distinct;  // record, its length (7 offset, 11 camera)
+    // (the offset edges hold two records of np = 7 / 3 per edge: ids of 2 n half-records, from then to)
     auto ids_of = [&](const HEdgeSet& es, std::vector<int>& ids) {
-      const int np = edge_param_dim(es.type);
-      ids.resize(es.ev0.size());
-      for (size_t k = 0; k < es.ev0.size(); ++k) {
+      const int per = is_offset_type(es.type) ? 2 : 1, np = edge_param_dim(es.type) / per;
+      ids.resize(es.ev0.size() * per);
+      for (size_t k = 0; k < ids.size(); ++k) {
         const double* p = es.params.data() + k * np;
         size_t j = 0;
         while (j < distinct.size() &&
@@ -1683,7 +1750,7 @@ int Engine::save(const char* path) {
         if (j == distinct.size()) {
           distinct.emplace_back(p, np);
           LineBuf& L = out[0];
-          L.tag(np == 7 ? "PARAMS_SE3OFFSET" : "PARAMS_CAMERACALIB"); L.i((int)j);
+          L.tag(np == 7 ? "PARAMS_SE3OFFSET" : np == 3 ? "PARAMS_SE2OFFSET" : "PARAMS_CAMERACALIB"); L.i((int)j);
           for (int q = 0; q < np; ++q) L.d(p[q]);
           L.nl();
         }
@@ -1696,6 +1763,8 @@ int Engine::save(const char* path) {
         ids_of(hg.esets[si], pids[si]);
         for (int v : hg.esets[si].ev1) track[v] = 1;
       }
+    for (size_t si = 0; si < hg.esets.size(); ++si)
+      if (is_offset_type(hg.esets[si].type)) ids_of(hg.esets[si], pids[si]);
     flush();
   }
   parallel_ranges(hg.verts.size(), nt, [&](int t, size_t lo, size_t hi) {
@@ -1764,6 +1833,13 @@ int Engine::save(const char* path) {
                                             // refused a graph whose information is not the identity)
           L.tag(es.type == G2OHIP_E_PROJECT_P2MC ? "EDGE_PROJECT_P2MC" : "EDGE_PROJECT_P2SC"); L.i(a); L.i(b);
           for (int q = 0; q < nm; ++q) L.d(m[q]);
+        } else if (is_offset_type(es.type)) {  // edge_se3_offset.cpp:90-100, edge_se2_offset.cpp:86-94: the two ids first
+          L.tag(es.type == G2OHIP_E_SE3_OFFSET ? "EDGE_SE3_OFFSET" : "EDGE_SE2_OFFSET"); L.i(a); L.i(b);
+          L.i(pids[si][2 * k]); L.i(pids[si][2 * k + 1]);
+          for (int q = 0; q < nm; ++q) L.d(m[q]);
+          for (int r = 0; r < D; ++r) for (int q = r; q < D; ++q) L.d(I[r * D + q]);
+        } else if (es.type == G2OHIP_E_SE2_XY_BEARING) {  // edge_se2_pointxy_bearing.cpp:62-66
+          L.tag("EDGE_BEARING_SE2_XY"); L.i(a); L.i(b); L.d(m[0]); L.d(I[0]);
         } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
           L.tag("EDGE_SE2_XY"); L.i(a); L.i(b);
           L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
@@ -1933,6 +2009,9 @@ static int family_of(int etype, int& vtA, int& vtB) {
     case G2OHIP_E_SE3_EXPMAP: vtA = vtB = G2OHIP_V_SE3_EXPMAP; return FAM_EXPMAP;
     case G2OHIP_E_PROJECT_P2MC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_CAM; return FAM_SBA_MONO;
     case G2OHIP_E_PROJECT_P2SC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_CAM; return FAM_SBA_STEREO;
+    case G2OHIP_E_SE3_OFFSET: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3_OFFSET;
+    case G2OHIP_E_SE2_OFFSET: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2_OFFSET;
+    case G2OHIP_E_SE2_XY_BEARING: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY_BEARING;
     // unary types: vtB = 0 (no second vertex)
     case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
     case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
@@ -2318,14 +2397,20 @@ void Engine::fill_group_device(EGroup& g) {
     case FAM_U_STEREO_POSE_ONLY: mmeas = 6; break;  // u_l v u_r | Xw
     case FAM_SBA_MONO: mmeas = 2; break;
     case FAM_SBA_STEREO: mmeas = 3; break;
+    case FAM_SE3_OFFSET: mmeas = 12; break;     // Z^-1 as an isometry, as FAM_SE3
+    case FAM_SE2_OFFSET: mmeas = 3; break;      // the inverse measurement, as FAM_SE2
+    case FAM_SE2XY_BEARING: mmeas = 1; break;
   }
   // device parameter record: the BA intrinsics as given; slam3d: the inverse offset as an isometry (12), the camera
   // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
-  // point Xw ahead of them in the caller's record goes into the measurement payload)
+  // point Xw ahead of them in the caller's record goes into the measurement payload); EdgeSE3Offset: the two offsets as
+  // isometries [R (9) | t (3)] (24); EdgeSE2Offset: the two offsets x y theta as given (6)
   const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type)
                    : g.family == FAM_SE3_XYZ ? 12
                    : is_slam3d_family(g.family) ? 16
-                   : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3 : 0;
+                   : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3
+                   : g.family == FAM_SE3_OFFSET ? 24
+                   : g.family == FAM_SE2_OFFSET ? 6 : 0;
   std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
       params(mpar ? (size_t)gne * mpar : 1);
   for (int k = 0; k < gne; ++k) {
@@ -2360,7 +2445,10 @@ void Engine::fill_group_device(EGroup& g) {
       for (int i = 0; i < 3; ++i) mo[21 + i] = p[i];
     } else if (g.family == FAM_U_SE2XY || g.family == FAM_U_XY || g.family == FAM_U_XYZ) {
       for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
-    } else if (g.family == FAM_SE2 || g.family == FAM_U_SE2) {  // edge_se2.cpp:41-47, edge_se2_prior.cpp:67-71: inverse measurement
+    } else if (g.family == FAM_SE2 || g.family == FAM_U_SE2 || g.family == FAM_SE2_OFFSET) {
+      // edge_se2.cpp:41-47, edge_se2_prior.cpp:67-71, edge_se2_offset.h setMeasurement: the inverse measurement
+      if (g.family == FAM_SE2_OFFSET)  // the two ParameterSE2Offset, SE2(x, y, theta) as given
+        for (int j = 0; j < 6; ++j) params[(size_t)k * 6 + j] = es.params[(size_t)e * 6 + j];
       const double th = norm_theta(-m[2]);
       const double c = std::cos(th), s = std::sin(th);
       mo[0] = c * (-m[0]) - s * (-m[1]);
@@ -2368,8 +2456,20 @@ void Engine::fill_group_device(EGroup& g) {
       mo[2] = th;
     } else if (g.family == FAM_SE2XY) {
       mo[0] = m[0]; mo[1] = m[1];
-    } else if (is_sba_family(g.family)) {
+    } else if (is_sba_family(g.family) || g.family == FAM_SE2XY_BEARING) {
       for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+    } else if (g.family == FAM_SE3_OFFSET) {  // edge_se3_offset.cpp:59-72: Z^-1 of the normalised measurement; the two
+                                              // ParameterSE3Offset::offset() = fromVectorQT, q normalised
+      iso_inverse_of(m, mo);
+      for (int h = 0; h < 2; ++h) {
+        const double* p = es.params.data() + (size_t)e * 14 + h * 7;
+        double* po = params.data() + (size_t)k * 24 + h * 12;
+        double q[4] = {p[3], p[4], p[5], p[6]};
+        const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        for (double& x : q) x /= n;
+        q2R(q[0], q[1], q[2], q[3], po);
+        for (int i = 0; i < 3; ++i) po[9 + i] = p[i];
+      }
     } else if (g.family == FAM_EXPMAP) {  // SE3Quat(Vector7), se3quat.h:81-88: normalizeRotation (w >= 0, unit)
       double q[4] = {m[3], m[4], m[5], m[6]};
       const double sn = q[3] < 0 ? -1.0 : 1.0;
@@ -2405,7 +2505,8 @@ void Engine::fill_group_device(EGroup& g) {
     const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
     g.ue = 0;
     if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family) ||
-         is_sba_family(g.family)) && gne > 1 && !(ev && atoi(ev) == 0)) {
+         is_sba_family(g.family) || is_offset_family(g.family) || g.family == FAM_SE2XY_BEARING) && gne > 1 &&
+        !(ev && atoi(ev) == 0)) {
       auto uniform = [&](const std::vector<double>& v, int st) {
         for (int k = 1; k < gne; ++k)
           if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
@@ -2869,6 +2970,12 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
         throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                           "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the sba types on "
                           "a VertexCam (edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
+  if (use_cgls())
+    for (const HEdgeSet& es : hg.esets)
+      if ((is_offset_type(es.type) || es.type == G2OHIP_E_SE2_XY_BEARING) && !es.ev0.empty())
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the offset and "
+                          "bearing edges (edge type " + std::to_string(es.type) + "); use lm_pcg or lm_hip_var");
   if (use_cgls())
     for (const HEdgeSet& es : hg.esets)
       if (es.type == G2OHIP_E_SE3_EXPMAP && !es.ev0.empty())

@@ -1861,6 +1861,9 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_EXPMAP: fn(FamilyExpmap{}); break;
     case FAM_SBA_MONO: fn(FamilySBAMono{}); break;
     case FAM_SBA_STEREO: fn(FamilySBAStereo{}); break;
+    case FAM_SE3_OFFSET: fn(FamilySE3Offset{}); break;
+    case FAM_SE2_OFFSET: fn(FamilySE2Offset{}); break;
+    case FAM_SE2XY_BEARING: fn(FamilySE2XYBearing{}); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;

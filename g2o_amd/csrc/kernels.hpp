@@ -15,6 +15,8 @@ enum Family {
   FAM_EXPMAP = 10,
   // sba types (point, VertexCam): EdgeProjectP2MC, EdgeProjectP2SC
   FAM_SBA_MONO = 11, FAM_SBA_STEREO = 12,
+  // offset and bearing edges: EdgeSE3Offset, EdgeSE2Offset (two poses, two sensor offsets), EdgeSE2PointXYBearing
+  FAM_SE3_OFFSET = 13, FAM_SE2_OFFSET = 14, FAM_SE2XY_BEARING = 15,
   // unary families (BaseUnaryEdge: one vertex, EdgeArgs::v1 / s1 null, DB = 0)
   FAM_U_SE2 = 16, FAM_U_SE2XY = 17, FAM_U_XY = 18, FAM_U_SE3 = 19, FAM_U_XYZ = 20, FAM_U_HOSTJ = 21,
   // pose-only projections on a VertexSE3Expmap camera: EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose
@@ -25,6 +27,9 @@ inline bool is_pose_only_family(int f) { return f == FAM_U_POSE_ONLY || f == FAM
 inline bool is_hostj_family(int f) { return f == FAM_HOSTJ || f == FAM_U_HOSTJ; }
 inline bool is_slam3d_family(int f) { return f >= FAM_SE3_XYZ && f <= FAM_SE3_XYZ_DISPARITY; }
 inline bool is_sba_family(int f) { return f == FAM_SBA_MONO || f == FAM_SBA_STEREO; }
+inline bool is_offset_family(int f) { return f == FAM_SE3_OFFSET || f == FAM_SE2_OFFSET; }
+// the families whose second vertex is the landmark (structure-only, the SE2 / SE3 landmark edges)
+inline bool is_lm_second_family(int f) { return is_slam3d_family(f) || f == FAM_SE2XY || f == FAM_SE2XY_BEARING; }
 
 struct EdgeArgs {
   const int* v0;

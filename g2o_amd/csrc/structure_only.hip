@@ -192,6 +192,19 @@ struct PointEdge<FAM_SE2XY> {  // FamilySE2XY::linearize, Jj
   }
 };
 
+template <>
+struct PointEdge<FAM_SE2XY_BEARING> {  // FamilySE2XYBearing::linearize, Jj
+  static constexpr int D = 1, LD = 2;
+  template <bool JAC>
+  DI static void eval(const SoGroup& g, int e, const double* p, double* err, double* A) {
+    const double* xi = g.so + (size_t)g.vo[e] * 3;
+    double dd[2];
+    FamilySE2XYBearing::to_sensor(xi, p, dd);
+    err[0] = normalize_theta(g.meas[e] - atan2(dd[1], dd[0]));
+    if (JAC) FamilySE2XYBearing::point_jacobian(xi[2], dd, A);
+  }
+};
+
 template <int N>
 struct PointPrior {  // FamilyUnaryPoint<N>: error = estimate - z, J = I
   static constexpr int D = N, LD = N;
@@ -279,6 +292,7 @@ DI void edge_any(const SoGroup* groups, int2 en, const double* p, double& chi, d
     }
   } else {
     if (g.family == FAM_SE2XY) edge_term<FAM_SE2XY, JAC>(g, en.y, p, chi, H, b);
+    else if (g.family == FAM_SE2XY_BEARING) edge_term<FAM_SE2XY_BEARING, JAC>(g, en.y, p, chi, H, b);
     else edge_term<FAM_U_XY, JAC>(g, en.y, p, chi, H, b);
   }
 }

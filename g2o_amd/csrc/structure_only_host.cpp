@@ -74,7 +74,7 @@ void Engine::so_build_list() {
     fixed.push_back(v.fixed ? 1 : 0);
   }
   L.nlm = (int)local.size();
-  // the landmark end of each group: v0 for the BA and sba families and the point priors, v1 for slam3d and SE2-XY
+  // the landmark end of each group: v0 for the BA and sba families and the point priors, v1 for slam3d, SE2-XY and the bearing edge
   std::vector<int> cnt(L.nlm + 1, 0);
   std::vector<int> gslot(groups.size(), -1);
   auto lm_end = [&](const EGroup& g, int k) {  // vertex index of the edge's marginalised endpoint(s): (a, b), -1 none
@@ -87,7 +87,7 @@ void Engine::so_build_list() {
     const EGroup& g = groups[gi];
     const bool lm_first = g.family == FAM_BA || g.family == FAM_BA_STEREO || g.family == FAM_U_XYZ ||
                           g.family == FAM_U_XY || is_sba_family(g.family);
-    const bool lm_second = is_slam3d_family(g.family) || g.family == FAM_SE2XY;
+    const bool lm_second = is_lm_second_family(g.family);
     for (int k = 0; k < g.ne; ++k) {
       const auto [a, b] = lm_end(g, k);
       if (a < 0 && b < 0) continue;
@@ -112,7 +112,7 @@ void Engine::so_build_list() {
   std::vector<int> fill(cnt.begin(), cnt.end() - 1);
   for (int gi : L.group_of) {
     const EGroup& g = groups[gi];
-    const bool lm_first = !(is_slam3d_family(g.family) || g.family == FAM_SE2XY);
+    const bool lm_first = !is_lm_second_family(g.family);
     for (int k = 0; k < g.ne; ++k) {
       const auto [a, b] = lm_end(g, k);
       const int v = lm_first ? a : b;
@@ -168,7 +168,7 @@ int Engine::structure_only_calc(int n, const int* ids, int num_iters, int num_ma
   std::memset(sg.data(), 0, sizeof(launch::SoGroup) * sg.size());
   for (size_t k = 0; k < L.group_of.size(); ++k) {
     const EGroup& g = groups[L.group_of[k]];
-    const bool lm_first = !(is_slam3d_family(g.family) || g.family == FAM_SE2XY);
+    const bool lm_first = !is_lm_second_family(g.family);
     launch::SoGroup& o = sg[k];
     o.vo = is_unary_family(g.family) ? nullptr : (lm_first ? g.v1.get() : g.v0.get());
     const int vto = lm_first ? g.vtB : g.vtA;

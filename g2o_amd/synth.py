@@ -26,6 +26,10 @@ Recipes:
   * ``slam3d_landmarks`` - 3D SLAM with landmarks (VERTEX_SE3:QUAT poses with EDGE_SE3:QUAT odometry, VERTEX_TRACKXYZ
     points seen through EDGE_SE3_TRACKXYZ / EDGE_PROJECT_DEPTH / EDGE_PROJECT_DISPARITY), the shape of
     g2o_simulator3d's output.
+  * ``se3_offset_graph`` / ``se2_offset_graph`` - pose graphs measured between sensor frames (EDGE_SE3_OFFSET /
+    EDGE_SE2_OFFSET with one or two distinct sensor offsets), the shape of g2o_simulator3d's pose sensor.
+  * ``bearing_scene`` - bearing-only 2D landmark SLAM (EDGE_BEARING_SE2_XY; every landmark seen from several poses
+    with parallax), the shape of g2o_simulator2d's bearing sensor.
 """
 from __future__ import annotations
 
@@ -53,17 +57,24 @@ E_SE3_EXPMAP = 10
 E_SE3_PROJECT_XYZ_ONLYPOSE, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE = 21, 22
 # the sba types: v0 a V_XYZ point, v1 a V_CAM camera; no params (the intrinsics live in the vertex)
 E_PROJECT_P2MC, E_PROJECT_P2SC = 11, 12
+# EdgeSE3Offset / EdgeSE2Offset between two poses (params: the from vertex's sensor offset, then the to vertex's),
+# EdgeSE2PointXYBearing from a V_SE2 pose to a V_XY point (one angle, no params)
+E_SE3_OFFSET, E_SE2_OFFSET, E_SE2_XY_BEARING = 13, 14, 15
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
             E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
             E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
-            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3}
+            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 7, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
            E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
-           E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3}
+           E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 6, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1}
+# parameter values per edge of the types that take a record (EdgeSet.params; where None is allowed it is the identity)
+PARAM_DIM = {E_SE3_PROJECT_XYZ: 4, E_STEREO_SE3_PROJECT_XYZ: 5, E_SE3_PRIOR: 7, E_SE3_XYZ: 7, E_SE3_XYZ_DEPTH: 11,
+             E_SE3_XYZ_DISPARITY: 11, E_SE3_PROJECT_XYZ_ONLYPOSE: 7, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 8,
+             E_SE3_OFFSET: 14, E_SE2_OFFSET: 6}
 # the vertex type a unary edge type attaches to
 PRIOR_VERTEX = {E_SE2_PRIOR: V_SE2, E_SE2_XY_PRIOR: V_SE2, E_XY_PRIOR: V_XY, E_SE3_PRIOR: V_SE3_QUAT, E_XYZ_PRIOR: V_XYZ}
 # the same for the pose-only projections, and the binary projection each of them is the pose-only form of
@@ -90,7 +101,8 @@ class EdgeSet:
     info: np.ndarray    # float64 [n, D, D]
     # float64 [n, 4] (fx fy cx cy) for projection edges, [n, 5] (+ bf) for stereo, [n, 7] (offset x y z qx qy qz qw)
     # or None (identity) for SE3 priors and E_SE3_XYZ, [n, 11] (offset, fx fy cx cy) for E_SE3_XYZ_DEPTH / _DISPARITY,
-    # [n, 7] (Xw fx fy cx cy) / [n, 8] (+ bf) for the pose-only projections
+    # [n, 7] (Xw fx fy cx cy) / [n, 8] (+ bf) for the pose-only projections, [n, 14] / [n, 6] (the from vertex's offset,
+    # then the to vertex's; or None, both the identity) for E_SE3_OFFSET / E_SE2_OFFSET
     params: np.ndarray | None = None
 
 
@@ -946,3 +958,148 @@ def pose_only_twin(prob: Problem) -> Problem:
         edges.append(EdgeSet(POSE_ONLY_BINARY[es.etype], ids, es.v0.copy(), es.meas.copy(), es.info.copy(),
                              es.params[:, 3:].copy()))
     return Problem(prob.name + "/twin", verts, edges, prob.pose_dim, prob.landmark_dim)
+
+
+# ---------------------------------------------------------------- offset pose graphs, bearing-only landmarks
+def _loop_pairs(rng, n, loops):
+    """Odometry (i, i + 1) and ``loops`` closures (i, j), j > i + 1, drawn at random."""
+    a, b = np.arange(0, n - 1), np.arange(1, n)
+    if loops > 0 and n > 2:
+        la = rng.integers(0, n - 2, loops)
+        lb = la + 2 + (rng.random(loops) * (n - 2 - la)).astype(np.int64)
+        a, b = np.concatenate([a, la]), np.concatenate([b, np.minimum(lb, n - 1)])
+    return a, b
+
+
+def se3_offset_graph(num_poses: int = 40, loops: int = 80, num_offsets: int = 2, rot_noise: float = 0.01,
+                     trans_noise: float = 0.02, seed: int = SEED) -> Problem:
+    """An SE3 pose graph measured between sensor frames (EdgeSE3Offset, what g2o_simulator3d's pose sensor writes):
+    ``num_poses`` VertexSE3 bodies on a rising circle joined by odometry and ``loops`` loop closures.  The body carries
+    ``num_offsets`` (1 or 2) sensors with distinct mounting offsets; an edge measures Z = (Xi Pi)^-1 (Xj Pj) * noise
+    between the sensor of its from vertex and that of its to vertex, the sensor pair alternating from edge to edge
+    when there are two.  params [m, 14]: the from vertex's offset, then the to vertex's.  Information: SPD, not
+    diagonal.  Pose 0 is fixed; initial estimates are the true poses perturbed."""
+    n = num_poses
+    rng = _rng(seed, 70)
+    th = 2 * math.pi * np.arange(n) / max(n, 8)
+    pos = np.stack([5 * np.cos(th), 5 * np.sin(th), 0.05 * np.arange(n)], 1)
+    R = _axis_angle(np.tile([0.0, 0.0, 1.0], (n, 1)), th + 0.5 * math.pi) @ _small_rot(rng, n, 0.2)
+    offR = _axis_angle(np.array([[0.3, -0.5, 0.8], [-0.7, 0.2, 0.4]]), np.array([0.6, -1.1]))
+    offt = np.array([[0.2, -0.1, 0.3], [-0.15, 0.25, 0.1]])
+    a, b = _loop_pairs(rng, n, loops)
+    m = len(a)
+    k = np.arange(m)
+    si = (k % 2) if num_offsets > 1 else np.zeros(m, np.int64)
+    sj = ((k // 2) % 2) if num_offsets > 1 else np.zeros(m, np.int64)
+    # n2w = X P
+    Rni, tni = R[a] @ offR[si], pos[a] + np.einsum("nij,nj->ni", R[a], offt[si])
+    Rnj, tnj = R[b] @ offR[sj], pos[b] + np.einsum("nij,nj->ni", R[b], offt[sj])
+    Rz = np.transpose(Rni, (0, 2, 1)) @ Rnj
+    tz = np.einsum("nji,nj->ni", Rni, tnj - tni)
+    sg = np.array([trans_noise] * 3 + [rot_noise] * 3)
+    Rz = Rz @ _small_rot(rng, m, rot_noise)
+    tz = tz + rng.standard_normal((m, 3)) * trans_noise
+    meas = np.concatenate([tz, rot_to_quat(Rz)], axis=1)
+    info = _spd_info(rng, m, sg)
+    offv = np.concatenate([offt, rot_to_quat(offR)], axis=1)
+    params = np.concatenate([offv[si], offv[sj]], axis=1)
+    R0 = R @ _small_rot(rng, n, 0.03)
+    t0 = pos + rng.standard_normal((n, 3)) * 0.05
+    R0[0], t0[0] = R[0], pos[0]
+    fixed = np.zeros(n, np.int32)
+    fixed[0] = 1
+    ids = np.arange(n, dtype=np.int32)
+    verts = VertexSet(V_SE3_QUAT, ids, _iso_vec(R0, t0), fixed, np.zeros(n, np.int32))
+    edges = EdgeSet(E_SE3_OFFSET, ids[a].copy(), ids[b].copy(), meas, info, params)
+    return Problem(f"se3offset{n}l{loops}o{num_offsets}", [verts], [edges], 6, 0)
+
+
+def se2_offset_graph(num_poses: int = 40, loops: int = 80, num_offsets: int = 2, noise=(0.03, 0.03, 0.01),
+                     seed: int = SEED) -> Problem:
+    """The 2D sibling of :func:`se3_offset_graph` (EdgeSE2Offset): VertexSE2 bodies on a circle, one or two sensors
+    with distinct offsets (x y theta), Z = (Xi Pi)^-1 (Xj Pj) + noise.  params [m, 6]."""
+    n = num_poses
+    rng = _rng(seed, 71)
+    th = 2 * math.pi * np.arange(n) / max(n, 8)
+    gt = np.stack([5 * np.cos(th), 5 * np.sin(th), np.mod(th + 0.5 * math.pi + np.pi, 2 * np.pi) - np.pi], 1)
+    gt[:, 2] += rng.standard_normal(n) * 0.2
+    gt[:, 2] = np.mod(gt[:, 2] + np.pi, 2 * np.pi) - np.pi
+    off = np.array([[0.3, -0.2, 0.7], [-0.25, 0.4, -1.2]])
+    a, b = _loop_pairs(rng, n, loops)
+    m = len(a)
+    k = np.arange(m)
+    si = (k % 2) if num_offsets > 1 else np.zeros(m, np.int64)
+    sj = ((k // 2) % 2) if num_offsets > 1 else np.zeros(m, np.int64)
+    ni, nj = _se2_compose(gt[a], off[si]), _se2_compose(gt[b], off[sj])
+    meas = _se2_between(ni, nj) + rng.standard_normal((m, 3)) * np.asarray(noise)
+    meas[:, 2] = np.mod(meas[:, 2] + np.pi, 2 * np.pi) - np.pi
+    info = _spd_info(rng, m, np.asarray(noise, float))
+    params = np.concatenate([off[si], off[sj]], axis=1)
+    est = gt + rng.standard_normal((n, 3)) * np.array([0.05, 0.05, 0.03])
+    est[0] = gt[0]
+    est[:, 2] = np.mod(est[:, 2] + np.pi, 2 * np.pi) - np.pi
+    fixed = np.zeros(n, np.int32)
+    fixed[0] = 1
+    ids = np.arange(n, dtype=np.int32)
+    verts = VertexSet(V_SE2, ids, est, fixed, np.zeros(n, np.int32))
+    edges = EdgeSet(E_SE2_OFFSET, ids[a].copy(), ids[b].copy(), meas, info, params)
+    return Problem(f"se2offset{n}l{loops}o{num_offsets}", [verts], [edges], 3, 0)
+
+
+def bearing_scene(num_poses: int = 12, num_landmarks: int = 30, obs_per_landmark: int = 4, bearing_noise: float = 0.01,
+                  odo_noise=(0.03, 0.03, 0.01), seed: int = SEED) -> Problem:
+    """Bearing-only 2D landmark SLAM (EdgeSE2PointXYBearing, what g2o_simulator2d's bearing sensor writes):
+    ``num_poses`` VertexSE2 poses on a circle of radius 6 around ``num_landmarks`` VertexPointXY landmarks scattered
+    within radius 2 of its centre, so that every pose sees every landmark at a distance of at least 4 and two poses
+    see one landmark under different directions (parallax).  Each landmark is seen from ``obs_per_landmark`` (>= 3)
+    distinct poses spread over the circle; consecutive poses are joined by EdgeSE2 odometry, which with the fixed pose
+    0 sets the gauge and the scale.  The landmarks are marginalised (BlockSolver_3_2).  Initial estimates: the true
+    values perturbed."""
+    n, L, k = num_poses, num_landmarks, min(obs_per_landmark, num_poses)
+    rng = _rng(seed, 72)
+    th = 2 * math.pi * np.arange(n) / n
+    gt = np.stack([6 * np.cos(th), 6 * np.sin(th), np.mod(th + np.pi + np.pi, 2 * np.pi) - np.pi], 1)  # facing the centre
+    gt[:, 2] = np.mod(gt[:, 2] + rng.standard_normal(n) * 0.3 + np.pi, 2 * np.pi) - np.pi
+    rad, ang = 2.0 * np.sqrt(rng.random(L)), 2 * math.pi * rng.random(L)
+    lm = np.stack([rad * np.cos(ang), rad * np.sin(ang)], 1)
+    # landmark l: poses start + round(j n / k), j < k, spread over the circle
+    start = rng.integers(0, n, L)
+    op = (start[:, None] + np.round(np.arange(k) * n / k).astype(np.int64)[None, :]) % n
+    oa, ob = op.reshape(-1), np.repeat(np.arange(L), k)
+    order = np.lexsort((ob, oa))
+    oa, ob = oa[order], ob[order]
+    c, s = np.cos(gt[oa, 2]), np.sin(gt[oa, 2])
+    dx, dy = lm[ob, 0] - gt[oa, 0], lm[ob, 1] - gt[oa, 1]
+    z = np.arctan2(-s * dx + c * dy, c * dx + s * dy) + rng.standard_normal(len(oa)) * bearing_noise
+    z = np.mod(z + np.pi, 2 * np.pi) - np.pi
+    a = np.arange(n - 1)
+    zodo = _se2_between(gt[a], gt[a + 1]) + rng.standard_normal((n - 1, 3)) * np.asarray(odo_noise)
+    zodo[:, 2] = np.mod(zodo[:, 2] + np.pi, 2 * np.pi) - np.pi
+    est = gt + rng.standard_normal((n, 3)) * np.array([0.05, 0.05, 0.02])
+    est[0] = gt[0]
+    est[:, 2] = np.mod(est[:, 2] + np.pi, 2 * np.pi) - np.pi
+    lest = lm + rng.standard_normal((L, 2)) * 0.1
+    fixed = np.zeros(n, np.int32)
+    fixed[0] = 1
+    pose_ids = np.arange(n, dtype=np.int32)
+    lm_ids = (n + np.arange(L)).astype(np.int32)
+    poses = VertexSet(V_SE2, pose_ids, est, fixed, np.zeros(n, np.int32))
+    points = VertexSet(V_XY, lm_ids, lest, np.zeros(L, np.int32), np.ones(L, np.int32))
+    odo = EdgeSet(E_SE2, pose_ids[a], pose_ids[a + 1], zodo,
+                  np.broadcast_to(np.diag(1.0 / np.square(odo_noise)), (n - 1, 3, 3)).copy())
+    w = (1.0 / bearing_noise ** 2) * (1.0 + 0.5 * rng.random(len(oa)))  # per-edge scalar information
+    obs = EdgeSet(E_SE2_XY_BEARING, pose_ids[oa], lm_ids[ob], z[:, None].copy(), w[:, None, None].copy())
+    return Problem(f"bearing{n}x{L}", [poses, points], [odo, obs], 3, 2)
+
+
+def offset_twin(prob: Problem) -> Problem:
+    """The host-Jacobian twin of a graph with offset / bearing edges: every E_SE3_OFFSET, E_SE2_OFFSET and
+    E_SE2_XY_BEARING set as an E_HOSTJ(6) / (3) / (1) set (32 + D) between the same vertices with the same
+    information; the caller supplies the payload."""
+    edges = []
+    for es in prob.edges:
+        if es.etype in (E_SE3_OFFSET, E_SE2_OFFSET, E_SE2_XY_BEARING):
+            edges.append(EdgeSet(32 + ERR_DIM[es.etype], es.v0.copy(), es.v1.copy(), None, es.info.copy(), None))
+        else:
+            edges.append(es)
+    return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)

@@ -92,6 +92,28 @@ extern "C" {
                                     e = (fx pc.x / pc.z + cx - u, fy pc.y / pc.z + cy - v) */
 #define G2OHIP_E_PROJECT_P2SC 12 /* EdgeProjectP2SC (EDGE_PROJECT_P2SC): meas u v u_r; info 3x3; rows 0-1 as
                                     G2OHIP_E_PROJECT_P2MC, e2 = fx (pc.x - baseline) / pc.z + cx - u_r */
+/* Offset and bearing edges of types_slam3d / types_slam2d, what g2o_simulator3d's pose sensor and g2o_simulator2d's
+ * bearing sensor write. Generic slot path. Robust kernels, edge levels, g2ohip_edge_chi2 and g2ohip_classify_edges take
+ * them like any device type; none has isDepthPositive, so depth_positive != NULL or check_depth is G2OHIP_ERR_ARG.
+ * lm_pcg6_3_eigen refuses a graph that holds any of them (g2ohip_last_error says so). Edges whose parameter records
+ * are all equal share one record on the device, and likewise the information. */
+#define G2OHIP_E_SE3_OFFSET 13 /* EdgeSE3Offset (EDGE_SE3_OFFSET), edge_se3_offset.cpp:102-132: v0, v1 both
+                                  G2OHIP_V_SE3_QUAT; meas x y z qx qy qz qw (q normalised on entry, as
+                                  EdgeSE3Offset::read); info 6x6; params n x 14: ParameterSE3Offset::offset() of the
+                                  from vertex, then of the to vertex, each x y z qx qy qz qw (q normalised); NULL: both
+                                  the identity. error = toVectorMQT(Z^-1 (Xi Pi)^-1 (Xj Pj)); the reference's analytic
+                                  Jacobians (isometry3d_gradients.h:84-189, the non-__clang__ branch) */
+#define G2OHIP_E_SE2_OFFSET 14 /* EdgeSE2Offset (EDGE_SE2_OFFSET), edge_se2_offset.cpp:102-106: v0, v1 both
+                                  G2OHIP_V_SE2; meas x y theta; info 3x3; params n x 6: the two ParameterSE2Offset as
+                                  x y theta, from then to; NULL: both the identity. error = Z^-1 (Xi Pi)^-1 (Xj Pj) as
+                                  (x, y, normalised angle); exact Jacobians (the reference differentiates numerically) */
+#define G2OHIP_E_SE2_XY_BEARING 15 /* EdgeSE2PointXYBearing (EDGE_BEARING_SE2_XY), edge_se2_pointxy_bearing.h:43-50: v0
+                                      G2OHIP_V_SE2, v1 G2OHIP_V_XY, in g2o's order; meas one angle; info 1x1; params
+                                      must be NULL (non-NULL is G2OHIP_ERR_ARG). With d = v0^-1 * l:
+                                      error = normalize_theta(z - atan2(d.y, d.x)); exact Jacobians (the reference
+                                      differentiates numerically), singular at d = 0 as the reference's error is. With
+                                      marginalised landmarks it runs on the 3/2 Schur path, in structure_only_2 and
+                                      on landmark shards, as G2OHIP_E_SE2_XY does */
 /* An edge type the device does not know (any BaseBinaryEdge<D, E, Vi, Vj> between registered vertices of
  * dimension 2, 3 or 6): the host's own linearizeOplus (the type's analytic one, or BaseBinaryEdge's numeric
  * central differences, base_binary_edge.hpp:198-266) supplies the error and both Jacobians, see
@@ -219,6 +241,14 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * reads none); an endpoint that is missing or of the wrong type fails the load. Without the flag the three tags are
  * skipped like any unknown one. */
 #define G2OHIP_LOAD_SBA 8u
+/* G2OHIP_LOAD_OFFSET (may be combined with the other flags): PARAMS_SE2OFFSET id x y theta and PARAMS_SE3OFFSET id
+ * x y z qx qy qz qw are read; EDGE_SE3_OFFSET v0 v1 pidFrom pidTo, 7 measurement values and 21 upper-triangle
+ * information values loads as G2OHIP_E_SE3_OFFSET; EDGE_SE2_OFFSET v0 v1 pidFrom pidTo x y theta and 6 upper-triangle
+ * values as G2OHIP_E_SE2_OFFSET; EDGE_BEARING_SE2_XY v0 v1 angle info00 as G2OHIP_E_SE2_XY_BEARING. A parameter id no
+ * line defines or one of the wrong kind, an endpoint that is missing or of the wrong type and a short line fail the
+ * load, g2ohip_last_error naming the tag or the id. Without the flag the three edge tags and PARAMS_SE2OFFSET are
+ * skipped like any unknown one. */
+#define G2OHIP_LOAD_OFFSET 16u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
@@ -232,7 +262,10 @@ int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, u
  * vertices are written as VERTEX_CAM with their 12 values, G2OHIP_E_PROJECT_P2MC / _P2SC as EDGE_PROJECT_P2MC /
  * EDGE_PROJECT_P2SC with the measurement alone (types_sba.cpp:114-131, 215-244); the points they touch stay
  * VERTEX_XYZ. These lines cannot carry an information matrix: a graph holding such an edge whose information is not
- * the identity is not written (G2OHIP_ERR_UNSUPPORTED, nothing written). */
+ * the identity is not written (G2OHIP_ERR_UNSUPPORTED, nothing written). G2OHIP_E_SE3_OFFSET / _SE2_OFFSET edges are
+ * written as EDGE_SE3_OFFSET / EDGE_SE2_OFFSET v0 v1 pidFrom pidTo, the measurement and the upper triangle of the
+ * information (edge_se3_offset.cpp:90-100, edge_se2_offset.cpp:86-94), with one PARAMS_SE3OFFSET / PARAMS_SE2OFFSET
+ * line per distinct offset in the same id space; G2OHIP_E_SE2_XY_BEARING as EDGE_BEARING_SE2_XY v0 v1 angle info00. */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
