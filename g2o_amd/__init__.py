@@ -67,6 +67,11 @@ E_SE3_OFFSET, E_SE2_OFFSET, E_SE2_XY_BEARING = 13, 14, 15
 EDGE_TAGS = {E_SE3_OFFSET: "EDGE_SE3_OFFSET", E_SE2_OFFSET: "EDGE_SE2_OFFSET", E_SE2_XY_BEARING: "EDGE_BEARING_SE2_XY"}
 
 
+# g2o's own BA edges on a CameraParameters parameter (include/g2o_hip.h G2OHIP_E_PROJECT_XYZ2UV / _XYZ2UVU): v0 the
+# V_XYZ point, v1 the V_SE3_EXPMAP camera; meas u v / u v u_r; params [n, 4] focal_length cx cy baseline
+E_PROJECT_XYZ2UV, E_PROJECT_XYZ2UVU = 23, 24
+
+
 # edge types the device does not know: host-supplied error + Jacobians (include/g2o_hip.h G2OHIP_E_HOSTJ)
 def E_HOSTJ(D: int) -> int:
     return 32 + D
@@ -92,6 +97,7 @@ LOAD_SLAM3D = 2
 LOAD_EXPMAP = 4
 LOAD_SBA = 8
 LOAD_OFFSET = 16
+LOAD_CAMERAPARAMS = 32
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -455,15 +461,16 @@ class SparseOptimizer:
         _check(lib().g2ohip_set_estimates(self.h, vtype, _p(est)), "set_estimates")
 
     def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False,
-             expmap: bool = False, sba: bool = False, offset: bool = False):
+             expmap: bool = False, sba: bool = False, offset: bool = False, camparams: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
         EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
         (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
         PARAMS_CAMERACALIB), expmap=True EDGE_SE3:EXPMAP, sba=True the sba tags (VERTEX_CAM, EDGE_PROJECT_P2MC,
         EDGE_PROJECT_P2SC), offset=True the offset and bearing tags (EDGE_SE3_OFFSET, EDGE_SE2_OFFSET,
-        EDGE_BEARING_SE2_XY + PARAMS_SE3OFFSET, PARAMS_SE2OFFSET); all are skipped otherwise."""
+        EDGE_BEARING_SE2_XY + PARAMS_SE3OFFSET, PARAMS_SE2OFFSET), camparams=True g2o's own BA tags
+        (EDGE_PROJECT_XYZ2UV:EXPMAP + PARAMS_CAMERAPARAMETERS); all are skipped otherwise."""
         flags = ((LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0) |
-                 (LOAD_SBA if sba else 0) | (LOAD_OFFSET if offset else 0))
+                 (LOAD_SBA if sba else 0) | (LOAD_OFFSET if offset else 0) | (LOAD_CAMERAPARAMS if camparams else 0))
         _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:

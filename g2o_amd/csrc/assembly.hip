@@ -750,16 +750,19 @@ void linearize_fused(int family, const EdgeArgs& a, const int4* chunks, int nchu
   if (nchunks <= 0) return;
   const EdgeData d{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, a.rk, a.rk_delta, a.ue};
   const SchurSplit z = sp ? *sp : SchurSplit{};
-  if (family == FAM_BA_STEREO) {  // G blocks only: the Kt record encodes the D = 2 geometry
+  if (family == FAM_BA_STEREO || family == FAM_BA_UVU) {  // G blocks only: the Kt record encodes the D = 2 geometry
     if (sp && sp->kx) throw std::runtime_error("linearize_fused: Kt records are monocular only");
-    if (sp)
-      hipLaunchKernelGGL((k_linearize_fused<FamilyStereo, true, false>), grid_for(nchunks, 4), 256, 0, s, d, chunks,
-                         nchunks, h0, h1, off_dst, off_tr, off_base, off_slot, Hll, b, num_poses, size_poses, lm_begin,
-                         lpart, z);
-    else
-      hipLaunchKernelGGL((k_linearize_fused<FamilyStereo, false, false>), grid_for(nchunks, 4), 256, 0, s, d, chunks,
-                         nchunks, h0, h1, off_dst, off_tr, off_base, off_slot, Hll, b, num_poses, size_poses, lm_begin,
-                         lpart, z);
+    auto go = [&](auto fam) {
+      using F = decltype(fam);
+      if (sp)
+        hipLaunchKernelGGL((k_linearize_fused<F, true, false>), grid_for(nchunks, 4), 256, 0, s, d, chunks, nchunks, h0,
+                           h1, off_dst, off_tr, off_base, off_slot, Hll, b, num_poses, size_poses, lm_begin, lpart, z);
+      else
+        hipLaunchKernelGGL((k_linearize_fused<F, false, false>), grid_for(nchunks, 4), 256, 0, s, d, chunks, nchunks, h0,
+                           h1, off_dst, off_tr, off_base, off_slot, Hll, b, num_poses, size_poses, lm_begin, lpart, z);
+    };
+    if (family == FAM_BA_UVU) go(FamilyUVU{});
+    else go(FamilyStereo{});
     KERNEL_CHECK();
     return;
   }
@@ -816,6 +819,8 @@ void backsub_j(int family, const EdgeArgs& a, int nl, const int2* erng, const in
   const int lanes = lanes_k.get();
   if (family == FAM_BA_STEREO)
     backsub_j_lanes<FamilyStereo>(lanes, d, nl, erng, hcam, Ufac, cl_all, size_poses, lm0, x, s);
+  else if (family == FAM_BA_UVU)
+    backsub_j_lanes<FamilyUVU>(lanes, d, nl, erng, hcam, Ufac, cl_all, size_poses, lm0, x, s);
   else if (family == FAM_BA)
     backsub_j_lanes<FamilyBA>(lanes, d, nl, erng, hcam, Ufac, cl_all, size_poses, lm0, x, s);
   else
@@ -835,17 +840,22 @@ void cam_assemble(int family, const EdgeArgs& a, const int* cm_ptr, int npose, d
   if (npose <= 0) return;
   const EdgeData d{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, a.rk, a.rk_delta, a.ue};
   const SchurSplit z = sp ? *sp : SchurSplit{};
-  if (family == FAM_BA_STEREO) {  // always the recomputing pass (no Kt records)
+  if (family == FAM_BA_STEREO || family == FAM_BA_UVU) {  // always the recomputing pass (no Kt records)
     if (sp && sp->kx) throw std::runtime_error("cam_assemble: Kt records are monocular only");
-    if (sp && cam_nt())
-      hipLaunchKernelGGL((k_cam_assemble<FamilyStereo, true, false, true>), npose, 256, 0, s, d, cm_ptr, cams, npose,
-                         Hpp, b, num_poses, lm_begin, z);
-    else if (sp)
-      hipLaunchKernelGGL((k_cam_assemble<FamilyStereo, true, false, false>), npose, 256, 0, s, d, cm_ptr, cams, npose,
-                         Hpp, b, num_poses, lm_begin, z);
-    else
-      hipLaunchKernelGGL((k_cam_assemble<FamilyStereo, false, false, false>), npose, 256, 0, s, d, cm_ptr, cams, npose,
-                         Hpp, b, num_poses, lm_begin, z);
+    auto go = [&](auto fam) {
+      using F = decltype(fam);
+      if (sp && cam_nt())
+        hipLaunchKernelGGL((k_cam_assemble<F, true, false, true>), npose, 256, 0, s, d, cm_ptr, cams, npose, Hpp, b,
+                           num_poses, lm_begin, z);
+      else if (sp)
+        hipLaunchKernelGGL((k_cam_assemble<F, true, false, false>), npose, 256, 0, s, d, cm_ptr, cams, npose, Hpp, b,
+                           num_poses, lm_begin, z);
+      else
+        hipLaunchKernelGGL((k_cam_assemble<F, false, false, false>), npose, 256, 0, s, d, cm_ptr, cams, npose, Hpp, b,
+                           num_poses, lm_begin, z);
+    };
+    if (family == FAM_BA_UVU) go(FamilyUVU{});
+    else go(FamilyStereo{});
     KERNEL_CHECK();
     return;
   }

@@ -108,7 +108,7 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
 }
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
   if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP | G2OHIP_LOAD_SBA |
-                                    G2OHIP_LOAD_OFFSET))) return G2OHIP_ERR_ARG;
+                                    G2OHIP_LOAD_OFFSET | G2OHIP_LOAD_CAMERAPARAMS))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
@@ -119,6 +119,14 @@ int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
     g_err = "g2ohip_save_g2o: the graph holds " + std::to_string(es->ev0.size()) +
             " EdgeStereoSE3ProjectXYZ edges, which the .g2o format cannot carry (the reference's reader and writer "
             "for the tag drop the intrinsics and misread the measurement)";
+    return G2OHIP_ERR_UNSUPPORTED;
+  }
+  // EdgeProjectXYZ2UVU likewise: the reader of EDGE_PROJECT_XYZ2UVU:EXPMAP (types_six_dof_expmap.cpp:335-346) reads no
+  // parameter id, so a loaded edge has no camera and addEdge rejects it (optimizable_graph.cpp:277-280)
+  if (const auto* es = g->e->hg.set_of(G2OHIP_E_PROJECT_XYZ2UVU); es && !es->ev0.empty()) {
+    g_err = "g2ohip_save_g2o: the graph holds " + std::to_string(es->ev0.size()) +
+            " EdgeProjectXYZ2UVU edges, which the .g2o format cannot carry (the reference's reader for "
+            "EDGE_PROJECT_XYZ2UVU:EXPMAP reads no CameraParameters id, so the graph drops the edge)";
     return G2OHIP_ERR_UNSUPPORTED;
   }
   // the pose-only projections likewise: their tags carry neither the point Xw nor the intrinsics

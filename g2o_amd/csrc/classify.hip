@@ -120,6 +120,7 @@ void classify(int family, const EdgeArgs& a, int ne, const ClassifyArgs& c, hipS
   switch (family) {
     case FAM_BA: classify_launch<FamilyBA>(d, ne, c, s); break;
     case FAM_BA_STEREO: classify_launch<FamilyStereo>(d, ne, c, s); break;
+    case FAM_BA_UVU: classify_launch<FamilyUVU>(d, ne, c, s); break;  // no isDepthPositive in the reference
     case FAM_SE3: classify_launch<FamilySE3>(d, ne, c, s); break;
     case FAM_SE2: classify_launch<FamilySE2>(d, ne, c, s); break;
     case FAM_SE2XY: classify_launch<FamilySE2XY>(d, ne, c, s); break;

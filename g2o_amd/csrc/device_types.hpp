@@ -416,7 +416,14 @@ struct FamilyBA {
 
 // ---- EdgeStereoSE3ProjectXYZ: v0 = point (3), v1 = camera SE3Quat (6); meas u_l v u_r, info packed upper 6,
 // intrinsics fx fy cx cy bf (stride 5) ----
-struct FamilyStereo {
+// UVU: EdgeProjectXYZ2UVU on a CameraParameters (types_six_dof_expmap.h:178-198): meas u v u_r, the record
+// f f cx cy b (the host expands focal_length cx cy baseline). Its error is stereocam_uvu_map's, all doubles. The
+// reference has no linearizeOplus for it (commented out, types_six_dof_expmap.h:196) and differentiates numerically;
+// here the Jacobians are the exact first derivatives: rows 0-1 EdgeProjectXYZ2UV's analytic forms
+// (types_six_dof_expmap.cpp:295-333), row 2 = -(f/z, 0, -f (x - b)/z^2) applied to R (point) and to [-[pc]x | I]
+// (camera, (omega, upsilon) order), which is the stereo edge's row 2 with bf = f * b.
+template <bool UVU>
+struct FamilyStereoT {
   static constexpr int D = 3, DA = 3, DB = 6, MEAS = 3, INFO = 6, PAR = 5;
   static constexpr int S0 = 3, S1 = 8;  // state strides
   // the point in the camera frame (SE3Quat::map)
@@ -433,15 +440,26 @@ struct FamilyStereo {
   // No contraction here: the projection rounds as the reference's does, operation by operation.
   DI static void residual(const double* K, const double* pc, double m0, double m1, double m2, double* err) {
 #pragma clang fp contract(off)
-    const double invz = 1.0 / pc[2];
-    const double bf_f = (double)(float)K[4];
-    const double u = pc[0] * invz * K[0] + K[2];
-    const double v = pc[1] * invz * K[1] + K[3];
-    const double ur = u - bf_f * invz;
-    err[0] = m0 - u;
-    err[1] = m1 - v;
-    err[2] = m2 - ur;
+    if constexpr (UVU) {  // obs - stereocam_uvu_map (types_six_dof_expmap.cpp:74-87): no float bf, (x - b) / z * f + cx
+      const double u = pc[0] / pc[2] * K[0] + K[2];
+      const double v = pc[1] / pc[2] * K[1] + K[3];
+      const double ur = (pc[0] - K[4]) / pc[2] * K[0] + K[2];
+      err[0] = m0 - u;
+      err[1] = m1 - v;
+      err[2] = m2 - ur;
+    } else {
+      const double invz = 1.0 / pc[2];
+      const double bf_f = (double)(float)K[4];
+      const double u = pc[0] * invz * K[0] + K[2];
+      const double v = pc[1] * invz * K[1] + K[3];
+      const double ur = u - bf_f * invz;
+      err[0] = m0 - u;
+      err[1] = m1 - v;
+      err[2] = m2 - ur;
+    }
   }
+  // the factor of row 2's baseline terms: bf as given, or f * b of the CameraParameters record
+  DI static double bf_of(const double* K) { return UVU ? K[0] * K[4] : K[4]; }
   // the error, and the point's z in the camera frame (isDepthPositive, types_six_dof_expmap.h:279-283)
   DI static double depth(const EdgeData& d, int e, double* err) {
     double q[4], pc[3];
@@ -469,7 +487,7 @@ struct FamilyStereo {
     const double m1 = NT ? __builtin_nontemporal_load(mp + 1) : mp[1];
     const double m2 = NT ? __builtin_nontemporal_load(mp + 2) : mp[2];
     residual(K, pc, m0, m1, m2, err);
-    const double fx = K[0], fy = K[1], bf = K[4];
+    const double fx = K[0], fy = K[1], bf = bf_of(K);
     const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z;
     double R[9];
     quat_to_R(q[0], q[1], q[2], q[3], R);
@@ -500,6 +518,8 @@ struct FamilyStereo {
     B[17] = B[5] - bf / z_2;
   }
 };
+using FamilyStereo = FamilyStereoT<false>;
+using FamilyUVU = FamilyStereoT<true>;
 
 // ---- EdgeSE3 (Isometry3): meas payload = Zinv [12], info packed upper 21 ----
 struct FamilySE3 {

@@ -61,6 +61,8 @@ static bool is_slam3d_type(int e) { return e >= G2OHIP_E_SE3_XYZ && e <= G2OHIP_
 static bool is_sba_type(int e) { return e == G2OHIP_E_PROJECT_P2MC || e == G2OHIP_E_PROJECT_P2SC; }
 // the edges between two sensor frames, with two offset parameters: EdgeSE3Offset, EdgeSE2Offset
 static bool is_offset_type(int e) { return e == G2OHIP_E_SE3_OFFSET || e == G2OHIP_E_SE2_OFFSET; }
+// g2o's own BA edges on a CameraParameters parameter: EdgeProjectXYZ2UV, EdgeProjectXYZ2UVU
+static bool is_camparams_type(int e) { return e == G2OHIP_E_PROJECT_XYZ2UV || e == G2OHIP_E_PROJECT_XYZ2UVU; }
 // BaseUnaryEdge types: the five priors, the two pose-only projections (EdgeSE3ProjectXYZOnlyPose and its stereo
 // sibling, on a VertexSE3Expmap) and the unary host-J escape
 static bool is_unary_type(int e) {
@@ -73,7 +75,8 @@ int edge_dim(int e) {
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: case G2OHIP_E_SE2_PRIOR: case G2OHIP_E_XYZ_PRIOR: return 3;
     case G2OHIP_E_SE3_XYZ: case G2OHIP_E_SE3_XYZ_DEPTH: case G2OHIP_E_SE3_XYZ_DISPARITY: return 3;
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: case G2OHIP_E_PROJECT_P2SC: return 3;
-    case G2OHIP_E_PROJECT_P2MC: return 2;
+    case G2OHIP_E_PROJECT_P2MC: case G2OHIP_E_PROJECT_XYZ2UV: return 2;
+    case G2OHIP_E_PROJECT_XYZ2UVU: return 3;
     case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: return 2;
     case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: case G2OHIP_E_SE3_OFFSET: return 6;
     case G2OHIP_E_SE2_OFFSET: return 3;
@@ -88,13 +91,16 @@ int edge_meas_dim(int e) {
   if (e == G2OHIP_E_SE2_XY_BEARING) return 1;  // (G2OHIP_E_SE2_OFFSET: x y theta, the default below)
   if (is_slam3d_type(e)) return 3;
   if (is_sba_type(e)) return e == G2OHIP_E_PROJECT_P2MC ? 2 : 3;
+  if (is_camparams_type(e)) return e == G2OHIP_E_PROJECT_XYZ2UV ? 2 : 3;
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
 }
 // doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
 // sensor offset x y z qx qy qz qw (optional: NULL = identity), as EdgeSE3PointXYZ's; the slam3d camera types' offset
 // followed by fx fy cx cy; the pose-only projections' Xw fx fy cx cy (stereo + bf); EdgeSE3Offset / EdgeSE2Offset: the
-// offset of the from vertex, then of the to vertex (2 x 7 / 2 x 3, optional: NULL = both the identity)
+// offset of the from vertex, then of the to vertex (2 x 7 / 2 x 3, optional: NULL = both the identity);
+// EdgeProjectXYZ2UV / XYZ2UVU: the CameraParameters focal_length cx cy baseline
 int edge_param_dim(int e) {
+  if (is_camparams_type(e)) return 4;
   if (e == G2OHIP_E_SE3_OFFSET) return 14;
   if (e == G2OHIP_E_SE2_OFFSET) return 6;
   if (e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 7;
@@ -104,6 +110,21 @@ int edge_param_dim(int e) {
   return e == G2OHIP_E_SE3_PROJECT_XYZ ? 4 : (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ ? 5 : 0);
 }
 static int family_of(int etype, int& vtA, int& vtB);
+// doubles of a BA-family edge type's parameter record on the device: the caller's, but a CameraParameters record as
+// f f cx cy (FamilyBA's fx fy cx cy; the baseline stays on the host) or f f cx cy b (FamilyUVU)
+static int ba_device_param_dim(int e) {
+  return e == G2OHIP_E_PROJECT_XYZ2UV ? 4 : (e == G2OHIP_E_PROJECT_XYZ2UVU ? 5 : edge_param_dim(e));
+}
+static void ba_device_params(int e, const double* p, double* out) {
+  if (is_camparams_type(e)) {
+    out[0] = out[1] = p[0];
+    out[2] = p[1];
+    out[3] = p[2];
+    if (e == G2OHIP_E_PROJECT_XYZ2UVU) out[4] = p[3];
+  } else {
+    for (int j = 0; j < edge_param_dim(e); ++j) out[j] = p[j];
+  }
+}
 // doubles of one host-J edge's payload: [e | Ji | Jj], a unary edge's [e | Ji]
 static size_t hostj_edge_len(const HostGraph& hg, const HEdgeSet& es, size_t k) {
   return (size_t)es.D * (1 + hg.verts[es.ev0[k]].dim + (es.unary ? 0 : hg.verts[es.ev1[k]].dim));
@@ -1311,8 +1332,8 @@ struct ParsedVertex { int type, id; double est[12]; };  // (12: VERTEX_CAM)
 // (the offset edges: pid the from vertex's parameter id, pid2 the to vertex's; p the two records)
 struct ParsedEdge { int type, a, b; double m[7], info[36], p[14]; int pid = -1, pid2 = -1; };
 // PARAMS_SE3OFFSET id x y z qx qy qz qw; camera: PARAMS_CAMERACALIB, the same followed by fx fy cx cy; se2:
-// PARAMS_SE2OFFSET id x y theta
-struct ParsedParam { int id; double v[11]; bool camera = false, se2 = false; };
+// PARAMS_SE2OFFSET id x y theta; camparams: PARAMS_CAMERAPARAMETERS id focal_length cx cy baseline
+struct ParsedParam { int id; double v[11]; bool camera = false, se2 = false, camparams = false; };
 struct ParsedChunk {
   std::vector<ParsedVertex> verts;
   std::vector<ParsedEdge> edges;
@@ -1349,8 +1370,9 @@ struct Cursor {
 // slam3d: VERTEX_TRACKXYZ, PARAMS_SE3OFFSET, PARAMS_CAMERACALIB and the three landmark edge tags (G2OHIP_LOAD_SLAM3D)
 // expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP); sba: VERTEX_CAM, EDGE_PROJECT_P2MC, EDGE_PROJECT_P2SC (G2OHIP_LOAD_SBA)
 // offset: PARAMS_SE3OFFSET, PARAMS_SE2OFFSET, EDGE_SE3_OFFSET, EDGE_SE2_OFFSET, EDGE_BEARING_SE2_XY (G2OHIP_LOAD_OFFSET)
+// camparams: PARAMS_CAMERAPARAMETERS, EDGE_PROJECT_XYZ2UV:EXPMAP (G2OHIP_LOAD_CAMERAPARAMS)
 void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, bool sba, bool offset,
-                 ParsedChunk& out) {
+                 bool camparams, ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1416,6 +1438,20 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       const double o0 = c.d(), o1 = c.d(), o2 = c.d();
       ed.info[0] = o0; ed.info[1] = o1; ed.info[2] = o1; ed.info[3] = o2;
       for (int k = 0; k < 4; ++k) ed.p[k] = c.d();  // fx fy cx cy
+      out.edges.push_back(ed);
+    } else if (camparams && tag == "PARAMS_CAMERAPARAMETERS") {  // types_six_dof_expmap.h:59-75: id f cx cy baseline
+      ParsedParam pp{c.i(), {}, false, false, true};
+      for (int k = 0; k < 4; ++k) pp.v[k] = c.d();
+      out.params.push_back(pp);
+    } else if (camparams && tag == "EDGE_PROJECT_XYZ2UV:EXPMAP") {
+      // types_six_dof_expmap.cpp:248-263: point, camera, the parameter id, u v, the upper triangle of the information.
+      // (EDGE_PROJECT_XYZ2UVU:EXPMAP stays an unknown tag: its reader, :335-346, reads no parameter id, so the edge
+      // has no camera and OptimizableGraph::addEdge drops it, optimizable_graph.cpp:277-280)
+      ParsedEdge ed{G2OHIP_E_PROJECT_XYZ2UV, c.i(), c.i(), {}, {}, {}};
+      ed.pid = c.i();
+      ed.m[0] = c.d(); ed.m[1] = c.d();
+      const double o0 = c.d(), o1 = c.d(), o2 = c.d();
+      ed.info[0] = o0; ed.info[1] = o1; ed.info[2] = o1; ed.info[3] = o2;
       out.edges.push_back(ed);
     } else if (tag == "EDGE_SE2_XY") {  // edge_se2_pointxy.cpp:46-52
       ParsedEdge ed{G2OHIP_E_SE2_XY, c.i(), c.i(), {}, {}, {}};
@@ -1510,7 +1546,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
 int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0,
              expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0, sba = (flags & G2OHIP_LOAD_SBA) != 0,
-             offset = (flags & G2OHIP_LOAD_OFFSET) != 0;
+             offset = (flags & G2OHIP_LOAD_OFFSET) != 0, camparams = (flags & G2OHIP_LOAD_CAMERAPARAMS) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1539,7 +1575,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
       th.emplace_back(
-          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, chunks[t]); });
+          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, camparams, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1605,7 +1641,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                 std::to_string(ed.a) + ", which is missing or of the wrong type");
         if (ed.type == G2OHIP_E_SE3_PRIOR) {
           auto po = offsets.find(ed.b);
-          if (po == offsets.end() || po->second->camera || po->second->se2)
+          if (po == offsets.end() || po->second->camera || po->second->se2 || po->second->camparams)
             throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: EDGE_SE3_PRIOR on vertex " + std::to_string(ed.a) +
                                                   " names parameter id " + std::to_string(ed.b) +
                                                   ", which no PARAMS_SE3OFFSET line defines");
@@ -1653,17 +1689,35 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
             if (po == offsets.end())
               throw StatusError(G2OHIP_ERR_ARG, where + " names parameter id " + std::to_string(pid[h]) + ", which no " +
                                                     pname + " line defines");
-            if (po->second->camera || po->second->se2 == se3)
+            if (po->second->camera || po->second->camparams || po->second->se2 == se3)
               throw StatusError(G2OHIP_ERR_ARG, where + " names parameter id " + std::to_string(pid[h]) +
                                                     ", which is of another kind than " + pname);
             std::memcpy(ed.p + h * np, po->second->v, sizeof(double) * np);
           }
         }
       }
+      if (ed.type == G2OHIP_E_PROJECT_XYZ2UV) {  // v0 a VERTEX_XYZ point, v1 a VERTEX_SE3:EXPMAP camera, one CameraParameters
+        const std::string where = "g2o_hip load: EDGE_PROJECT_XYZ2UV:EXPMAP " + std::to_string(ed.a) + " -> " + std::to_string(ed.b);
+        const int want[2] = {G2OHIP_V_XYZ, G2OHIP_V_SE3_EXPMAP}, end[2] = {ed.a, ed.b};
+        const char* vname[2] = {"VERTEX_XYZ", "VERTEX_SE3:EXPMAP"};
+        for (int h = 0; h < 2; ++h) {
+          auto it = hg.idmap.find(end[h]);
+          if (it == hg.idmap.end() || hg.verts[it->second].type != want[h])
+            throw StatusError(G2OHIP_ERR_ARG, where + ": vertex " + std::to_string(end[h]) + " is missing or no " + vname[h]);
+        }
+        auto po = offsets.find(ed.pid);
+        if (po == offsets.end())
+          throw StatusError(G2OHIP_ERR_ARG, where + " names parameter id " + std::to_string(ed.pid) +
+                                                ", which no PARAMS_CAMERAPARAMETERS line defines");
+        if (!po->second->camparams)
+          throw StatusError(G2OHIP_ERR_ARG, where + " names parameter id " + std::to_string(ed.pid) +
+                                                ", which is of another kind than PARAMS_CAMERAPARAMETERS");
+        std::memcpy(ed.p, po->second->v, sizeof(double) * 4);
+      }
       if (is_slam3d_type(ed.type)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
         const bool cam = ed.type != G2OHIP_E_SE3_XYZ;
         auto po = offsets.find(ed.pid);
-        if (po == offsets.end() || po->second->camera != cam || po->second->se2)
+        if (po == offsets.end() || po->second->camera != cam || po->second->se2 || po->second->camparams)
           throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: landmark edge (type " + std::to_string(ed.type) + ") " +
                                                 std::to_string(ed.a) + " -> " + std::to_string(ed.b) +
                                                 " names parameter id " + std::to_string(ed.pid) + ", which no " +
@@ -1736,7 +1790,8 @@ int Engine::save(const char* path) {
   std::vector<std::vector<int>> pids(hg.esets.size());
   std::vector<char> track(hg.verts.size(), 0);
   {
-    std::vector<std::pair<const double*, int>> distinct;  // record, its length (7 offset, 11 camera)
+    std::vector<std::pair<const double*, int>> distinct;  // record, its length (7 offset, 11 camera, 3 SE2 offset,
+                                                          // 4 CameraParameters: f cx cy baseline)
     // (the offset edges hold two records of np = 7 / 3 per edge: ids of 2 n half-records, from then to)
     auto ids_of = [&](const HEdgeSet& es, std::vector<int>& ids) {
       const int per = is_offset_type(es.type) ? 2 : 1, np = edge_param_dim(es.type) / per;
@@ -1750,7 +1805,9 @@ int Engine::save(const char* path) {
         if (j == distinct.size()) {
           distinct.emplace_back(p, np);
           LineBuf& L = out[0];
-          L.tag(np == 7 ? "PARAMS_SE3OFFSET" : np == 3 ? "PARAMS_SE2OFFSET" : "PARAMS_CAMERACALIB"); L.i((int)j);
+          L.tag(np == 7 ? "PARAMS_SE3OFFSET" : np == 3 ? "PARAMS_SE2OFFSET" : np == 4 ? "PARAMS_CAMERAPARAMETERS"
+                                                                                    : "PARAMS_CAMERACALIB");
+          L.i((int)j);
           for (int q = 0; q < np; ++q) L.d(p[q]);
           L.nl();
         }
@@ -1765,6 +1822,8 @@ int Engine::save(const char* path) {
       }
     for (size_t si = 0; si < hg.esets.size(); ++si)
       if (is_offset_type(hg.esets[si].type)) ids_of(hg.esets[si], pids[si]);
+    for (size_t si = 0; si < hg.esets.size(); ++si)  // one PARAMS_CAMERAPARAMETERS line per distinct record
+      if (hg.esets[si].type == G2OHIP_E_PROJECT_XYZ2UV) ids_of(hg.esets[si], pids[si]);
     flush();
   }
   parallel_ranges(hg.verts.size(), nt, [&](int t, size_t lo, size_t hi) {
@@ -1838,6 +1897,9 @@ int Engine::save(const char* path) {
           L.i(pids[si][2 * k]); L.i(pids[si][2 * k + 1]);
           for (int q = 0; q < nm; ++q) L.d(m[q]);
           for (int r = 0; r < D; ++r) for (int q = r; q < D; ++q) L.d(I[r * D + q]);
+        } else if (es.type == G2OHIP_E_PROJECT_XYZ2UV) {  // types_six_dof_expmap.cpp:265-276: the parameter id first
+          L.tag("EDGE_PROJECT_XYZ2UV:EXPMAP"); L.i(a); L.i(b); L.i(pids[si][k]);
+          L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
         } else if (es.type == G2OHIP_E_SE2_XY_BEARING) {  // edge_se2_pointxy_bearing.cpp:62-66
           L.tag("EDGE_BEARING_SE2_XY"); L.i(a); L.i(b); L.d(m[0]); L.d(I[0]);
         } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
@@ -1995,11 +2057,13 @@ int Engine::minimal_state(double* out) {
 
 // ------------------------------------------------------------------ Engine: structure
 // device family of an edge type (host-J types: any endpoint vertex types)
-static bool is_ba_family(int fam) { return fam == FAM_BA || fam == FAM_BA_STEREO; }
 static int family_of(int etype, int& vtA, int& vtB) {
   switch (etype) {
     case G2OHIP_E_SE3_PROJECT_XYZ: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA;
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA_STEREO;
+    // CameraParameters edges: the monocular one is FamilyBA's arithmetic with fx = fy = focal_length
+    case G2OHIP_E_PROJECT_XYZ2UV: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA;
+    case G2OHIP_E_PROJECT_XYZ2UVU: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA_UVU;
     case G2OHIP_E_SE3_QUAT: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3;
     case G2OHIP_E_SE2: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2;
     case G2OHIP_E_SE2_XY: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY;
@@ -2249,7 +2313,8 @@ int Engine::eval_edges(int type, bool classify, double* chi2, unsigned char* dep
   const size_t si = es - hg.esets.data();
   int vtA, vtB;
   const int fam = family_of(type, vtA, vtB);
-  if ((depth || check_depth) && !launch::family_has_depth(fam))
+  // (EdgeProjectXYZ2UV runs as FAM_BA, but the reference type has no isDepthPositive)
+  if ((depth || check_depth) && (!launch::family_has_depth(fam) || is_camparams_type(type)))
     throw StatusError(G2OHIP_ERR_ARG, "edge type " + std::to_string(type) + " has no isDepthPositive()");
   if (classify && ((inlier < 0 && inlier != G2OHIP_LEVEL_KEEP) || (outlier < 0 && outlier != G2OHIP_LEVEL_KEEP)))
     throw StatusError(G2OHIP_ERR_ARG, "classify_edges: a level is >= 0 or G2OHIP_LEVEL_KEEP");
@@ -2386,7 +2451,8 @@ void Engine::fill_group_device(EGroup& g) {
   const int minfo = D * (D + 1) / 2;
   int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY
                   ? 2
-                  : (g.family == FAM_SE3 ? 12 : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO ? 3 : 0));
+                  : (g.family == FAM_SE3 ? 12
+                     : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO || g.family == FAM_BA_UVU ? 3 : 0));
   switch (g.family) {  // unary families: the payload k_linearize_unary's family reads (device_types.hpp)
     case FAM_U_SE2: case FAM_U_XYZ: mmeas = 3; break;
     case FAM_U_SE2XY: case FAM_U_XY: mmeas = 2; break;
@@ -2401,11 +2467,11 @@ void Engine::fill_group_device(EGroup& g) {
     case FAM_SE2_OFFSET: mmeas = 3; break;      // the inverse measurement, as FAM_SE2
     case FAM_SE2XY_BEARING: mmeas = 1; break;
   }
-  // device parameter record: the BA intrinsics as given; slam3d: the inverse offset as an isometry (12), the camera
-  // types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
+  // device parameter record: the BA intrinsics as given (a CameraParameters record expanded: ba_device_params);
+  // slam3d: the inverse offset as an isometry (12), the camera types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
   // point Xw ahead of them in the caller's record goes into the measurement payload); EdgeSE3Offset: the two offsets as
   // isometries [R (9) | t (3)] (24); EdgeSE2Offset: the two offsets x y theta as given (6)
-  const int mpar = is_ba_family(g.family) ? edge_param_dim(es.type)
+  const int mpar = is_ba_family(g.family) ? ba_device_param_dim(es.type)
                    : g.family == FAM_SE3_XYZ ? 12
                    : is_slam3d_family(g.family) ? 16
                    : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3
@@ -2432,7 +2498,7 @@ void Engine::fill_group_device(EGroup& g) {
     };
     if (is_ba_family(g.family)) {
       for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
-      for (int j = 0; j < mpar; ++j) params[(size_t)k * mpar + j] = es.params[(size_t)e * mpar + j];
+      ba_device_params(es.type, es.params.data() + (size_t)e * edge_param_dim(es.type), params.data() + (size_t)k * mpar);
     } else if (g.family == FAM_SE3) {
       iso_inverse_of(m, mo);
     } else if (g.family == FAM_U_SE3) {  // edge_se3_prior.cpp:55-63: Z^-1, then the offset P = fromVectorQT(params)
@@ -2667,7 +2733,7 @@ void Engine::setup_edges_device() {
     std::vector<int> ptr(num_poses + 1, 0), cv0, cv1;
     std::vector<double> cmeas, cinfo, cpar;
     // per observation: D measurement doubles (2, stereo 3), the packed information, the intrinsics (4, stereo 5)
-    const int cD = g.D, cI = cD * (cD + 1) / 2, cP = edge_param_dim(es.type);
+    const int cD = g.D, cI = cD * (cD + 1) / 2, cP = ba_device_param_dim(es.type);
     cm_e_h.clear();
     for (int i = 0; i < num_poses; ++i) {
       ptr[i + 1] = ptr[i] + (int)lists[i].size();
@@ -2680,7 +2746,8 @@ void Engine::setup_edges_device() {
         const double* I = es.info.data() + (size_t)e * cD * cD;
         for (int c = 0; c < cD; ++c)  // packed upper, column-major: (0,0) (0,1) (1,1) ...
           for (int r = 0; r <= c; ++r) cinfo.push_back(I[r * cD + c]);
-        for (int j = 0; j < cP; ++j) cpar.push_back(es.params[(size_t)e * cP + j]);
+        cpar.resize(cpar.size() + cP);
+        ba_device_params(es.type, es.params.data() + (size_t)e * edge_param_dim(es.type), cpar.data() + cpar.size() - cP);
       }
     }
     auto nz_i = [](std::vector<int>& v) -> std::vector<int>& { if (v.empty()) v.push_back(0); return v; };
@@ -2976,6 +3043,13 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
         throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                           "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the offset and "
                           "bearing edges (edge type " + std::to_string(es.type) + "); use lm_pcg or lm_hip_var");
+  if (use_cgls())
+    for (const HEdgeSet& es : hg.esets)
+      if (is_camparams_type(es.type) && !es.ev0.empty())
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the "
+                          "CameraParameters edges EdgeProjectXYZ2UV / XYZ2UVU (edge type " + std::to_string(es.type) +
+                          "); use lm_pcg6_3 or lm_hip_fix6_3");
   if (use_cgls())
     for (const HEdgeSet& es : hg.esets)
       if (es.type == G2OHIP_E_SE3_EXPMAP && !es.ev0.empty())
@@ -4872,7 +4946,7 @@ double Engine::kernel_bytes(const std::string& name) const {
     for (const EGroup& g : groups)
       // measurement + packed information + intrinsics streamed per edge: 2 + 3 + 4 doubles, stereo 3 + 6 + 5
       if (is_ba_family(g.family)) {
-        const int D = g.D, np = g.family == FAM_BA ? 4 : 5;
+        const int D = g.D, np = g.family == FAM_BA ? 4 : 5;  // (FAM_BA_UVU: f f cx cy b)
         by += g.ne * ((D + D * (D + 1) / 2 + np) * 8.0 + 8 + (ba_fused ? 0.0 : 9.0 + 27.0) * 8 + ob) +
               (ba_fused ? local_lm.size() * 12 * 8.0 : 0.0);
       } else if (is_slam3d_family(g.family)) {
@@ -4895,7 +4969,8 @@ double Engine::kernel_bytes(const std::string& name) const {
     double by = (double)so_.nlm * (4 + 4 + 1 + 2.0 * so_.ld * 8);
     for (int gi : so_.group_of) {
       const EGroup& g = groups[gi];
-      const int np = g.family == FAM_BA ? 4 : g.family == FAM_BA_STEREO ? 5 : g.family == FAM_SE3_XYZ ? 12
+      const int np = g.family == FAM_BA ? 4 : g.family == FAM_BA_STEREO || g.family == FAM_BA_UVU ? 5
+                     : g.family == FAM_SE3_XYZ ? 12
                      : is_slam3d_family(g.family) ? 16 : 0;
       by += g.ne * (8.0 + (g.vtB ? 4.0 : 0.0) + g.D * 8.0 + ((g.ue & 1) ? 0.0 : g.D * (g.D + 1) / 2 * 8.0) +
                     ((g.ue & 2) ? 0.0 : np * 8.0));

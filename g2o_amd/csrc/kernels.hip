@@ -1852,6 +1852,7 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
   switch (family) {
     case FAM_BA: fn(FamilyBA{}); break;
     case FAM_BA_STEREO: fn(FamilyStereo{}); break;
+    case FAM_BA_UVU: fn(FamilyUVU{}); break;
     case FAM_SE3: fn(FamilySE3{}); break;
     case FAM_SE2: fn(FamilySE2{}); break;
     case FAM_SE2XY: fn(FamilySE2XY{}); break;

@@ -20,8 +20,13 @@ enum Family {
   // unary families (BaseUnaryEdge: one vertex, EdgeArgs::v1 / s1 null, DB = 0)
   FAM_U_SE2 = 16, FAM_U_SE2XY = 17, FAM_U_XY = 18, FAM_U_SE3 = 19, FAM_U_XYZ = 20, FAM_U_HOSTJ = 21,
   // pose-only projections on a VertexSE3Expmap camera: EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose
-  FAM_U_POSE_ONLY = 22, FAM_U_STEREO_POSE_ONLY = 23
+  FAM_U_POSE_ONLY = 22, FAM_U_STEREO_POSE_ONLY = 23,
+  // EdgeProjectXYZ2UVU (point, VertexSE3Expmap camera, a CameraParameters record): FamilyUVU. A binary family, as
+  // FAM_BA_STEREO; EdgeProjectXYZ2UV runs as FAM_BA with the record f f cx cy
+  FAM_BA_UVU = 24
 };
+// the fused landmark-major assembly's families (point, VertexSE3Expmap camera)
+inline bool is_ba_family(int f) { return f == FAM_BA || f == FAM_BA_STEREO || f == FAM_BA_UVU; }
 inline bool is_unary_family(int f) { return f >= FAM_U_SE2 && f <= FAM_U_STEREO_POSE_ONLY; }
 inline bool is_pose_only_family(int f) { return f == FAM_U_POSE_ONLY || f == FAM_U_STEREO_POSE_ONLY; }
 inline bool is_hostj_family(int f) { return f == FAM_HOSTJ || f == FAM_U_HOSTJ; }
@@ -100,7 +105,7 @@ struct SchurSplit {
   double* bschur;
   int* fail;             // landmark block not positive definite (informational, as k_schur_prep)
 };
-// family: FAM_BA or FAM_BA_STEREO (the Kt-record variants, sp->kx, are FAM_BA only)
+// family: FAM_BA, FAM_BA_STEREO or FAM_BA_UVU (the Kt-record variants, sp->kx, are FAM_BA only)
 void linearize_fused(int family, const EdgeArgs& a, const int4* chunks, int nchunks, const int* h0, const int* h1,
                      const long long* off_dst, const unsigned char* off_tr, double* off_base, double* off_slot,
                      double* Hll, double* b, int num_poses, int size_poses, int lm_begin, double* lpart,

@@ -66,8 +66,9 @@ struct PointEdge<FAM_BA> {  // FamilyBA::linearize_at
   }
 };
 
-template <>
-struct PointEdge<FAM_BA_STEREO> {  // FamilyStereo::linearize_at
+template <bool UVU>
+struct PointStereo {  // FamilyStereoT<UVU>::linearize_at
+  using F = FamilyStereoT<UVU>;
   static constexpr int D = 3, LD = 3;
   template <bool JAC>
   DI static void eval(const SoGroup& g, int e, const double* p, double* err, double* A) {
@@ -78,9 +79,9 @@ struct PointEdge<FAM_BA_STEREO> {  // FamilyStereo::linearize_at
     pc[0] += c[0]; pc[1] += c[1]; pc[2] += c[2];
     const double* K = so_param(g, e, 5);
     const double* m = g.meas + (size_t)e * 3;
-    FamilyStereo::residual(K, pc, m[0], m[1], m[2], err);
+    F::residual(K, pc, m[0], m[1], m[2], err);
     if (JAC) {
-      const double fx = K[0], fy = K[1], bf = K[4];
+      const double fx = K[0], fy = K[1], bf = F::bf_of(K);
       const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z;
       double R[9];
       quat_to_R(q[0], q[1], q[2], q[3], R);
@@ -93,6 +94,8 @@ struct PointEdge<FAM_BA_STEREO> {  // FamilyStereo::linearize_at
     }
   }
 };
+template <> struct PointEdge<FAM_BA_STEREO> : PointStereo<false> {};
+template <> struct PointEdge<FAM_BA_UVU> : PointStereo<true> {};  // EdgeProjectXYZ2UVU (EdgeProjectXYZ2UV is FAM_BA)
 
 template <int MODE>
 struct PointSlam3d {  // FamilySlam3d<MODE>::linearize, the last three columns of J'
@@ -283,6 +286,7 @@ DI void edge_any(const SoGroup* groups, int2 en, const double* p, double& chi, d
     switch (g.family) {
       case FAM_BA: edge_term<FAM_BA, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_BA_STEREO: edge_term<FAM_BA_STEREO, JAC>(g, en.y, p, chi, H, b); break;
+      case FAM_BA_UVU: edge_term<FAM_BA_UVU, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_SE3_XYZ: edge_term<FAM_SE3_XYZ, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_SE3_XYZ_DEPTH: edge_term<FAM_SE3_XYZ_DEPTH, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_SE3_XYZ_DISPARITY: edge_term<FAM_SE3_XYZ_DISPARITY, JAC>(g, en.y, p, chi, H, b); break;

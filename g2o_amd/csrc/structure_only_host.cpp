@@ -85,7 +85,7 @@ void Engine::so_build_list() {
   };
   for (size_t gi = 0; gi < groups.size() && L.nlm; ++gi) {
     const EGroup& g = groups[gi];
-    const bool lm_first = g.family == FAM_BA || g.family == FAM_BA_STEREO || g.family == FAM_U_XYZ ||
+    const bool lm_first = is_ba_family(g.family) || g.family == FAM_U_XYZ ||
                           g.family == FAM_U_XY || is_sba_family(g.family);
     const bool lm_second = is_lm_second_family(g.family);
     for (int k = 0; k < g.ne; ++k) {

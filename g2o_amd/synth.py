@@ -60,21 +60,26 @@ E_PROJECT_P2MC, E_PROJECT_P2SC = 11, 12
 # EdgeSE3Offset / EdgeSE2Offset between two poses (params: the from vertex's sensor offset, then the to vertex's),
 # EdgeSE2PointXYBearing from a V_SE2 pose to a V_XY point (one angle, no params)
 E_SE3_OFFSET, E_SE2_OFFSET, E_SE2_XY_BEARING = 13, 14, 15
+# g2o's own BA edges on a CameraParameters parameter: EdgeProjectXYZ2UV (u v), EdgeProjectXYZ2UVU (u v u_r); v0 a V_XYZ
+# point, v1 a V_SE3_EXPMAP camera; params focal_length cx cy baseline
+E_PROJECT_XYZ2UV, E_PROJECT_XYZ2UVU = 23, 24
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
             E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
             E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
-            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 7, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1}
+            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 7, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
+            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
            E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
-           E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 6, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1}
+           E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 6, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
+           E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3}
 # parameter values per edge of the types that take a record (EdgeSet.params; where None is allowed it is the identity)
 PARAM_DIM = {E_SE3_PROJECT_XYZ: 4, E_STEREO_SE3_PROJECT_XYZ: 5, E_SE3_PRIOR: 7, E_SE3_XYZ: 7, E_SE3_XYZ_DEPTH: 11,
              E_SE3_XYZ_DISPARITY: 11, E_SE3_PROJECT_XYZ_ONLYPOSE: 7, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 8,
-             E_SE3_OFFSET: 14, E_SE2_OFFSET: 6}
+             E_SE3_OFFSET: 14, E_SE2_OFFSET: 6, E_PROJECT_XYZ2UV: 4, E_PROJECT_XYZ2UVU: 4}
 # the vertex type a unary edge type attaches to
 PRIOR_VERTEX = {E_SE2_PRIOR: V_SE2, E_SE2_XY_PRIOR: V_SE2, E_XY_PRIOR: V_XY, E_SE3_PRIOR: V_SE3_QUAT, E_XYZ_PRIOR: V_XYZ}
 # the same for the pose-only projections, and the binary projection each of them is the pose-only form of
@@ -102,7 +107,8 @@ class EdgeSet:
     # float64 [n, 4] (fx fy cx cy) for projection edges, [n, 5] (+ bf) for stereo, [n, 7] (offset x y z qx qy qz qw)
     # or None (identity) for SE3 priors and E_SE3_XYZ, [n, 11] (offset, fx fy cx cy) for E_SE3_XYZ_DEPTH / _DISPARITY,
     # [n, 7] (Xw fx fy cx cy) / [n, 8] (+ bf) for the pose-only projections, [n, 14] / [n, 6] (the from vertex's offset,
-    # then the to vertex's; or None, both the identity) for E_SE3_OFFSET / E_SE2_OFFSET
+    # then the to vertex's; or None, both the identity) for E_SE3_OFFSET / E_SE2_OFFSET, [n, 4] (focal_length cx cy
+    # baseline) for E_PROJECT_XYZ2UV / E_PROJECT_XYZ2UVU
     params: np.ndarray | None = None
 
 
@@ -571,6 +577,68 @@ def sba_twin(prob: Problem) -> Problem:
         else:
             edges.append(es)
     return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)
+
+
+def ba_camparams(num_cameras: int = 1000, num_points: int = 100_000, obs_per_point: int = 10, window: int = 64,
+                 stereo: bool = False, stereo_fraction: float | None = None, focal: float = 1000.0,
+                 baseline: float = 0.1, pixel_noise: float = 1.0, cam_rot_noise: float = 0.002,
+                 cam_trans_noise: float = 0.01, point_noise: float = 0.05, fixed_cameras: int | None = None,
+                 seed: int = SEED, disparity_noise: float = 1.0, info: np.ndarray | None = None) -> Problem:
+    """The scene of :func:`ba` (same cameras, points, estimates and pixel noise) in g2o's own BA types, as upstream
+    ba_demo builds it: EdgeProjectXYZ2UV observations (u, v) or, with ``stereo``, EdgeProjectXYZ2UVU ones (u, v, u_r)
+    with u_r = (x - baseline) / z * focal + cx + noise (the noise, sigma ``disparity_noise``, from ba_stereo's stream).
+    Every edge names one CameraParameters record ``focal cx cy baseline`` (cx = 320, cy = 240).  ``info`` is the
+    information of every stereo edge (default I3).  With ``stereo_fraction`` that fraction of the observations (chosen
+    as ba_stereo chooses them) is XYZ2UVU and the rest XYZ2UV in a second EdgeSet.  Two cameras are fixed for a purely
+    monocular graph, one otherwise, unless ``fixed_cameras`` says otherwise."""
+    frac = (1.0 if stereo else 0.0) if stereo_fraction is None else float(stereo_fraction)
+    nf = (2 if frac <= 0.0 else 1) if fixed_cameras is None else fixed_cameras
+    prob, pc, uv_true = _ba_scene(num_cameras, num_points, obs_per_point, window, pixel_noise, cam_rot_noise,
+                                  cam_trans_noise, point_noise, nf, seed)
+    mono = prob.edges[0]
+    m = len(mono.v0)
+    cx, cy = mono.params[0, 2], mono.params[0, 3]
+    f, b = float(focal), float(baseline)
+    noise = mono.meas - uv_true  # _ba_scene's pixel noise, whatever its focal length
+    uv = np.stack([pc[:, 0] / pc[:, 2] * f + cx, pc[:, 1] / pc[:, 2] * f + cy], axis=1) + noise
+    ur = (pc[:, 0] - b) / pc[:, 2] * f + cx + _rng(seed, 5).standard_normal(m) * disparity_noise
+    if frac >= 1.0:
+        st = np.ones(m, bool)
+    elif frac <= 0.0:
+        st = np.zeros(m, bool)
+    else:
+        st = _rng(seed, 6).random(m) < frac
+    ns = int(st.sum())
+    rec = np.array([f, cx, cy, b])
+    edges = []
+    if ns:
+        om = np.eye(3) if info is None else np.asarray(info, np.float64).reshape(3, 3)
+        edges.append(EdgeSet(E_PROJECT_XYZ2UVU, mono.v0[st].copy(), mono.v1[st].copy(),
+                             np.concatenate([uv[st], ur[st, None]], axis=1), np.broadcast_to(om, (ns, 3, 3)).copy(),
+                             np.broadcast_to(rec, (ns, 4)).copy()))
+    if ns < m:
+        edges.append(EdgeSet(E_PROJECT_XYZ2UV, mono.v0[~st].copy(), mono.v1[~st].copy(), uv[~st].copy(),
+                             mono.info[~st].copy(), np.broadcast_to(rec, (m - ns, 4)).copy()))
+    return Problem(prob.name + f"_camparams{frac:g}", prob.vertices, edges, 6, 3)
+
+
+def camparams_twin(prob: Problem) -> Problem:
+    """The same graph in the fork's types: every E_PROJECT_XYZ2UV set as E_SE3_PROJECT_XYZ with fx fy cx cy =
+    f f cx cy, every E_PROJECT_XYZ2UVU set as E_STEREO_SE3_PROJECT_XYZ with bf = f * b.  The monocular twin computes
+    the same numbers; the stereo twin's error differs in its rounding (a float bf, u - bf / z)."""
+    edges = []
+    for es in prob.edges:
+        if es.etype == E_PROJECT_XYZ2UV:
+            f, cx, cy = es.params[:, 0], es.params[:, 1], es.params[:, 2]
+            edges.append(EdgeSet(E_SE3_PROJECT_XYZ, es.v0.copy(), es.v1.copy(), es.meas.copy(), es.info.copy(),
+                                 np.stack([f, f, cx, cy], axis=1)))
+        elif es.etype == E_PROJECT_XYZ2UVU:
+            f, cx, cy, b = es.params[:, 0], es.params[:, 1], es.params[:, 2], es.params[:, 3]
+            edges.append(EdgeSet(E_STEREO_SE3_PROJECT_XYZ, es.v0.copy(), es.v1.copy(), es.meas.copy(), es.info.copy(),
+                                 np.stack([f, f, cx, cy, f * b], axis=1)))
+        else:
+            edges.append(es)
+    return Problem(prob.name + "/twin", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)
 
 
 def by_name(name: str, scale: str = "full") -> Problem:

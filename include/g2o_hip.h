@@ -143,6 +143,25 @@ extern "C" {
                                     u_l v u_r; info 3x3; params Xw fx fy cx cy bf (n*8). As the reference's cam_project
                                     keeps 1/z in a float (.cpp:602), the error sees 1/z rounded to float, the Jacobian
                                     the double */
+/* ---- g2o's own BA edges on a CameraParameters parameter (what upstream ba_demo builds): v0 the point (G2OHIP_V_XYZ),
+ * v1 the camera (G2OHIP_V_SE3_EXPMAP), in g2o's vertex order. params: n*4, one CameraParameters per edge,
+ * focal_length cx cy baseline (types_six_dof_expmap.h:42-78); NULL is G2OHIP_ERR_ARG. Edges whose records are all equal
+ * share one record on the device. Error with pc = R p + t (SE3Quat::map), all doubles, in the operation order of
+ * cam_map / stereocam_uvu_map (types_six_dof_expmap.cpp:74-87). Neither type has an isDepthPositive: depth_positive /
+ * check_depth are G2OHIP_ERR_ARG. Alone in a graph either type takes the fused landmark-major assembly, mixed with any
+ * other edge type the generic slot path; lm_pcg6_3_eigen refuses them. ---- */
+#define G2OHIP_E_PROJECT_XYZ2UV 23  /* EdgeProjectXYZ2UV, types_six_dof_expmap.h:130-152: meas u v; info 2x2;
+                                    e = (u - (pc.x/pc.z*f + cx), v - (pc.y/pc.z*f + cy)); the analytic Jacobians of
+                                    .cpp:295-333 (G2OHIP_E_SE3_PROJECT_XYZ's with fx = fy = f). The baseline never
+                                    enters; it stays on the host and g2ohip_save_g2o writes it back */
+#define G2OHIP_E_PROJECT_XYZ2UVU 24 /* EdgeProjectXYZ2UVU, types_six_dof_expmap.h:178-198: meas u v u_r; info 3x3; rows
+                                    0-1 as G2OHIP_E_PROJECT_XYZ2UV, row 2 = u_r - ((pc.x - b)/pc.z*f + cx), b the double
+                                    as given (not G2OHIP_E_STEREO_SE3_PROJECT_XYZ's error: no float-rounded bf, and
+                                    (x - b)/z*f instead of u - bf/z). The reference has no linearizeOplus for this edge
+                                    (commented out, .h:196) and differentiates numerically; the device uses the exact
+                                    first derivatives: rows 0-1 as XYZ2UV, row 2 = -(f/z, 0, -f(x - b)/z^2) applied to
+                                    R for the point and to [-[pc]x | I] in (omega, upsilon) order for the camera, i.e.
+                                    G2OHIP_E_STEREO_SE3_PROJECT_XYZ's row 2 with bf = f*b */
 /* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3 or 6 (an edge type of the application's own, say): the
  * host supplies the error and the Jacobian as for G2OHIP_E_HOSTJ, payload [e (D) | Ji (D x dim(v0))] row-major per
  * edge. meas unused (may be NULL); info D*D. */
@@ -209,11 +228,16 @@ int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int*
 /* params: the intrinsics of the projection types (G2OHIP_ERR_ARG when one of them gets NULL), the offsets of
  * G2OHIP_E_SE3_PRIOR and G2OHIP_E_SE3_XYZ (n*7, or NULL: identity), offset + intrinsics of G2OHIP_E_SE3_XYZ_DEPTH /
  * _DISPARITY (n*11, NULL is G2OHIP_ERR_ARG), the point and intrinsics of the pose-only projections (Xw fx fy cx cy,
- * n*7, stereo + bf, n*8; NULL is G2OHIP_ERR_ARG), NULL for the others (G2OHIP_E_SE3_EXPMAP among them). v1: NULL for the unary types (and only for them). */
+ * n*7, stereo + bf, n*8; NULL is G2OHIP_ERR_ARG), the CameraParameters of G2OHIP_E_PROJECT_XYZ2UV / _XYZ2UVU (f cx cy
+ * baseline, n*4; NULL is G2OHIP_ERR_ARG), NULL for the others (G2OHIP_E_SE3_EXPMAP among them). v1: NULL for the unary types (and only for them). */
 /* .g2o files do not carry G2OHIP_E_STEREO_SE3_PROJECT_XYZ: the reference's reader and writer for its tag
  * (EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP, types_six_dof_expmap.cpp:469-493) move four measurement values through a
  * 3-vector and no intrinsics. The loader skips the tag like any unknown one; g2ohip_save_g2o on a graph that holds
- * such edges writes nothing and returns G2OHIP_ERR_UNSUPPORTED (g2ohip_last_error says why). */
+ * such edges writes nothing and returns G2OHIP_ERR_UNSUPPORTED (g2ohip_last_error says why).
+ * Nor do they carry G2OHIP_E_PROJECT_XYZ2UVU: the reference's reader for EDGE_PROJECT_XYZ2UVU:EXPMAP
+ * (types_six_dof_expmap.cpp:335-346) reads no parameter id, so a loaded edge has no camera and addEdge rejects it
+ * (optimizable_graph.cpp:277-280). The loader always skips the tag; g2ohip_save_g2o on a graph that holds such edges
+ * writes nothing and returns G2OHIP_ERR_UNSUPPORTED. */
 int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
 /* g2ohip_load_g2o with flags. G2OHIP_LOAD_UNARY: the unary tags EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY, EDGE_PRIOR_XY,
  * EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR and the PARAMS_SE3OFFSET lines the last one refers to are parsed (by the same
@@ -249,6 +273,12 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * load, g2ohip_last_error naming the tag or the id. Without the flag the three edge tags and PARAMS_SE2OFFSET are
  * skipped like any unknown one. */
 #define G2OHIP_LOAD_OFFSET 16u
+/* G2OHIP_LOAD_CAMERAPARAMS (may be combined with the other flags): PARAMS_CAMERAPARAMETERS id focal_length cx cy
+ * baseline is read; EDGE_PROJECT_XYZ2UV:EXPMAP v0 v1 paramId u v info00 info01 info11 (types_six_dof_expmap.cpp:248-263)
+ * loads as G2OHIP_E_PROJECT_XYZ2UV. A parameter id no line defines or one of another kind, an endpoint that is missing
+ * or of the wrong type and a short line fail the load, g2ohip_last_error naming the tag or the id. Without the flag
+ * both tags are skipped like any unknown one. */
+#define G2OHIP_LOAD_CAMERAPARAMS 32u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
@@ -265,7 +295,10 @@ int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, u
  * the identity is not written (G2OHIP_ERR_UNSUPPORTED, nothing written). G2OHIP_E_SE3_OFFSET / _SE2_OFFSET edges are
  * written as EDGE_SE3_OFFSET / EDGE_SE2_OFFSET v0 v1 pidFrom pidTo, the measurement and the upper triangle of the
  * information (edge_se3_offset.cpp:90-100, edge_se2_offset.cpp:86-94), with one PARAMS_SE3OFFSET / PARAMS_SE2OFFSET
- * line per distinct offset in the same id space; G2OHIP_E_SE2_XY_BEARING as EDGE_BEARING_SE2_XY v0 v1 angle info00. */
+ * line per distinct offset in the same id space; G2OHIP_E_SE2_XY_BEARING as EDGE_BEARING_SE2_XY v0 v1 angle info00.
+ * G2OHIP_E_PROJECT_XYZ2UV edges are written as EDGE_PROJECT_XYZ2UV:EXPMAP v0 v1 paramId u v and the upper triangle of
+ * the information (types_six_dof_expmap.cpp:265-276), with one PARAMS_CAMERAPARAMETERS id focal_length cx cy baseline
+ * line per distinct record in the same id space. */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
