@@ -72,6 +72,20 @@ EDGE_TAGS = {E_SE3_OFFSET: "EDGE_SE3_OFFSET", E_SE2_OFFSET: "EDGE_SE2_OFFSET", E
 E_PROJECT_XYZ2UV, E_PROJECT_XYZ2UVU = 23, 24
 
 
+# types_icp (include/g2o_hip.h G2OHIP_E_V_V_GICP, G2OHIP_E_XYZ_VSC): Edge_V_V_GICP between two V_SE3_QUAT (meas [n, 12]
+# pos0 normal0 pos1 normal1, info [n, 3, 3] the point-to-plane information, params None; or params [n, 12], cov0 then
+# cov1 as packed upper triangles 00 01 11 02 12 22: the whole set plane-to-plane, info may then be None);
+# Edge_XYZ_VSC from a V_XYZ point to a V_SE3_QUAT camera standing for the VertexSCam (meas u v u_r, params [n, 5]
+# fx fy cx cy baseline). ICP_EDGE_TAGS: the .g2o tag (Edge_XYZ_VSC has none: the reference's read / write return false);
+# kept beside EDGE_TAGS, which holds the offset and bearing tags alone
+E_V_V_GICP, E_XYZ_VSC = 25, 26
+ICP_EDGE_TAGS = {E_V_V_GICP: "EDGE_V_V_GICP"}
+
+
+# EdgeGICP::prec0 / cov0 in numpy, and the packed form of the covariances (ValueError on a normal parallel to (0,1,0))
+gicp_prec, gicp_cov, gicp_pack = synth.gicp_prec, synth.gicp_cov, synth.gicp_pack
+
+
 # edge types the device does not know: host-supplied error + Jacobians (include/g2o_hip.h G2OHIP_E_HOSTJ)
 def E_HOSTJ(D: int) -> int:
     return 32 + D
@@ -98,6 +112,7 @@ LOAD_EXPMAP = 4
 LOAD_SBA = 8
 LOAD_OFFSET = 16
 LOAD_CAMERAPARAMS = 32
+LOAD_ICP = 64
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -126,7 +141,7 @@ EXPORTS = [
     "g2ohip_measure_peaks", "g2ohip_set_dogleg_params", "g2ohip_dogleg_state", "g2ohip_dogleg_blend",
     "g2ohip_dogleg_next_delta", "g2ohip_structure_only_calc",
     "g2ohip_set_edge_levels", "g2ohip_get_edge_levels", "g2ohip_initialize_level", "g2ohip_edge_chi2",
-    "g2ohip_classify_edges",
+    "g2ohip_classify_edges", "g2ohip_set_pair_major", "g2ohip_pair_major_info",
 ]
 
 # G2OHIP_LEVEL_KEEP: classify_edges leaves the level of the edges on that side as it is
@@ -221,6 +236,8 @@ def lib() -> C.CDLL:
         "g2ohip_lm_scale_factor": ([D], D),
         "g2ohip_measure_peaks": ([I, P, I], I),
         "g2ohip_set_dogleg_params": ([P, D, I, D, D], I),
+        "g2ohip_set_pair_major": ([P, I], I),
+        "g2ohip_pair_major_info": ([P, P], I),
         "g2ohip_dogleg_state": ([P, P, I], I),
         "g2ohip_dogleg_blend": ([D, D, D, D, D, D, P], I),
         "g2ohip_dogleg_next_delta": ([D, D, D], D),
@@ -404,9 +421,17 @@ class SparseOptimizer:
         v0 = np.ascontiguousarray(es.v0, np.int32)
         v1 = None if es.v1 is None else np.ascontiguousarray(es.v1, np.int32)  # None: a unary edge type
         meas = None if es.meas is None else np.ascontiguousarray(es.meas, np.float64)
-        info = np.ascontiguousarray(es.info, np.float64)
+        info = None if es.info is None else np.ascontiguousarray(es.info, np.float64)  # None: plane-to-plane GICP only
         par = None if es.params is None else np.ascontiguousarray(es.params, np.float64)
         pd = synth.PARAM_DIM.get(es.etype)
+        md, D = synth.MEAS_DIM.get(es.etype), synth.ERR_DIM.get(es.etype)
+        if es.etype in (E_V_V_GICP, E_XYZ_VSC):  # the C side reads n * md and n * D * D doubles
+            if meas is None or meas.size != len(v0) * md:
+                raise G2OHipError(f"add_edges: edge type {es.etype} takes {md} measurement values per edge, got "
+                                  f"{0 if meas is None else meas.size} for {len(v0)} edges")
+            if info is not None and info.size != len(v0) * D * D:
+                raise G2OHipError(f"add_edges: edge type {es.etype} takes a {D}x{D} information per edge, got "
+                                  f"{info.size} values for {len(v0)} edges")
         if par is not None and pd is not None and par.size != len(v0) * pd:  # the C side reads n * pd doubles
             raise G2OHipError(f"add_edges: edge type {es.etype} takes {pd} parameter values per edge, got {par.size} "
                               f"for {len(v0)} edges")
@@ -461,16 +486,19 @@ class SparseOptimizer:
         _check(lib().g2ohip_set_estimates(self.h, vtype, _p(est)), "set_estimates")
 
     def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False,
-             expmap: bool = False, sba: bool = False, offset: bool = False, camparams: bool = False):
+             expmap: bool = False, sba: bool = False, offset: bool = False, camparams: bool = False,
+             icp: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
         EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
         (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
         PARAMS_CAMERACALIB), expmap=True EDGE_SE3:EXPMAP, sba=True the sba tags (VERTEX_CAM, EDGE_PROJECT_P2MC,
         EDGE_PROJECT_P2SC), offset=True the offset and bearing tags (EDGE_SE3_OFFSET, EDGE_SE2_OFFSET,
         EDGE_BEARING_SE2_XY + PARAMS_SE3OFFSET, PARAMS_SE2OFFSET), camparams=True g2o's own BA tags
-        (EDGE_PROJECT_XYZ2UV:EXPMAP + PARAMS_CAMERAPARAMETERS); all are skipped otherwise."""
+        (EDGE_PROJECT_XYZ2UV:EXPMAP + PARAMS_CAMERAPARAMETERS), icp=True EDGE_V_V_GICP (point-to-plane, the information
+        Edge_V_V_GICP::read builds; a normal0 parallel to (0,1,0) fails the load); all are skipped otherwise."""
         flags = ((LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0) |
-                 (LOAD_SBA if sba else 0) | (LOAD_OFFSET if offset else 0) | (LOAD_CAMERAPARAMS if camparams else 0))
+                 (LOAD_SBA if sba else 0) | (LOAD_OFFSET if offset else 0) | (LOAD_CAMERAPARAMS if camparams else 0) |
+                 (LOAD_ICP if icp else 0))
         _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:
@@ -492,6 +520,16 @@ class SparseOptimizer:
 
     def set_algorithm(self, name: str):
         _check(lib().g2ohip_set_algorithm(self.h, name.encode()), "set_algorithm")
+
+    def set_pair_major(self, enable: bool = True):
+        """g2ohip_set_pair_major: False keeps a graph of Edge_V_V_GICP edges on the generic slot path."""
+        _check(lib().g2ohip_set_pair_major(self.h, int(bool(enable))), "set_pair_major")
+
+    def pair_major_info(self) -> dict:
+        """After a structure build: whether it is pair-major, and its pairs and chunks."""
+        out = np.zeros(3, np.int32)
+        _check(lib().g2ohip_pair_major_info(self.h, _p(out)), "pair_major_info")
+        return dict(pair_major=bool(out[0]), pairs=int(out[1]), chunks=int(out[2]))
 
     def set_dogleg_params(self, initial_delta: float = 0.0, max_trials: int = 0, initial_lambda: float = 0.0,
                           lambda_factor: float = 0.0):

@@ -99,7 +99,8 @@ int g2ohip_add_vertices(g2ohip_graph* g, int type, int n, const int* ids, const 
 }
 int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int* v1, const double* meas,
                      const double* info, const double* params) {
-  if (!g || (n > 0 && (!v0 || !info))) return G2OHIP_ERR_ARG;  // v1: NULL for the unary types only (Engine::add_edges)
+  // v1: NULL for the unary types only; info: NULL for a plane-to-plane Edge_V_V_GICP set only (Engine::add_edges)
+  if (!g || (n > 0 && (!v0 || (!info && !(type == G2OHIP_E_V_V_GICP && params))))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->add_edges(type, n, v0, v1, meas, info, params); });
 }
 int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
@@ -108,7 +109,7 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
 }
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
   if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP | G2OHIP_LOAD_SBA |
-                                    G2OHIP_LOAD_OFFSET | G2OHIP_LOAD_CAMERAPARAMS))) return G2OHIP_ERR_ARG;
+                                    G2OHIP_LOAD_OFFSET | G2OHIP_LOAD_CAMERAPARAMS | G2OHIP_LOAD_ICP))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
@@ -127,6 +128,13 @@ int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
     g_err = "g2ohip_save_g2o: the graph holds " + std::to_string(es->ev0.size()) +
             " EdgeProjectXYZ2UVU edges, which the .g2o format cannot carry (the reference's reader for "
             "EDGE_PROJECT_XYZ2UVU:EXPMAP reads no CameraParameters id, so the graph drops the edge)";
+    return G2OHIP_ERR_UNSUPPORTED;
+  }
+  // Edge_XYZ_VSC likewise: the reference's read and write return false (types_icp.cpp), no file holds the type
+  if (const auto* es = g->e->hg.set_of(G2OHIP_E_XYZ_VSC); es && !es->ev0.empty()) {
+    g_err = "g2ohip_save_g2o: the graph holds " + std::to_string(es->ev0.size()) +
+            " Edge_XYZ_VSC edges, which the .g2o format cannot carry (the reference's Edge_XYZ_VSC::read and ::write "
+            "return false)";
     return G2OHIP_ERR_UNSUPPORTED;
   }
   // the pose-only projections likewise: their tags carry neither the point Xw nor the intrinsics
@@ -206,6 +214,14 @@ int g2ohip_set_algorithm(g2ohip_graph* g, const char* name) {
                : m == "str" ? g2ohip::Engine::Algo::StructureOnly
                             : g2ohip::Engine::Algo::GaussNewton;
   return G2OHIP_OK;
+}
+int g2ohip_set_pair_major(g2ohip_graph* g, int enable) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->set_pair_major(enable); });
+}
+int g2ohip_pair_major_info(g2ohip_graph* g, int* out) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->pair_major_info(out); });
 }
 int g2ohip_set_dogleg_params(g2ohip_graph* g, double initial_delta, int max_trials_after_failure, double initial_lambda,
                              double lambda_factor) {

@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(CL_BLOCK) k_classify(EdgeData d, int ne, launc
     if constexpr (has_depth<F>::value) z = F::depth(d, e, err);
     else F::error(d, e, err);
     double Om[F::D * F::D];
-    load_info<F::D>(info_rec(d, e, F::INFO), Om);
+    family_info<F>(d, e, Om);
 #pragma unroll
     for (int i = 0; i < F::D; ++i) {
       double r = 0;
@@ -133,6 +133,8 @@ void classify(int family, const EdgeArgs& a, int ne, const ClassifyArgs& c, hipS
     case FAM_SE3_OFFSET: classify_launch<FamilySE3Offset>(d, ne, c, s); break;
     case FAM_SE2_OFFSET: classify_launch<FamilySE2Offset>(d, ne, c, s); break;
     case FAM_SE2XY_BEARING: classify_launch<FamilySE2XYBearing>(d, ne, c, s); break;
+    case FAM_GICP: classify_launch<FamilyGICP>(d, ne, c, s); break;
+    case FAM_VSC: classify_launch<FamilyVSC>(d, ne, c, s); break;
     case FAM_U_SE2: classify_launch<FamilyUnarySE2>(d, ne, c, s); break;
     case FAM_U_SE2XY: classify_launch<FamilyUnarySE2XY>(d, ne, c, s); break;
     case FAM_U_XY: classify_launch<FamilyUnaryXY>(d, ne, c, s); break;

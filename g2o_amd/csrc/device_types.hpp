@@ -11,6 +11,7 @@
 //   EdgeSE3Offset      types/slam3d/edge_se3_offset.cpp:102-132, isometry3d_gradients.h:84-189 (the Pi / Pj overload)
 //   EdgeSE2Offset      types/slam2d/edge_se2_offset.cpp:102-106, parameter_se2_offset.cpp:76-86 (no analytic Jacobian)
 //   EdgeSE2PointXYBearing  types/slam2d/edge_se2_pointxy_bearing.h:43-50 (no analytic Jacobian)
+//   Edge_V_V_GICP      types/icp/types_icp.h:161-238, types_icp.cpp:49-57, 163-203
 //   unary priors       types/slam2d/edge_se2_prior.h:39-77, edge_se2_xyprior.h:39-71, edge_xy_prior.h,
 //                      types/slam3d/edge_se3_prior.cpp:89-102 (isometry3d_gradients.h:265-325), edge_xyz_prior.cpp:63-70
 //   oplus             types_six_dof_expmap.h:97-100 (SE3Quat::exp * T, se3quat.h:217-257),
@@ -25,6 +26,8 @@
 // Jacobians are produced row-major (D x dim) in registers; nothing is stored.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace g2ohip {
 namespace dev {
@@ -251,7 +254,8 @@ struct EdgeData {
   const double* s1;         // state array of vertex-1 type
   int rk;                   // robust kernel of the edge set (G2OHIP_RK_*), 0 none
   double rk_delta;          // RobustKernel::delta
-  int ue = 0;               // uniform records: bit 0 one information record for every edge, bit 1 one intrinsics record
+  int ue = 0;               // uniform records: bit 0 one information record for every edge, bit 1 one intrinsics record;
+                            // bit 2: the Edge_V_V_GICP set is plane-to-plane (params = cov0 | cov1, Omega from the state)
 };
 // an edge's packed information / intrinsics record (a single shared record when the edge group's are all equal)
 DI const double* info_rec(const EdgeData& d, int e, int stride) {
@@ -343,6 +347,37 @@ DI void load_info(const double* p, double* Om) {  // packed upper -> full row-ma
       Om[r * D + c] = v;
       Om[c * D + r] = v;
     }
+}
+
+// The information of an edge, full row-major. A family whose information depends on the state (Edge_V_V_GICP in
+// plane-to-plane mode) forms it in F::information(d, e, Om); every other family reads its packed record. Every kernel
+// that needs a binary or unary family's Omega takes it from here.
+template <class F, class = void>
+struct has_information : std::false_type {};
+template <class F>
+struct has_information<F, std::void_t<decltype(&F::information)>> : std::true_type {};
+template <class F>
+DI void family_info(const EdgeData& d, int e, double* Om) {
+  if constexpr (has_information<F>::value) F::information(d, e, Om);
+  else load_info<F::D>(info_rec(d, e, F::INFO), Om);
+}
+
+// Eigen's fixed-size 3x3 inverse (compute_inverse_size3: cofactors over the determinant expanded along column 0), as
+// k_schur_prep restates it; a and out row-major
+DI void inv3_cofactor(const double* a, double* out) {
+  auto m = [&](int r, int c) { return a[r * 3 + c]; };
+  const double c00 = m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1);
+  const double c10 = m(0, 2) * m(2, 1) - m(0, 1) * m(2, 2);
+  const double c20 = m(0, 1) * m(1, 2) - m(0, 2) * m(1, 1);
+  const double det = c00 * m(0, 0) + c10 * m(1, 0) + c20 * m(2, 0);
+  const double inv = 1.0 / det;
+  out[0] = c00 * inv; out[1] = c10 * inv; out[2] = c20 * inv;
+  out[3] = (m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2)) * inv;
+  out[4] = (m(0, 0) * m(2, 2) - m(0, 2) * m(2, 0)) * inv;
+  out[5] = (m(0, 2) * m(1, 0) - m(0, 0) * m(1, 2)) * inv;
+  out[6] = (m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0)) * inv;
+  out[7] = (m(0, 1) * m(2, 0) - m(0, 0) * m(2, 1)) * inv;
+  out[8] = (m(0, 0) * m(1, 1) - m(0, 1) * m(1, 0)) * inv;
 }
 
 // ---- EdgeSE3ProjectXYZ: v0 = point (3), v1 = camera SE3Quat (6) ----
@@ -1156,6 +1191,166 @@ struct FamilySE2XYBearing {
     Ji[1] = -Jj[1];
     Ji[2] = 1.0;
   }
+};
+
+// ---- Edge_V_V_GICP (types/icp/types_icp.h:161-238, types_icp.cpp:163-203): two VertexSE3 (Isometry3 states). meas
+// payload = pos0 | pos1 [6] (the normals stay on the host), info packed upper 6 (the point-to-plane information).
+// error = T0^-1 * (T1 * pos1) - pos0 in computeError's association. The reference's analytic Jacobians
+// (GICP_ANALYTIC_JACOBIANS): Ji = [-I | dRidx p1t, dRidy p1t, dRidz p1t] with p1t = (T0^-1 T1) pos1,
+// Jj = [R01 | R01 dRidx^T pos1, R01 dRidy^T pos1, R01 dRidz^T pos1] with R01 = R0^T R1; the three constant matrices
+// (types_icp.cpp:49-57, antisymmetric with entries +-2) are written out as their products with a vector.
+// Plane-to-plane (EdgeData::ue bit 2, the whole edge set; the reference keeps pl_pl per edge): the parameter record is
+// cov0 | cov1, each packed upper 6, and Omega = (cov0 + R01 cov1 R01^T)^-1 at the current state
+// (types_icp.h:220-226), Eigen's 3x3 cofactor inverse. The Jacobians ignore Omega's dependence on the state, as the
+// reference's do. ----
+struct FamilyGICP {
+  static constexpr int D = 3, DA = 6, DB = 6, MEAS = 6, INFO = 6, PAR = 12;
+  // W = T0^-1 (inverse first, as Isometry3::inverse), X1 = T1
+  DI static void load(const EdgeData& d, int e, double* W, double* X1) {
+    const double* x0 = d.s0 + (size_t)d.v0[e] * 12;
+    const double* x1 = d.s1 + (size_t)d.v1[e] * 12;
+    double X0[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { X0[k] = x0[k]; X1[k] = x1[k]; }
+    iso_inv(X0, W);
+  }
+  DI static void apply(const double* T, const double* p, double* o) {  // linear() * p + translation()
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = T[i * 3] * p[0] + T[i * 3 + 1] * p[1] + T[i * 3 + 2] * p[2] + T[9 + i];
+  }
+  DI static void error_of(const EdgeData& d, int e, const double* W, const double* X1, double* p1, double* err) {
+    const double* m = d.meas + (size_t)e * MEAS;
+    p1[0] = m[3]; p1[1] = m[4]; p1[2] = m[5];
+    double pw[3], pl[3];
+    apply(X1, p1, pw);
+    apply(W, pw, pl);
+    err[0] = pl[0] - m[0]; err[1] = pl[1] - m[1]; err[2] = pl[2] - m[2];
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double W[12], X1[12], p1[3];
+    load(d, e, W, X1);
+    error_of(d, e, W, X1, p1, err);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    double W[12], X1[12], p1[3], T01[12], pt[3];
+    load(d, e, W, X1);
+    error_of(d, e, W, X1, p1, err);
+    iso_mul(W, X1, T01);
+    apply(T01, p1, pt);
+    const double x = 2 * pt[0], y = 2 * pt[1], z = 2 * pt[2];
+    // dRidx p = (0, 2 pz, -2 py), dRidy p = (-2 pz, 0, 2 px), dRidz p = (2 py, -2 px, 0)
+    const double ci[9] = {0, -z, y, z, 0, -x, -y, x, 0};  // row r: (dRidx p, dRidy p, dRidz p)[r]
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        Ji[r * 6 + c] = r == c ? -1.0 : 0.0;
+        Ji[r * 6 + 3 + c] = ci[r * 3 + c];
+        Jj[r * 6 + c] = T01[r * 3 + c];
+      }
+    // dRid{x,y,z}^T pos1 = -(dRid{x,y,z} pos1): the columns of -[2 pos1]x ordered as above
+    const double X = 2 * p1[0], Y = 2 * p1[1], Z = 2 * p1[2];
+    const double cj[9] = {0, Z, -Y, -Z, 0, X, Y, -X, 0};
+    double M[9];
+    mat3mul(T01, cj, M);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Jj[r * 6 + 3 + c] = M[r * 3 + c];
+  }
+  DI static void information(const EdgeData& d, int e, double* Om) {
+    if (!(d.ue & 4)) {  // point-to-plane: the caller's record
+      load_info<3>(info_rec(d, e, INFO), Om);
+      return;
+    }
+    double W[12], X1[12], R[9], C0[9], C1[9], T[9], S[9];
+    load(d, e, W, X1);
+    mat3mul(W, X1, R);  // R01
+    const double* c = param_rec(d, e, PAR);
+    load_info<3>(c, C0);
+    load_info<3>(c + 6, C1);
+    mat3mul(R, C1, T);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)  // cov0 + (R cov1) R^T
+        S[i * 3 + j] = C0[i * 3 + j] + (T[i * 3] * R[j * 3] + T[i * 3 + 1] * R[j * 3 + 1] + T[i * 3 + 2] * R[j * 3 + 2]);
+    inv3_cofactor(S, Om);
+  }
+};
+
+// ---- Edge_XYZ_VSC (types/icp/types_icp.h:247-407): v0 = point (3), v1 = VertexSCam, a VertexSE3 (Isometry3 state,
+// camera-to-world) whose cached w2n / w2i are recomputed here from the state. meas u v u_r, info packed upper 6, the
+// parameter record fx fy cx cy baseline (VertexSCam's static Kcam and baseline; one shared record when EdgeData::ue
+// bit 1 is set). error = mapPoint(point) - measurement in mapPoint's order: w2n = T^-1, w2i = Kcam w2n formed first,
+// (u, v) = (w2i pt)_01 / (w2i pt)_2, u_r from Kcam (w2n pt - (b, 0, 0)). The reference differentiates numerically
+// (SCAM_ANALYTIC_JACOBIANS is commented out); these are the exact first derivatives: with pc = w2n pt and P the
+// projection's 3x3 derivative at pc, A = P R^T (point) and B = P [-I | 2 [pc]x] (VertexSE3's oplus: the translation,
+// then the quaternion's x y z). ----
+struct FamilyVSC {
+  static constexpr int D = 3, DA = 3, DB = 6, MEAS = 3, INFO = 6, PAR = 5;
+  // X: the camera's isometry, K: fx fy cx cy baseline, p: the point, m: the measurement
+  template <bool JA, bool JB>
+  DI static void core(const double* X, const double* K, const double* p, const double* m, double* err, double* A,
+                      double* B) {
+    double W[12];
+    iso_inv(X, W);  // w2n = [R^T | -R^T t]
+    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], bl = K[4];
+    // w2i = Kcam * w2n, rows 0 and 1 (row 2 is w2n's)
+    double I0[4], I1[4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      I0[c] = fx * W[c] + cx * W[6 + c];
+      I1[c] = fy * W[3 + c] + cy * W[6 + c];
+    }
+    I0[3] = fx * W[9] + cx * W[11];
+    I1[3] = fy * W[10] + cy * W[11];
+    const double px = p[0], py = p[1], pz = p[2];
+    const double p1x = I0[0] * px + I0[1] * py + I0[2] * pz + I0[3];
+    const double p1y = I1[0] * px + I1[1] * py + I1[2] * pz + I1[3];
+    const double x = W[0] * px + W[1] * py + W[2] * pz + W[9];
+    const double y = W[3] * px + W[4] * py + W[5] * pz + W[10];
+    const double z = W[6] * px + W[7] * py + W[8] * pz + W[11];
+    const double invp1 = 1.0 / z;
+    err[0] = p1x * invp1 - m[0];
+    err[1] = p1y * invp1 - m[1];
+    err[2] = (fx * (x - bl) + cx * z) / z - m[2];
+    if (JA || JB) {
+      const double iz2 = invp1 * invp1;
+      const double P[9] = {fx * invp1, 0, -fx * x * iz2, 0, fy * invp1, -fy * y * iz2, fx * invp1, 0, -fx * (x - bl) * iz2};
+      if (JA) mat3mul(P, W, A);
+      if (JB) {
+        const double S[9] = {0, -2 * z, 2 * y, 2 * z, 0, -2 * x, -2 * y, 2 * x, 0};  // 2 [pc]x
+        double M[9];
+        mat3mul(P, S, M);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            B[r * 6 + c] = -P[r * 3 + c];
+            B[r * 6 + 3 + c] = M[r * 3 + c];
+          }
+      }
+    }
+  }
+  template <bool JAC>
+  DI static void eval(const EdgeData& d, int e, double* err, double* A, double* B) {
+    const double* pp = d.s0 + (size_t)d.v0[e] * 3;
+    const double* xp = d.s1 + (size_t)d.v1[e] * 12;
+    const double* mp = d.meas + (size_t)e * MEAS;
+    const double* Kp = param_rec(d, e, PAR);
+    double X[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) X[k] = xp[k];
+    const double p[3] = {pp[0], pp[1], pp[2]}, m[3] = {mp[0], mp[1], mp[2]};
+    const double K[5] = {Kp[0], Kp[1], Kp[2], Kp[3], Kp[4]};
+    core<JAC, JAC>(X, K, p, m, err, A, B);
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double A[9], B[18];
+    eval<false>(d, e, err, A, B);
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* A, double* B) { eval<true>(d, e, err, A, B); }
 };
 
 // ---- host-Jacobian edges (an edge type the device does not know): the host's linearizeOplus

@@ -63,6 +63,8 @@ static bool is_sba_type(int e) { return e == G2OHIP_E_PROJECT_P2MC || e == G2OHI
 static bool is_offset_type(int e) { return e == G2OHIP_E_SE3_OFFSET || e == G2OHIP_E_SE2_OFFSET; }
 // g2o's own BA edges on a CameraParameters parameter: EdgeProjectXYZ2UV, EdgeProjectXYZ2UVU
 static bool is_camparams_type(int e) { return e == G2OHIP_E_PROJECT_XYZ2UV || e == G2OHIP_E_PROJECT_XYZ2UVU; }
+// types_icp: Edge_V_V_GICP between two VertexSE3, Edge_XYZ_VSC from a point to a VertexSCam (a VertexSE3)
+static bool is_icp_type(int e) { return e == G2OHIP_E_V_V_GICP || e == G2OHIP_E_XYZ_VSC; }
 // BaseUnaryEdge types: the five priors, the two pose-only projections (EdgeSE3ProjectXYZOnlyPose and its stereo
 // sibling, on a VertexSE3Expmap) and the unary host-J escape
 static bool is_unary_type(int e) {
@@ -77,6 +79,7 @@ int edge_dim(int e) {
     case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: case G2OHIP_E_PROJECT_P2SC: return 3;
     case G2OHIP_E_PROJECT_P2MC: case G2OHIP_E_PROJECT_XYZ2UV: return 2;
     case G2OHIP_E_PROJECT_XYZ2UVU: return 3;
+    case G2OHIP_E_V_V_GICP: case G2OHIP_E_XYZ_VSC: return 3;
     case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: return 2;
     case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: case G2OHIP_E_SE3_OFFSET: return 6;
     case G2OHIP_E_SE2_OFFSET: return 3;
@@ -92,14 +95,19 @@ int edge_meas_dim(int e) {
   if (is_slam3d_type(e)) return 3;
   if (is_sba_type(e)) return e == G2OHIP_E_PROJECT_P2MC ? 2 : 3;
   if (is_camparams_type(e)) return e == G2OHIP_E_PROJECT_XYZ2UV ? 2 : 3;
+  if (e == G2OHIP_E_V_V_GICP) return 12;  // pos0 normal0 pos1 normal1, the file order (G2OHIP_E_XYZ_VSC: u v u_r, below)
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
 }
 // doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
 // sensor offset x y z qx qy qz qw (optional: NULL = identity), as EdgeSE3PointXYZ's; the slam3d camera types' offset
 // followed by fx fy cx cy; the pose-only projections' Xw fx fy cx cy (stereo + bf); EdgeSE3Offset / EdgeSE2Offset: the
 // offset of the from vertex, then of the to vertex (2 x 7 / 2 x 3, optional: NULL = both the identity);
-// EdgeProjectXYZ2UV / XYZ2UVU: the CameraParameters focal_length cx cy baseline
+// EdgeProjectXYZ2UV / XYZ2UVU: the CameraParameters focal_length cx cy baseline; Edge_V_V_GICP: cov0 | cov1, each
+// packed upper 6 (optional: NULL = point-to-plane, the information is the caller's); Edge_XYZ_VSC: VertexSCam's static
+// fx fy cx cy baseline
 int edge_param_dim(int e) {
+  if (e == G2OHIP_E_V_V_GICP) return 12;
+  if (e == G2OHIP_E_XYZ_VSC) return 5;
   if (is_camparams_type(e)) return 4;
   if (e == G2OHIP_E_SE3_OFFSET) return 14;
   if (e == G2OHIP_E_SE2_OFFSET) return 6;
@@ -1246,7 +1254,10 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   const bool unary = is_unary_type(type);
   if (unary != (v1 == nullptr) && (n > 0 || v1)) return G2OHIP_ERR_ARG;  // v1 is NULL for the unary types, only for them
   const int np = edge_param_dim(type);
-  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ && !is_offset_type(type)) return G2OHIP_ERR_ARG;
+  const bool gicp = type == G2OHIP_E_V_V_GICP;
+  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ && !is_offset_type(type) && !gicp)
+    return G2OHIP_ERR_ARG;
+  if (!info && n > 0 && !(gicp && params)) return G2OHIP_ERR_ARG;  // only a plane-to-plane set goes without one
   if (is_sba_type(type) && params) return G2OHIP_ERR_ARG;  // the intrinsics live in the VertexCam
   if (type == G2OHIP_E_SE2_XY_BEARING && params) return G2OHIP_ERR_ARG;  // EdgeSE2PointXYBearing has no parameter
   const int nm = edge_meas_dim(type);
@@ -1254,6 +1265,8 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   for (int k = 0; k < n; ++k)
     if (!hg.idmap.count(v0[k]) || (!unary && !hg.idmap.count(v1[k]))) return G2OHIP_ERR_ARG;
   HEdgeSet* es = hg.set_of(type);
+  // Edge_V_V_GICP: plane-to-plane (params given) holds for the whole set, not per edge as the reference's pl_pl
+  if (gicp && es && !es->ev0.empty() && n > 0 && (params != nullptr) != !es->params.empty()) return G2OHIP_ERR_ARG;
   if (!es) {
     hg.esets.emplace_back();
     es = &hg.esets.back();
@@ -1267,9 +1280,10 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
     if (!unary) es->ev1.push_back(hg.idmap[v1[k]]);
   }
   if (nm > 0) es->meas.insert(es->meas.end(), meas, meas + (size_t)n * nm);
-  es->info.insert(es->info.end(), info, info + (size_t)n * D * D);
+  if (info) es->info.insert(es->info.end(), info, info + (size_t)n * D * D);
+  else es->info.insert(es->info.end(), (size_t)n * D * D, 0.0);  // plane-to-plane: rebuilt on the device, never read
   if (np > 0 && params) es->params.insert(es->params.end(), params, params + (size_t)n * np);
-  if (np > 0 && !params) {  // EdgeSE3Prior / EdgeSE3PointXYZ without an offset parameter: the identity
+  if (np > 0 && !params && !gicp) {  // EdgeSE3Prior / EdgeSE3PointXYZ without an offset parameter: the identity
     const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
     if (type == G2OHIP_E_SE2_OFFSET) es->params.insert(es->params.end(), (size_t)n * 6, 0.0);
     else
@@ -1330,7 +1344,8 @@ namespace {
 struct ParsedVertex { int type, id; double est[12]; };  // (12: VERTEX_CAM)
 // unary: b = -1, or the SE3 prior's parameter id; pid: the slam3d landmark edges' parameter id
 // (the offset edges: pid the from vertex's parameter id, pid2 the to vertex's; p the two records)
-struct ParsedEdge { int type, a, b; double m[7], info[36], p[14]; int pid = -1, pid2 = -1; };
+// (EDGE_V_V_GICP: m the 12 values pos0 normal0 pos1 normal1; at: the start of the line, for a message's line number)
+struct ParsedEdge { int type, a, b; double m[12], info[36], p[14]; int pid = -1, pid2 = -1; const char* at = nullptr; };
 // PARAMS_SE3OFFSET id x y z qx qy qz qw; camera: PARAMS_CAMERACALIB, the same followed by fx fy cx cy; se2:
 // PARAMS_SE2OFFSET id x y theta; camparams: PARAMS_CAMERAPARAMETERS id focal_length cx cy baseline
 struct ParsedParam { int id; double v[11]; bool camera = false, se2 = false, camparams = false; };
@@ -1371,8 +1386,9 @@ struct Cursor {
 // expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP); sba: VERTEX_CAM, EDGE_PROJECT_P2MC, EDGE_PROJECT_P2SC (G2OHIP_LOAD_SBA)
 // offset: PARAMS_SE3OFFSET, PARAMS_SE2OFFSET, EDGE_SE3_OFFSET, EDGE_SE2_OFFSET, EDGE_BEARING_SE2_XY (G2OHIP_LOAD_OFFSET)
 // camparams: PARAMS_CAMERAPARAMETERS, EDGE_PROJECT_XYZ2UV:EXPMAP (G2OHIP_LOAD_CAMERAPARAMS)
+// icp: EDGE_V_V_GICP (G2OHIP_LOAD_ICP)
 void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, bool sba, bool offset,
-                 bool camparams, ParsedChunk& out) {
+                 bool camparams, bool icp, ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1492,6 +1508,12 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       for (int r = 0; r < D; ++r)
         for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
       out.edges.push_back(ed);
+    } else if (icp && tag == "EDGE_V_V_GICP") {  // types_icp.cpp:124-160: pos0 normal0 pos1 normal1; the information
+                                                 // is built from normal0 when the edges are added (Engine::load)
+      ParsedEdge ed{G2OHIP_E_V_V_GICP, c.i(), c.i(), {}, {}, {}};
+      for (int k = 0; k < 12; ++k) ed.m[k] = c.d();
+      ed.at = t0;
+      out.edges.push_back(ed);
     } else if (offset && tag == "EDGE_BEARING_SE2_XY") {  // edge_se2_pointxy_bearing.cpp:56-60: angle, information
       ParsedEdge ed{G2OHIP_E_SE2_XY_BEARING, c.i(), c.i(), {}, {}, {}};
       ed.m[0] = c.d();
@@ -1546,7 +1568,8 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
 int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0,
              expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0, sba = (flags & G2OHIP_LOAD_SBA) != 0,
-             offset = (flags & G2OHIP_LOAD_OFFSET) != 0, camparams = (flags & G2OHIP_LOAD_CAMERAPARAMS) != 0;
+             offset = (flags & G2OHIP_LOAD_OFFSET) != 0, camparams = (flags & G2OHIP_LOAD_CAMERAPARAMS) != 0,
+             icp = (flags & G2OHIP_LOAD_ICP) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1575,7 +1598,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
       th.emplace_back(
-          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, camparams, chunks[t]); });
+          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, camparams, icp, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1614,8 +1637,9 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   std::vector<double> em, ei, ep;
   auto flush_e = [&](int type) -> int {
     if (ea.empty()) return G2OHIP_OK;
+    // (a loaded Edge_V_V_GICP is point-to-plane: no parameter record)
     const int r = add_edges(type, (int)ea.size(), ea.data(), is_unary_type(type) ? nullptr : eb.data(), em.data(),
-                            ei.data(), edge_param_dim(type) ? ep.data() : nullptr);
+                            ei.data(), edge_param_dim(type) && type != G2OHIP_E_V_V_GICP ? ep.data() : nullptr);
     ea.clear(); eb.clear(); em.clear(); ei.clear(); ep.clear();
     return r;
   };
@@ -1714,6 +1738,36 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                 ", which is of another kind than PARAMS_CAMERAPARAMETERS");
         std::memcpy(ed.p, po->second->v, sizeof(double) * 4);
       }
+      if (ed.type == G2OHIP_E_V_V_GICP) {
+        const std::string where = "g2o_hip load: EDGE_V_V_GICP " + std::to_string(ed.a) + " -> " + std::to_string(ed.b);
+        for (int id : {ed.a, ed.b}) {
+          auto it = hg.idmap.find(id);
+          if (it == hg.idmap.end() || hg.verts[it->second].type != G2OHIP_V_SE3_QUAT)
+            throw StatusError(G2OHIP_ERR_ARG, where + ": vertex " + std::to_string(id) + " is missing or no VERTEX_SE3:QUAT");
+        }
+        // Edge_V_V_GICP::read (types_icp.cpp:141-152): makeRot0 (types_icp.h:84-96), then R0^T diag(.01, .01, 1) R0.
+        // makeRot0 normalises y = (0,1,0) - n_y n without the check its comment asks for: a normal parallel to (0,1,0)
+        // divides by zero. Such a line is refused here, nothing is stored.
+        const double* nr = ed.m + 3;
+        double y[3] = {-nr[1] * nr[0], 1.0 - nr[1] * nr[1], -nr[1] * nr[2]};
+        const double yn = std::sqrt(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]);
+        if (!(yn > 0) || !std::isfinite(yn)) {
+          const long line = 1 + std::count(base, ed.at, '\n');
+          throw StatusError(G2OHIP_ERR_ARG, where + " (line " + std::to_string(line) + " of " + path +
+                                                "): normal0 is parallel to (0,1,0), for which the reference's makeRot0 "
+                                                "divides by zero");
+        }
+        for (double& v : y) v /= yn;
+        const double R0[9] = {nr[1] * y[2] - nr[2] * y[1], nr[2] * y[0] - nr[0] * y[2], nr[0] * y[1] - nr[1] * y[0],
+                              y[0], y[1], y[2], nr[0], nr[1], nr[2]};  // rows: n x y, y, n
+        const double pr[3] = {0.01, 0.01, 1.0};
+        for (int r = 0; r < 3; ++r)
+          for (int q = 0; q < 3; ++q) {
+            double s = 0;
+            for (int t = 0; t < 3; ++t) s += R0[t * 3 + r] * pr[t] * R0[t * 3 + q];
+            ed.info[r * 3 + q] = s;
+          }
+      }
       if (is_slam3d_type(ed.type)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
         const bool cam = ed.type != G2OHIP_E_SE3_XYZ;
         auto po = offsets.find(ed.pid);
@@ -1728,7 +1782,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
       eb.push_back(ed.b);
       em.insert(em.end(), ed.m, ed.m + nm);
       ei.insert(ei.end(), ed.info, ed.info + D * D);
-      ep.insert(ep.end(), ed.p, ed.p + edge_param_dim(ed.type));
+      if (ed.type != G2OHIP_E_V_V_GICP) ep.insert(ep.end(), ed.p, ed.p + edge_param_dim(ed.type));
     }
   if (int r = flush_e(cur)) return r;
   for (auto& c : chunks)
@@ -1900,6 +1954,9 @@ int Engine::save(const char* path) {
         } else if (es.type == G2OHIP_E_PROJECT_XYZ2UV) {  // types_six_dof_expmap.cpp:265-276: the parameter id first
           L.tag("EDGE_PROJECT_XYZ2UV:EXPMAP"); L.i(a); L.i(b); L.i(pids[si][k]);
           L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
+        } else if (es.type == G2OHIP_E_V_V_GICP) {  // types_icp.cpp:206-222: pos0 normal0 pos1 normal1, nothing else
+          L.tag("EDGE_V_V_GICP"); L.i(a); L.i(b);
+          for (int q = 0; q < 12; ++q) L.d(m[q]);
         } else if (es.type == G2OHIP_E_SE2_XY_BEARING) {  // edge_se2_pointxy_bearing.cpp:62-66
           L.tag("EDGE_BEARING_SE2_XY"); L.i(a); L.i(b); L.d(m[0]); L.d(I[0]);
         } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
@@ -2076,6 +2133,8 @@ static int family_of(int etype, int& vtA, int& vtB) {
     case G2OHIP_E_SE3_OFFSET: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3_OFFSET;
     case G2OHIP_E_SE2_OFFSET: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2_OFFSET;
     case G2OHIP_E_SE2_XY_BEARING: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY_BEARING;
+    case G2OHIP_E_V_V_GICP: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_GICP;
+    case G2OHIP_E_XYZ_VSC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_QUAT; return FAM_VSC;
     // unary types: vtB = 0 (no second vertex)
     case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
     case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
@@ -2466,7 +2525,10 @@ void Engine::fill_group_device(EGroup& g) {
     case FAM_SE3_OFFSET: mmeas = 12; break;     // Z^-1 as an isometry, as FAM_SE3
     case FAM_SE2_OFFSET: mmeas = 3; break;      // the inverse measurement, as FAM_SE2
     case FAM_SE2XY_BEARING: mmeas = 1; break;
+    case FAM_GICP: mmeas = 6; break;            // pos0 | pos1 (the normals stay on the host, for save)
+    case FAM_VSC: mmeas = 3; break;
   }
+  const bool gicp_plpl = g.family == FAM_GICP && !es.params.empty();
   // device parameter record: the BA intrinsics as given (a CameraParameters record expanded: ba_device_params);
   // slam3d: the inverse offset as an isometry (12), the camera types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
   // point Xw ahead of them in the caller's record goes into the measurement payload); EdgeSE3Offset: the two offsets as
@@ -2476,7 +2538,9 @@ void Engine::fill_group_device(EGroup& g) {
                    : is_slam3d_family(g.family) ? 16
                    : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3
                    : g.family == FAM_SE3_OFFSET ? 24
-                   : g.family == FAM_SE2_OFFSET ? 6 : 0;
+                   : g.family == FAM_SE2_OFFSET ? 6
+                   : gicp_plpl ? 12               // Edge_V_V_GICP plane-to-plane: cov0 | cov1 packed upper, as given
+                   : g.family == FAM_VSC ? 5 : 0;  // Edge_XYZ_VSC: fx fy cx cy baseline, as given
   std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
       params(mpar ? (size_t)gne * mpar : 1);
   for (int k = 0; k < gne; ++k) {
@@ -2524,6 +2588,13 @@ void Engine::fill_group_device(EGroup& g) {
       mo[0] = m[0]; mo[1] = m[1];
     } else if (is_sba_family(g.family) || g.family == FAM_SE2XY_BEARING) {
       for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+    } else if (g.family == FAM_VSC) {
+      for (int j = 0; j < 3; ++j) mo[j] = m[j];
+      for (int j = 0; j < 5; ++j) params[(size_t)k * 5 + j] = es.params[(size_t)e * 5 + j];
+    } else if (g.family == FAM_GICP) {
+      for (int j = 0; j < 3; ++j) { mo[j] = m[j]; mo[3 + j] = m[6 + j]; }
+      if (gicp_plpl)
+        for (int j = 0; j < 12; ++j) params[(size_t)k * 12 + j] = es.params[(size_t)e * 12 + j];
     } else if (g.family == FAM_SE3_OFFSET) {  // edge_se3_offset.cpp:59-72: Z^-1 of the normalised measurement; the two
                                               // ParameterSE3Offset::offset() = fromVectorQT, q normalised
       iso_inverse_of(m, mo);
@@ -2571,7 +2642,8 @@ void Engine::fill_group_device(EGroup& g) {
     const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
     g.ue = 0;
     if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family) ||
-         is_sba_family(g.family) || is_offset_family(g.family) || g.family == FAM_SE2XY_BEARING) && gne > 1 &&
+         is_sba_family(g.family) || is_offset_family(g.family) || g.family == FAM_SE2XY_BEARING ||
+         g.family == FAM_GICP || g.family == FAM_VSC) && gne > 1 &&
         !(ev && atoi(ev) == 0)) {
       auto uniform = [&](const std::vector<double>& v, int st) {
         for (int k = 1; k < gne; ++k)
@@ -2582,6 +2654,7 @@ void Engine::fill_group_device(EGroup& g) {
       if (mpar && uniform(params, mpar)) { g.ue |= 2; params.resize(mpar); }  // (the sba types have no record)
     }
   }
+  if (gicp_plpl) g.ue |= 4;  // FamilyGICP::information rebuilds Omega from the state
   g.info.upload(info, stream);
   g.params.upload(params, stream);
   if (is_hostj_family(g.family)) upload_group_payload(hg, g, stream);
@@ -2661,6 +2734,24 @@ void Engine::setup_edges_device() {
     const HEdgeSet& es = hg.esets[g.set];
     std::stable_sort(g.edges.begin(), g.edges.end(), [&](int a, int b) { return hidx[es.ev0[a]] < hidx[es.ev0[b]]; });
   }
+  {  // pair-major assembly: the binary groups are one Edge_V_V_GICP group
+    int nbin = 0, ngicp = 0;
+    for (const EGroup& g : groups)
+      if (!is_unary_family(g.family)) { ++nbin; ngicp += g.family == FAM_GICP; }
+    pair_major = !do_schur && nranks == 1 && pd == 6 && nbin == 1 && ngicp == 1 && !pm_force_slot;
+  }
+  if (pair_major)  // stable by the unordered pair of hessian indices; a fixed end counts as "no block"
+    for (EGroup& g : groups)
+      if (g.family == FAM_GICP) {
+        const HEdgeSet& es = hg.esets[g.set];
+        auto key = [&](int e) {
+          const int a = hidx[es.ev0[e]], b = hidx[es.ev1[e]];
+          if (a < 0 && b < 0) return std::make_pair(INT_MAX, INT_MAX);
+          if (a < 0 || b < 0) return std::make_pair(std::max(a, b), INT_MAX);
+          return std::make_pair(std::min(a, b), std::max(a, b));
+        };
+        std::stable_sort(g.edges.begin(), g.edges.end(), [&](int a, int b) { return key(a) < key(b); });
+      }
   for (EGroup& g : groups) fill_group_device(g);
   if (ba_fused) {
     const EGroup& g = groups[0];
@@ -3045,6 +3136,13 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
                           "bearing edges (edge type " + std::to_string(es.type) + "); use lm_pcg or lm_hip_var");
   if (use_cgls())
     for (const HEdgeSet& es : hg.esets)
+      if (is_icp_type(es.type) && !es.ev0.empty())
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the types_icp "
+                          "edges Edge_V_V_GICP / Edge_XYZ_VSC (edge type " + std::to_string(es.type) +
+                          "); use lm_pcg, lm_pcg6_3 or lm_hip_var");
+  if (use_cgls())
+    for (const HEdgeSet& es : hg.esets)
       if (is_camparams_type(es.type) && !es.ev0.empty())
         throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                           "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the "
@@ -3152,7 +3250,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
   for (int f = 0; f < ne; ++f) {
     if (ekey[f] < 0) continue;
     const long long bsz = ekey[f] < nHpp ? (long long)pd * pd : (long long)pd * ld;
-    if (blk_count[ekey[f]] == 1) {
+    if (blk_count[ekey[f]] == 1 || pair_major) {  // (pair-major: k_pair_reduce owns the block, no per-edge slots)
       offdst[f] = blk_off(ekey[f]);
     } else {
       slotoff[f] = nslotd;
@@ -3184,11 +3282,55 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     R.dst.upload(dst.empty() ? std::vector<long long>{0} : dst, stream);
   }
   doffslot.resize((size_t)std::max<long long>(nslotd, 1));
+  // pair-major tables: the group's edges are sorted by pair (setup_edges_device); one run per pair, cut into chunks
+  std::vector<int3> pm_pairs;  // (first side's hessian index, second side's or -1, first edge)
+  pm_nchunks = pm_npairs = 0;
+  if (pair_major)
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      const EGroup& g = groups[gi];
+      if (g.family != FAM_GICP) continue;
+      std::vector<int4> chunks;
+      std::vector<int2> range;
+      std::vector<long long> dst;
+      for (int k = 0; k < g.ne;) {
+        int va, vb;
+        verts_of(gi, k, va, vb);
+        const int a = hidx[va], b = hidx[vb];
+        if (a < 0 && b < 0) break;  // both ends fixed: inactive, sorted behind every pair
+        const int lo = a < 0 || b < 0 ? std::max(a, b) : std::min(a, b), hi = a < 0 || b < 0 ? -1 : std::max(a, b);
+        int k2 = k + 1;
+        for (; k2 < g.ne; ++k2) {
+          int wa, wb;
+          verts_of(gi, k2, wa, wb);
+          const int c = hidx[wa], d = hidx[wb];
+          const int lo2 = c < 0 || d < 0 ? std::max(c, d) : std::min(c, d), hi2 = c < 0 || d < 0 ? -1 : std::max(c, d);
+          if (lo2 != lo || hi2 != hi || (c < 0 && d < 0)) break;
+        }
+        const int p = (int)pm_pairs.size();
+        pm_pairs.push_back(int3{lo, hi, k});
+        const int c0 = (int)chunks.size();
+        for (int q = k; q < k2; q += 64) chunks.push_back(int4{q, std::min(64, k2 - q), p, hi >= 0 ? 1 : 0});
+        range.push_back(int2{c0, (int)chunks.size()});
+        dst.push_back(hi >= 0 ? offdst[gfirst[gi] + k] : -1);
+        k = k2;
+      }
+      pm_npairs = (int)pm_pairs.size();
+      pm_nchunks = (int)chunks.size();
+      pm_chunks.upload(chunks.empty() ? std::vector<int4>{int4{0, 0, 0, 0}} : chunks, stream);
+      pm_range.upload(range.empty() ? std::vector<int2>{int2{0, 0}} : range, stream);
+      pm_dst.upload(dst.empty() ? std::vector<long long>{-1} : dst, stream);
+      pm_partial.resize((size_t)std::max(pm_nchunks, 1) * 90);
+    }
   // per-vertex-side slots: arena by vertex dimension, each group's sides contiguous
   for (long long& c : nslot) c = 0;
   for (EGroup& g : groups) {
     long long& ca = nslot[g.DA];
     g.slotA = ca;
+    if (pair_major && g.family == FAM_GICP) {  // two side slots per pair, no per-edge slots
+      g.slotB = ca;
+      ca += 2LL * pm_npairs;
+      continue;
+    }
     ca += g.ne;
     if (!g.DB) continue;  // a unary group: ne slots in the arena of DA only
     long long& cb = nslot[g.DB];
@@ -3240,6 +3382,13 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     std::vector<std::vector<int>> incp(num_poses), incl(nLloc);
     for (size_t gi = 0; gi < groups.size(); ++gi) {
       const EGroup& g = groups[gi];
+      if (pair_major && g.family == FAM_GICP) {  // the lists point at pair sides instead of edge sides
+        for (int p = 0; p < pm_npairs; ++p) {
+          incp[pm_pairs[p].x].push_back((int)(g.slotA + 2 * p));
+          if (pm_pairs[p].y >= 0) incp[pm_pairs[p].y].push_back((int)(g.slotA + 2 * p + 1));
+        }
+        continue;
+      }
       for (int k = 0; k < g.ne; ++k) {
         int va, vb;
         verts_of(gi, k, va, vb);
@@ -3913,6 +4062,19 @@ int Engine::build_system_split(double lambda, const double* lamp) {  // block_so
     }
     return G2OHIP_OK;
   }
+  if (pair_major) {
+    for (const EGroup& g : groups)
+      if (g.family == FAM_GICP) {
+        timer.begin("linearize", stream);
+        launch::linearize_pairs(g.family, group_args(g), pm_nchunks, pm_chunks.get(), d_hidx[g.vtA].get(),
+                                d_hidx[g.vtB].get(), pm_partial.get(), stream);
+        timer.end(stream);
+        timer.begin("pair_reduce", stream);
+        launch::pair_reduce(pd, pm_npairs, pm_range.get(), pm_dst.get(), pm_partial.get(),
+                            slot_arena(pd) + g.slotA * (pd * (pd + 1) / 2 + pd), dH.get(), stream);
+        timer.end(stream);
+      }
+  } else {
   timer.begin("linearize", stream);
   for (const EGroup& g : groups)
     if (!is_unary_family(g.family))
@@ -3921,6 +4083,7 @@ int Engine::build_system_split(double lambda, const double* lamp) {  // block_so
                         slot_arena(g.DB) + g.slotB * (g.DB * (g.DB + 1) / 2 + g.DB), g.off_dst.get(), g.off_tr.get(),
                         dH.get(), doffslot.get(), stream);
   timer.end(stream);
+  }
   if (has_unary_) {  // the unary groups: one slot per edge (k_linearize_unary), timed as a class of their own
     timer.begin("linearize_unary", stream);
     for (const EGroup& g : groups)
@@ -4412,6 +4575,22 @@ int Engine::gn_solve(int iteration, g2ohip_batch_stats* st) {
   levenberg_iterations = 0;
   if (f[0] != 0 && write_debug && rank == 0 && !use_pcg() && !use_cgls()) write_debug_dump();
   return f[0] == 0 ? 0 : 2;
+}
+
+int Engine::set_pair_major(int enable) {
+  if (enable != 0 && enable != 1) return G2OHIP_ERR_ARG;
+  if (pm_force_slot != (enable == 0)) {
+    pm_force_slot = enable == 0;
+    structure_built = false;  // the edge order, the slots and the incidence lists follow the path
+  }
+  return G2OHIP_OK;
+}
+int Engine::pair_major_info(int* out) const {
+  if (!out) return G2OHIP_ERR_ARG;
+  out[0] = structure_built && pair_major ? 1 : 0;
+  out[1] = out[0] ? pm_npairs : 0;
+  out[2] = out[0] ? pm_nchunks : 0;
+  return G2OHIP_OK;
 }
 
 int Engine::set_dogleg_params(double initial_delta, int max_trials, double initial_lambda, double lambda_factor) {

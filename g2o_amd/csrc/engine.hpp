@@ -247,6 +247,8 @@ class Engine {
   Algo algo = Algo::Levenberg;
   // OptimizationAlgorithmDogleg properties (optimization_algorithm_dogleg.cpp:45-48); a value <= 0: the default
   int set_dogleg_params(double initial_delta, int max_trials, double initial_lambda, double lambda_factor);
+  int set_pair_major(int enable);
+  int pair_major_info(int* out) const;  // out[0] path taken (1 pair-major), out[1] pairs, out[2] chunks
   // [delta, lastStep, lastNumTries, currentLambda, wasPDInAllIterations] after the last dogleg iteration
   void dogleg_state(double* out) const;
 
@@ -416,6 +418,15 @@ class Engine {
   // monocular + stereo graph does; fusing priors into the camera pass is not done); edges landmark-major,
   // wave chunks of whole landmarks, camera-major copies of the edge data for the camera-side pass
   bool ba_fused = false;
+  // pair-major assembly (pairs.hip): every active binary edge is Edge_V_V_GICP on 6x6 pose blocks, no Schur complement,
+  // one rank (unary priors may be present and keep k_linearize_unary). The group's edges are sorted by vertex pair and
+  // cut into chunks of <= 64; pm_force_slot (g2ohip_set_pair_major(g, 0)) keeps such a graph on the slot path
+  bool pair_major = false, pm_force_slot = false;
+  int pm_nchunks = 0, pm_npairs = 0;
+  DevBuf<int4> pm_chunks;      // (first edge, edges, pair, bit 0: both ends free)
+  DevBuf<int2> pm_range;       // per pair its chunk range
+  DevBuf<long long> pm_dst;    // per pair the offset of its Hpp block, -1: one end fixed
+  DevBuf<double> pm_partial;   // per chunk [first side 27 | block 36 | second side 27]
   DevBuf<int4> fz_chunks, fz_fix;
   int fz_nchunks = 0, fz_nfix = 0;
   DevBuf<double> fz_lpart;

@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(256) k_error(EdgeData d, int ne, double* __res
   double err[F::D];
   F::error(d, e, err);
   double Om[F::D * F::D];
-  load_info<F::D>(info_rec(d, (int)e, F::INFO), Om);
+  family_info<F>(d, e, Om);
   double s = 0;
 #pragma unroll
   for (int i = 0; i < F::D; ++i) {
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(256)
   double err[D], A[D * DA], B[D * DB], Om[D * D];
   if (nfA || nfB) {
     F::linearize(d, e, err, A, B);
-    load_info<D>(info_rec(d, e, F::INFO), Om);
+    family_info<F>(d, e, Om);
     if (d.rk) {  // robust branch of constructQuadraticForm (base_binary_edge.hpp:104-135): Omega, omega_r scaled by rho'
       double chi = 0;
 #pragma unroll
@@ -253,7 +253,7 @@ __global__ void __launch_bounds__(256)
   if (e < ne && h0[d.v0[e]] >= 0) {
     double err[D], A[D * DA], Om[D * D];
     F::linearize(d, e, err, A);
-    load_info<D>(info_rec(d, e, F::INFO), Om);
+    family_info<F>(d, e, Om);
     if (d.rk) {  // base_unary_edge.hpp:62-69: weightedOmega = rho' Omega, b -= rho' A^T Omega e
       double chi = 0;
 #pragma unroll
@@ -1183,7 +1183,7 @@ __global__ void __launch_bounds__(256)
 template <class F>
 __device__ __forceinline__ double edge_chi(const EdgeData& d, int e, const double* err) {
   double Om[F::D * F::D];
-  load_info<F::D>(info_rec(d, e, F::INFO), Om);
+  family_info<F>(d, e, Om);
   double c = 0;
 #pragma unroll
   for (int i = 0; i < F::D; ++i) {
@@ -1865,6 +1865,8 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_SE3_OFFSET: fn(FamilySE3Offset{}); break;
     case FAM_SE2_OFFSET: fn(FamilySE2Offset{}); break;
     case FAM_SE2XY_BEARING: fn(FamilySE2XYBearing{}); break;
+    case FAM_GICP: fn(FamilyGICP{}); break;
+    case FAM_VSC: fn(FamilyVSC{}); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;

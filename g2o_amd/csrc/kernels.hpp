@@ -23,7 +23,11 @@ enum Family {
   FAM_U_POSE_ONLY = 22, FAM_U_STEREO_POSE_ONLY = 23,
   // EdgeProjectXYZ2UVU (point, VertexSE3Expmap camera, a CameraParameters record): FamilyUVU. A binary family, as
   // FAM_BA_STEREO; EdgeProjectXYZ2UV runs as FAM_BA with the record f f cx cy
-  FAM_BA_UVU = 24
+  FAM_BA_UVU = 24,
+  // Edge_V_V_GICP between two VertexSE3 (types_icp): FamilyGICP, point-to-plane or plane-to-plane per edge set
+  FAM_GICP = 25,
+  // Edge_XYZ_VSC (point, VertexSCam = a VertexSE3 camera): FamilyVSC, the landmark first as in the BA families
+  FAM_VSC = 26
 };
 // the fused landmark-major assembly's families (point, VertexSE3Expmap camera)
 inline bool is_ba_family(int f) { return f == FAM_BA || f == FAM_BA_STEREO || f == FAM_BA_UVU; }
@@ -47,7 +51,7 @@ struct EdgeArgs {
   int rk = 0;          // robust kernel (G2OHIP_RK_*), uniform over the edge group
   double rk_delta = 1.0;
   int D = 0, DA = 0, DB = 0;  // host-J family dimensions
-  int ue = 0;                 // uniform records (EdgeData::ue): bit 0 information, bit 1 intrinsics
+  int ue = 0;                 // uniform records (EdgeData::ue): bit 0 information, bit 1 intrinsics; bit 2 GICP plane-to-plane
 };
 
 namespace launch {
@@ -79,6 +83,15 @@ void vertex_reduce(int dim, int nv, int lanes, const int* ptr, const int* code, 
                    double* b, const int* boff, hipStream_t s);
 void offblock_reduce(int nb, int bsz, const int* ptr, const long long* soff, const double* slots, double* out,
                      const long long* dst, hipStream_t s);
+// pair-major assembly (pairs.hip) of a graph whose binary edges are all Edge_V_V_GICP. chunks = (first edge, edges
+// (<= 64), pair, flags: bit 0 both ends free) over the group's edges sorted by vertex pair; partial: 90 doubles per
+// chunk [first side 27 | block 36 | second side 27]. pair_reduce sums each pair's chunk range prange[p] in a fixed
+// order, writes the block at H + pdst[p] (pdst < 0: one end fixed, no block, no second side) and the side sums into
+// slots 2p and 2p + 1, which vertex_reduce then takes as it takes per-edge slots.
+void linearize_pairs(int family, const EdgeArgs& a, int nchunks, const int4* chunks, const int* h0, const int* h1,
+                     double* partial, hipStream_t s);
+void pair_reduce(int dim, int npairs, const int2* prange, const long long* pdst, const double* partial, double* slots,
+                 double* H, hipStream_t s);
 // fused BA assembly (assembly.hip): chunks = (first edge, edges, partial slot or -1, 0) of whole landmarks per wave
 // With a SchurSplit (sp != nullptr, lambda known at assembly, no shared off-diagonal blocks) the landmark side of the
 // Schur complement is formed during assembly: the linearize waves factor each landmark's Hll + lambda I = U U^T and

@@ -175,6 +175,22 @@ template <> struct PointEdge<FAM_SBA_MONO> : PointSBA<false> {};
 template <> struct PointEdge<FAM_SBA_STEREO> : PointSBA<true> {};
 
 template <>
+struct PointEdge<FAM_VSC> {  // FamilyVSC::core, the point's Jacobian alone
+  static constexpr int D = 3, LD = 3;
+  template <bool JAC>
+  DI static void eval(const SoGroup& g, int e, const double* p, double* err, double* A) {
+    const double* xp = g.so + (size_t)g.vo[e] * 12;
+    const double* mp = g.meas + (size_t)e * 3;
+    const double* Kp = so_param(g, e, 5);
+    double X[12], B[18];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) X[k] = xp[k];
+    const double m[3] = {mp[0], mp[1], mp[2]}, K[5] = {Kp[0], Kp[1], Kp[2], Kp[3], Kp[4]};
+    FamilyVSC::core<JAC, false>(X, K, p, m, err, A, B);
+  }
+};
+
+template <>
 struct PointEdge<FAM_SE2XY> {  // FamilySE2XY::linearize, Jj
   static constexpr int D = 2, LD = 2;
   template <bool JAC>
@@ -292,6 +308,7 @@ DI void edge_any(const SoGroup* groups, int2 en, const double* p, double& chi, d
       case FAM_SE3_XYZ_DISPARITY: edge_term<FAM_SE3_XYZ_DISPARITY, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_SBA_MONO: edge_term<FAM_SBA_MONO, JAC>(g, en.y, p, chi, H, b); break;
       case FAM_SBA_STEREO: edge_term<FAM_SBA_STEREO, JAC>(g, en.y, p, chi, H, b); break;
+      case FAM_VSC: edge_term<FAM_VSC, JAC>(g, en.y, p, chi, H, b); break;
       default: edge_term<FAM_U_XYZ, JAC>(g, en.y, p, chi, H, b); break;
     }
   } else {

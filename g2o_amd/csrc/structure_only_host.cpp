@@ -74,7 +74,7 @@ void Engine::so_build_list() {
     fixed.push_back(v.fixed ? 1 : 0);
   }
   L.nlm = (int)local.size();
-  // the landmark end of each group: v0 for the BA and sba families and the point priors, v1 for slam3d, SE2-XY and the bearing edge
+  // the landmark end of each group: v0 for the BA and sba families, Edge_XYZ_VSC and the point priors, v1 for slam3d, SE2-XY and the bearing edge
   std::vector<int> cnt(L.nlm + 1, 0);
   std::vector<int> gslot(groups.size(), -1);
   auto lm_end = [&](const EGroup& g, int k) {  // vertex index of the edge's marginalised endpoint(s): (a, b), -1 none
@@ -86,7 +86,7 @@ void Engine::so_build_list() {
   for (size_t gi = 0; gi < groups.size() && L.nlm; ++gi) {
     const EGroup& g = groups[gi];
     const bool lm_first = is_ba_family(g.family) || g.family == FAM_U_XYZ ||
-                          g.family == FAM_U_XY || is_sba_family(g.family);
+                          g.family == FAM_U_XY || is_sba_family(g.family) || g.family == FAM_VSC;
     const bool lm_second = is_lm_second_family(g.family);
     for (int k = 0; k < g.ne; ++k) {
       const auto [a, b] = lm_end(g, k);

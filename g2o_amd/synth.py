@@ -30,6 +30,10 @@ Recipes:
     EDGE_SE2_OFFSET with one or two distinct sensor offsets), the shape of g2o_simulator3d's pose sensor.
   * ``bearing_scene`` - bearing-only 2D landmark SLAM (EDGE_BEARING_SE2_XY; every landmark seen from several poses
     with parallax), the shape of g2o_simulator2d's bearing sensor.
+  * ``gicp_pair`` / ``gicp_scans`` / ``gicp_sba`` - scan registration in the types_icp vocabulary (EDGE_V_V_GICP
+    correspondences between VERTEX_SE3:QUAT scans, point-to-plane or plane-to-plane; Edge_XYZ_VSC stereo
+    observations of marginalised points): the scenes of gicp_demo.cpp and gicp_sba_demo.cpp, and a ring of scans
+    with many correspondences per scan pair.
 """
 from __future__ import annotations
 
@@ -63,23 +67,27 @@ E_SE3_OFFSET, E_SE2_OFFSET, E_SE2_XY_BEARING = 13, 14, 15
 # g2o's own BA edges on a CameraParameters parameter: EdgeProjectXYZ2UV (u v), EdgeProjectXYZ2UVU (u v u_r); v0 a V_XYZ
 # point, v1 a V_SE3_EXPMAP camera; params focal_length cx cy baseline
 E_PROJECT_XYZ2UV, E_PROJECT_XYZ2UVU = 23, 24
+# types_icp: Edge_V_V_GICP between two V_SE3_QUAT (meas pos0 normal0 pos1 normal1; params None = point-to-plane, or
+# cov0 | cov1 packed upper = plane-to-plane), Edge_XYZ_VSC from a V_XYZ point to a V_SE3_QUAT camera (params fx fy cx
+# cy baseline)
+E_V_V_GICP, E_XYZ_VSC = 25, 26
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
             E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
             E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
             E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 7, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
-            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3}
+            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 12, E_XYZ_VSC: 3}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
            E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 6, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
-           E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3}
+           E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 3, E_XYZ_VSC: 3}
 # parameter values per edge of the types that take a record (EdgeSet.params; where None is allowed it is the identity)
 PARAM_DIM = {E_SE3_PROJECT_XYZ: 4, E_STEREO_SE3_PROJECT_XYZ: 5, E_SE3_PRIOR: 7, E_SE3_XYZ: 7, E_SE3_XYZ_DEPTH: 11,
              E_SE3_XYZ_DISPARITY: 11, E_SE3_PROJECT_XYZ_ONLYPOSE: 7, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 8,
-             E_SE3_OFFSET: 14, E_SE2_OFFSET: 6, E_PROJECT_XYZ2UV: 4, E_PROJECT_XYZ2UVU: 4}
+             E_SE3_OFFSET: 14, E_SE2_OFFSET: 6, E_PROJECT_XYZ2UV: 4, E_PROJECT_XYZ2UVU: 4, E_V_V_GICP: 12, E_XYZ_VSC: 5}
 # the vertex type a unary edge type attaches to
 PRIOR_VERTEX = {E_SE2_PRIOR: V_SE2, E_SE2_XY_PRIOR: V_SE2, E_XY_PRIOR: V_XY, E_SE3_PRIOR: V_SE3_QUAT, E_XYZ_PRIOR: V_XYZ}
 # the same for the pose-only projections, and the binary projection each of them is the pose-only form of
@@ -108,7 +116,8 @@ class EdgeSet:
     # or None (identity) for SE3 priors and E_SE3_XYZ, [n, 11] (offset, fx fy cx cy) for E_SE3_XYZ_DEPTH / _DISPARITY,
     # [n, 7] (Xw fx fy cx cy) / [n, 8] (+ bf) for the pose-only projections, [n, 14] / [n, 6] (the from vertex's offset,
     # then the to vertex's; or None, both the identity) for E_SE3_OFFSET / E_SE2_OFFSET, [n, 4] (focal_length cx cy
-    # baseline) for E_PROJECT_XYZ2UV / E_PROJECT_XYZ2UVU
+    # baseline) for E_PROJECT_XYZ2UV / E_PROJECT_XYZ2UVU, [n, 12] (cov0 | cov1, packed upper triangles) or None
+    # (point-to-plane) for E_V_V_GICP (info may be None when params is given), [n, 5] (fx fy cx cy baseline) for E_XYZ_VSC
     params: np.ndarray | None = None
 
 
@@ -1168,6 +1177,170 @@ def offset_twin(prob: Problem) -> Problem:
     for es in prob.edges:
         if es.etype in (E_SE3_OFFSET, E_SE2_OFFSET, E_SE2_XY_BEARING):
             edges.append(EdgeSet(32 + ERR_DIM[es.etype], es.v0.copy(), es.v1.copy(), None, es.info.copy(), None))
+        else:
+            edges.append(es)
+    return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)
+
+
+# ---------------------------------------------------------------- types_icp scenes
+def _gicp_rot0(normal):
+    """EdgeGICP::makeRot0 (types_icp.h:84-96): rows n x y, y, n with y = (0,1,0) - n_y n normalised."""
+    n = np.asarray(normal, np.float64).reshape(3)
+    y = np.array([0.0, 1.0, 0.0]) - n[1] * n
+    yn = float(np.linalg.norm(y))
+    if not (yn > 0.0 and np.isfinite(yn)):
+        raise ValueError("gicp: a normal parallel to (0,1,0) makes the reference's makeRot0 divide by zero")
+    y = y / yn
+    return np.stack([np.cross(n, y), y, n])
+
+
+def gicp_prec(normal, e: float = 0.01):
+    """EdgeGICP::prec0 / prec1 (types_icp.h:111-130): R0^T diag(e, e, 1) R0, the point-to-plane information."""
+    R0 = _gicp_rot0(normal)
+    return R0.T @ np.diag([e, e, 1.0]) @ R0
+
+
+def gicp_cov(normal, e: float = 0.01):
+    """EdgeGICP::cov0 / cov1 (types_icp.h:133-152): R0^T diag(1, 1, e) R0, the plane-to-plane covariance."""
+    R0 = _gicp_rot0(normal)
+    return R0.T @ np.diag([1.0, 1.0, e]) @ R0
+
+
+def gicp_pack(M):
+    """[n, 3, 3] symmetric -> [n, 6] packed upper triangles 00 01 11 02 12 22 (the order of Edge_V_V_GICP's params)."""
+    M = np.asarray(M, np.float64).reshape(-1, 3, 3)
+    return np.stack([M[:, 0, 0], M[:, 0, 1], M[:, 1, 1], M[:, 0, 2], M[:, 1, 2], M[:, 2, 2]], 1)
+
+
+def _gicp_normals(k: np.ndarray) -> np.ndarray:
+    """gicp_demo's normals (0, i, 1) normalised, i taken modulo 50 (the demo's i runs to 999, where the normal is
+    within 1e-3 of the direction makeRot0 cannot take)."""
+    n = np.stack([np.zeros(len(k)), (k % 50).astype(np.float64), np.ones(len(k))], 1)
+    return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+def _gicp_edges(rng, R, t, a, b, pts, pl_pl, euc_noise, k0=0):
+    """Edge_V_V_GICP correspondences of world points ``pts`` [m, 3] between scans a[m] and b[m] with true poses
+    (R, t): pos = T^-1 p + noise, gicp_demo's normals; point-to-plane information prec0(0.01) or, with ``pl_pl``,
+    the covariances cov0(0.01) | cov1(0.01) and no information."""
+    m = len(a)
+    p0 = np.einsum("nji,nj->ni", R[a], pts - t[a]) + rng.standard_normal((m, 3)) * euc_noise
+    p1 = np.einsum("nji,nj->ni", R[b], pts - t[b]) + rng.standard_normal((m, 3)) * euc_noise
+    kk = (k0 + np.arange(m)) % 50  # the fifty distinct normals: one prec0 / cov0 each
+    base = _gicp_normals(np.arange(50))
+    nm = base[kk]
+    meas = np.concatenate([p0, nm, p1, nm], 1)
+    if pl_pl:
+        cov = gicp_pack(np.stack([gicp_cov(x, 0.01) for x in base]))[kk]
+        return meas, None, np.concatenate([cov, cov], 1)
+    return meas, np.stack([gicp_prec(x, 0.01) for x in base])[kk], None
+
+
+def gicp_pair(n_points: int = 1000, pl_pl: bool = False, euc_noise: float = 0.01, seed: int = SEED) -> Problem:
+    """gicp_demo.cpp's scene: two VertexSE3 at (0, 0, 0) and (0, 0, 1), the first fixed, ``n_points`` world points in
+    the box of the demo seen from both with Gaussian noise, one Edge_V_V_GICP per point; the second pose starts at
+    (0, 0, 0.2).  ``pl_pl``: the edge set is plane-to-plane (params cov0 | cov1, info None)."""
+    rng = _rng(seed, 80)
+    pts = np.stack([(rng.random(n_points) - 0.5) * 3, rng.random(n_points) - 0.5, rng.random(n_points) + 10], 1)
+    R = np.broadcast_to(np.eye(3), (2, 3, 3)).copy()
+    t = np.array([[0.0, 0, 0], [0, 0, 1.0]])
+    a, b = np.zeros(n_points, np.int64), np.ones(n_points, np.int64)
+    meas, info, params = _gicp_edges(rng, R, t, a, b, pts, pl_pl, euc_noise)
+    t0 = t.copy()
+    t0[1, 2] = 0.2
+    ids = np.arange(2, dtype=np.int32)
+    verts = VertexSet(V_SE3_QUAT, ids, _iso_vec(R, t0), np.array([1, 0], np.int32), np.zeros(2, np.int32))
+    edges = EdgeSet(E_V_V_GICP, ids[a].copy(), ids[b].copy(), meas, info, params)
+    return Problem(f"gicp_pair{n_points}{'pl' if pl_pl else ''}", [verts], [edges], 6, 0)
+
+
+def gicp_scans(num_scans: int = 8, neighbours: int = 2, points_per_pair=256, pl_pl: bool = False, fixed=(0,),
+               euc_noise: float = 0.01, seed: int = SEED) -> Problem:
+    """Scan registration on a ring: ``num_scans`` VertexSE3 on a circle of radius 3 looking at its centre, each matched
+    to its next ``neighbours`` scans by Edge_V_V_GICP correspondences of points scattered around the centre.
+    ``points_per_pair``: one number, or a sequence cycled over the pairs (deliberately uneven multiplicities, e.g.
+    (1, 64, 200)).  Every third pair is entered the other way round for the second half of its edges, so that one
+    vertex pair holds edges (i, j) and (j, i).  ``fixed``: the fixed scans.  The initial estimates are the true poses
+    perturbed.  Edges are in pair order; within a pair in point order."""
+    n = num_scans
+    rng = _rng(seed, 81)
+    th = 2 * math.pi * np.arange(n) / n
+    t = np.stack([3 * np.cos(th), 3 * np.sin(th), 0.1 * np.arange(n)], 1)
+    R = _axis_angle(np.tile([0.0, 0.0, 1.0], (n, 1)), th + math.pi) @ _small_rot(rng, n, 0.2)
+    mult = [int(points_per_pair)] if np.isscalar(points_per_pair) else [int(x) for x in points_per_pair]
+    pairs = [(i, (i + d) % n) for i in range(n) for d in range(1, neighbours + 1) if (i + d) % n != i]
+    a, b, pts = [], [], []
+    for q, (i, j) in enumerate(pairs):
+        m = mult[q % len(mult)]
+        ai, bi = np.full(m, i), np.full(m, j)
+        if q % 3 == 2:  # the second half of the pair's edges the other way round
+            ai[m // 2:], bi[m // 2:] = j, i
+        a.append(ai)
+        b.append(bi)
+        pts.append(rng.standard_normal((m, 3)) * np.array([1.0, 1.0, 0.5]))
+    a, b, pts = np.concatenate(a), np.concatenate(b), np.concatenate(pts)
+    meas, info, params = _gicp_edges(rng, R, t, a, b, pts, pl_pl, euc_noise)
+    R0 = R @ _small_rot(rng, n, 0.02)
+    t0 = t + rng.standard_normal((n, 3)) * 0.03
+    fx = np.zeros(n, np.int32)
+    for i in fixed:
+        fx[i] = 1
+        R0[i], t0[i] = R[i], t[i]
+    ids = np.arange(n, dtype=np.int32)
+    verts = VertexSet(V_SE3_QUAT, ids, _iso_vec(R0, t0), fx, np.zeros(n, np.int32))
+    edges = EdgeSet(E_V_V_GICP, ids[a].copy(), ids[b].copy(), meas, info, params)
+    return Problem(f"gicp_scans{n}x{neighbours}{'pl' if pl_pl else ''}", [verts], [edges], 6, 0)
+
+
+def gicp_sba(n_matches: int = 200, n_points: int = 100, num_cams: int = 2, pix_noise: float = 1.0,
+             euc_noise: float = 0.01, kcam=(150.0, 150.0, 320.0, 240.0, 0.075), seed: int = SEED) -> Problem:
+    """gicp_sba_demo.cpp's scene: ``num_cams`` VertexSCam (V_SE3_QUAT, camera-to-world) at (0, 0, i), the first fixed,
+    ``n_matches`` Edge_V_V_GICP correspondences between consecutive cameras (point-to-plane, prec0(0.01)) and
+    ``n_points`` marginalised points in front of the cameras, each seen by every camera through an Edge_XYZ_VSC
+    (u v u_r with pixel noise, the disparity's a sixteenth; identity information; one shared record fx fy cx cy
+    baseline).  The points start a little off their true positions, the free cameras off theirs."""
+    rng = _rng(seed, 82)
+    C = num_cams
+    R = np.broadcast_to(np.eye(3), (C, 3, 3)).copy()
+    t = np.stack([np.zeros(C), np.zeros(C), np.arange(C, dtype=np.float64)], 1)
+    box = lambda m: np.stack([(rng.random(m) - 0.5) * 3, rng.random(m) - 0.5, rng.random(m) + 10], 1)  # noqa: E731
+    a = np.arange(n_matches) % (C - 1)
+    meas, info, _ = _gicp_edges(rng, R, t, a, a + 1, box(n_matches), False, euc_noise)
+    pts = box(n_points)
+    fx, fy, cx, cy, bl = kcam
+    pa, ca = np.repeat(np.arange(n_points), C), np.tile(np.arange(C), n_points)
+    pc = pts[pa] - t[ca]  # identity rotations
+    z = np.stack([fx * pc[:, 0] / pc[:, 2] + cx, fy * pc[:, 1] / pc[:, 2] + cy,
+                  fx * (pc[:, 0] - bl) / pc[:, 2] + cx], 1)
+    z += rng.standard_normal(z.shape) * np.array([pix_noise, pix_noise, pix_noise / 16.0])
+    t0 = t + rng.standard_normal((C, 3)) * 0.05
+    R0 = R @ _small_rot(rng, C, 0.01)
+    R0[0], t0[0] = R[0], t[0]
+    cam_ids = np.arange(C, dtype=np.int32)
+    pt_ids = (C + np.arange(n_points)).astype(np.int32)
+    fixed = np.zeros(C, np.int32)
+    fixed[0] = 1
+    cams = VertexSet(V_SE3_QUAT, cam_ids, _iso_vec(R0, t0), fixed, np.zeros(C, np.int32))
+    points = VertexSet(V_XYZ, pt_ids, pts + rng.standard_normal((n_points, 3)) * 0.1, np.zeros(n_points, np.int32),
+                       np.ones(n_points, np.int32))
+    gicp = EdgeSet(E_V_V_GICP, cam_ids[a].copy(), cam_ids[a + 1].copy(), meas, info, None)
+    vsc = EdgeSet(E_XYZ_VSC, pt_ids[pa].copy(), cam_ids[ca].copy(), z,
+                  np.broadcast_to(np.eye(3), (len(pa), 3, 3)).copy(), np.broadcast_to(np.asarray(kcam), (len(pa), 5)).copy())
+    return Problem(f"gicp_sba{n_matches}x{n_points}", [cams, points], [gicp, vsc], 6, 3)
+
+
+def icp_twin(prob: Problem) -> Problem:
+    """The host-Jacobian twin of a graph with types_icp edges: every E_V_V_GICP and E_XYZ_VSC set as an E_HOSTJ(3) set
+    (35) between the same vertices; the caller supplies the payload.  A point-to-plane set and a VSC set keep their
+    information.  A plane-to-plane set carries identity information: its records are whitened, [L^T e | L^T Ji |
+    L^T Jj] with Omega = L L^T at the current state, which gives the same quadratic form and the same chi2 under every
+    robust kernel."""
+    edges = []
+    for es in prob.edges:
+        if es.etype in (E_V_V_GICP, E_XYZ_VSC):
+            plpl = es.etype == E_V_V_GICP and es.params is not None
+            info = np.broadcast_to(np.eye(3), (len(es.v0), 3, 3)).copy() if plpl else es.info.copy()
+            edges.append(EdgeSet(32 + 3, es.v0.copy(), es.v1.copy(), None, info, None))
         else:
             edges.append(es)
     return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)

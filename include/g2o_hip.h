@@ -162,6 +162,34 @@ extern "C" {
                                     first derivatives: rows 0-1 as XYZ2UV, row 2 = -(f/z, 0, -f(x - b)/z^2) applied to
                                     R for the point and to [-[pc]x | I] in (omega, upsilon) order for the camera, i.e.
                                     G2OHIP_E_STEREO_SE3_PROJECT_XYZ's row 2 with bf = f*b */
+/* ---- types_icp (types/icp/types_icp.h): scan registration, what gicp_demo and gicp_sba_demo build. Robust kernels,
+ * edge levels, g2ohip_edge_chi2 and g2ohip_classify_edges take both types like any device type; neither has
+ * isDepthPositive (depth_positive != NULL or check_depth is G2OHIP_ERR_ARG). lm_pcg6_3_eigen refuses a graph that holds
+ * either. ---- */
+#define G2OHIP_E_V_V_GICP 25 /* Edge_V_V_GICP (EDGE_V_V_GICP), types_icp.h:161-238, types_icp.cpp:163-203: v0, v1 both
+                                G2OHIP_V_SE3_QUAT; meas n x 12 in the file's order pos0 normal0 pos1 normal1 (the device
+                                keeps the two positions, the normals stay on the host for g2ohip_save_g2o); info 3x3, the
+                                point-to-plane information the caller supplies (gicp_demo: prec0(0.01)).
+                                error = T0^-1 (T1 pos1) - pos0; the reference's analytic Jacobians
+                                (GICP_ANALYTIC_JACOBIANS). params NULL: point-to-plane. params n x 12 (cov0 then cov1,
+                                each the packed upper triangle 00 01 11 02 12 22): plane-to-plane, Omega =
+                                (cov0 + R01 cov1 R01^T)^-1 is rebuilt on the device at every evaluation (types_icp.h:
+                                220-226; chi2, the robust weight and the quadratic form use it, the Jacobians ignore
+                                its dependence on the state, as the reference's do) and info may be NULL. Deviation:
+                                the reference keeps pl_pl per edge, here it holds for the whole edge set (adding
+                                edges with params to a set without, or the reverse, is G2OHIP_ERR_ARG). A graph whose
+                                active binary edges are all of this type, without marginalised vertices, on one rank,
+                                is assembled pair-major (g2ohip_set_pair_major) */
+#define G2OHIP_E_XYZ_VSC 26  /* Edge_XYZ_VSC, types_icp.h:247-407: v0 G2OHIP_V_XYZ, v1 G2OHIP_V_SE3_QUAT standing for the
+                                VertexSCam (a VertexSE3, camera-to-world, with VertexSE3's oplus; its cached w2n / w2i
+                                are recomputed from the state on the device); meas u v u_r; info 3x3; params n x 5:
+                                fx fy cx cy baseline, the reference's static Kcam and baseline (NULL is
+                                G2OHIP_ERR_ARG; equal records are shared). error = mapPoint(point) - measurement in
+                                mapPoint's order. The reference differentiates numerically (SCAM_ANALYTIC_JACOBIANS is
+                                commented out); the device uses the exact first derivatives. Generic slot path; with
+                                marginalised points the 6/3 Schur kernels, structure_only_3 and landmark shards, as
+                                the other 6/3 projections. No .g2o file carries it (the reference's read / write
+                                return false): g2ohip_save_g2o refuses a graph that holds it */
 /* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3 or 6 (an edge type of the application's own, say): the
  * host supplies the error and the Jacobian as for G2OHIP_E_HOSTJ, payload [e (D) | Ji (D x dim(v0))] row-major per
  * edge. meas unused (may be NULL); info D*D. */
@@ -225,11 +253,14 @@ int g2ohip_add_vertices(g2ohip_graph* g, int type, int n, const int* ids, const 
                         const int* marginalized);
 int g2ohip_add_edges(g2ohip_graph* g, int type, int n, const int* v0, const int* v1, const double* meas,
                      const double* info /* n * D*D row-major */, const double* params /* n*4, stereo n*5, or NULL */);
+/* meas strides are the type's (G2OHIP_E_V_V_GICP: n*12, G2OHIP_E_XYZ_VSC: n*3). info may be NULL only for a
+ * G2OHIP_E_V_V_GICP set in plane-to-plane mode (params given). */
 /* params: the intrinsics of the projection types (G2OHIP_ERR_ARG when one of them gets NULL), the offsets of
  * G2OHIP_E_SE3_PRIOR and G2OHIP_E_SE3_XYZ (n*7, or NULL: identity), offset + intrinsics of G2OHIP_E_SE3_XYZ_DEPTH /
  * _DISPARITY (n*11, NULL is G2OHIP_ERR_ARG), the point and intrinsics of the pose-only projections (Xw fx fy cx cy,
  * n*7, stereo + bf, n*8; NULL is G2OHIP_ERR_ARG), the CameraParameters of G2OHIP_E_PROJECT_XYZ2UV / _XYZ2UVU (f cx cy
- * baseline, n*4; NULL is G2OHIP_ERR_ARG), NULL for the others (G2OHIP_E_SE3_EXPMAP among them). v1: NULL for the unary types (and only for them). */
+ * baseline, n*4; NULL is G2OHIP_ERR_ARG), the two covariances of a plane-to-plane G2OHIP_E_V_V_GICP set (n*12, or NULL:
+ * point-to-plane), fx fy cx cy baseline of G2OHIP_E_XYZ_VSC (n*5; NULL is G2OHIP_ERR_ARG), NULL for the others (G2OHIP_E_SE3_EXPMAP among them). v1: NULL for the unary types (and only for them). */
 /* .g2o files do not carry G2OHIP_E_STEREO_SE3_PROJECT_XYZ: the reference's reader and writer for its tag
  * (EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP, types_six_dof_expmap.cpp:469-493) move four measurement values through a
  * 3-vector and no intrinsics. The loader skips the tag like any unknown one; g2ohip_save_g2o on a graph that holds
@@ -279,6 +310,13 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * or of the wrong type and a short line fail the load, g2ohip_last_error naming the tag or the id. Without the flag
  * both tags are skipped like any unknown one. */
 #define G2OHIP_LOAD_CAMERAPARAMS 32u
+/* G2OHIP_LOAD_ICP (may be combined with the other flags): EDGE_V_V_GICP v0 v1 pos0 normal0 pos1 normal1 (12 values,
+ * types_icp.cpp:124-160) loads as G2OHIP_E_V_V_GICP, point-to-plane, with the information Edge_V_V_GICP::read builds:
+ * R0^T diag(0.01, 0.01, 1) R0, R0 from makeRot0 (types_icp.h:84-96). Deviation: makeRot0 normalises
+ * (0,1,0) - normal0.y normal0 without a check, so a normal0 parallel to (0,1,0) divides by zero; such a line fails the
+ * load with G2OHIP_ERR_ARG (g2ohip_last_error names the line number) and nothing of it is stored. An endpoint that is
+ * missing or no VERTEX_SE3:QUAT and a short line fail the load too. Without the flag the tag is skipped. */
+#define G2OHIP_LOAD_ICP 64u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
@@ -298,7 +336,10 @@ int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, u
  * line per distinct offset in the same id space; G2OHIP_E_SE2_XY_BEARING as EDGE_BEARING_SE2_XY v0 v1 angle info00.
  * G2OHIP_E_PROJECT_XYZ2UV edges are written as EDGE_PROJECT_XYZ2UV:EXPMAP v0 v1 paramId u v and the upper triangle of
  * the information (types_six_dof_expmap.cpp:265-276), with one PARAMS_CAMERAPARAMETERS id focal_length cx cy baseline
- * line per distinct record in the same id space. */
+ * line per distinct record in the same id space. G2OHIP_E_V_V_GICP edges are written as EDGE_V_V_GICP v0 v1 and the 12
+ * values pos0 normal0 pos1 normal1 (types_icp.cpp:206-222): as in the reference the line carries neither the
+ * information nor the covariances, a reader rebuilds the point-to-plane information from normal0. A graph holding
+ * G2OHIP_E_XYZ_VSC edges is not written (G2OHIP_ERR_UNSUPPORTED, nothing written). */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
@@ -340,6 +381,14 @@ long long g2ohip_host_payload_len(g2ohip_graph* g, int edge_type);
 int g2ohip_set_algorithm(g2ohip_graph* g, const char* name);
 /* OptimizationAlgorithmDogleg properties (optimization_algorithm_dogleg.cpp:45-48); a value <= 0 keeps the default:
  * initialDelta 1e4, maxTrialsAfterFailure 100, initialLambda 1e-7, lambdaFactor 10 */
+/* Pair-major assembly (G2OHIP_E_V_V_GICP): a graph whose active binary edges are all Edge_V_V_GICP (unary priors may be
+ * present), with no marginalised vertex and on one rank, sorts its edges by vertex pair, sums each chunk of <= 64
+ * edges of a pair inside the linearize wave and each pair's chunks in one workgroup, instead of writing and reducing
+ * per-edge slots. enable = 0 keeps such a graph on the generic slot path (the same Hpp / b within rounding; for
+ * comparisons), 1 (the default) takes the pair-major path where it applies. Takes effect at the next structure build.
+ * g2ohip_pair_major_info: out[0] = 1 when the built structure is pair-major, out[1] its pairs, out[2] its chunks. */
+int g2ohip_set_pair_major(g2ohip_graph* g, int enable);
+int g2ohip_pair_major_info(g2ohip_graph* g, int out[3]);
 int g2ohip_set_dogleg_params(g2ohip_graph* g, double initial_delta, int max_trials_after_failure,
                              double initial_lambda, double lambda_factor);
 /* state after the last dogleg iteration: out[0] delta (trustRegion()), out[1] lastStep (1 SD, 2 GN, 3 DL, 0 undefined;
