@@ -82,6 +82,14 @@ E_V_V_GICP, E_XYZ_VSC = 25, 26
 ICP_EDGE_TAGS = {E_V_V_GICP: "EDGE_V_V_GICP"}
 
 
+# types/sim3 (include/g2o_hip.h G2OHIP_V_SIM3, G2OHIP_E_SIM3): VertexSim3Expmap, estimate tx ty tz qx qy qz qw s
+# (world->camera), dimension 7; EdgeSim3 between two of them, meas a Sim3 in the same layout, info [n, 7, 7] in (omega,
+# upsilon, sigma) order, params None. SIM3_TAGS: their .g2o tags (load(sim3=True))
+V_SIM3 = 7
+E_SIM3 = 27
+SIM3_TAGS = {"vertex": "VERTEX_SIM3:EXPMAP", "edge": "EDGE_SIM3:EXPMAP"}
+
+
 # EdgeGICP::prec0 / cov0 in numpy, and the packed form of the covariances (ValueError on a normal parallel to (0,1,0))
 gicp_prec, gicp_cov, gicp_pack = synth.gicp_prec, synth.gicp_cov, synth.gicp_pack
 
@@ -113,6 +121,7 @@ LOAD_SBA = 8
 LOAD_OFFSET = 16
 LOAD_CAMERAPARAMS = 32
 LOAD_ICP = 64
+LOAD_SIM3 = 128
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -141,7 +150,7 @@ EXPORTS = [
     "g2ohip_measure_peaks", "g2ohip_set_dogleg_params", "g2ohip_dogleg_state", "g2ohip_dogleg_blend",
     "g2ohip_dogleg_next_delta", "g2ohip_structure_only_calc",
     "g2ohip_set_edge_levels", "g2ohip_get_edge_levels", "g2ohip_initialize_level", "g2ohip_edge_chi2",
-    "g2ohip_classify_edges", "g2ohip_set_pair_major", "g2ohip_pair_major_info",
+    "g2ohip_classify_edges", "g2ohip_set_pair_major", "g2ohip_pair_major_info", "g2ohip_set_sim3_fix_scale",
 ]
 
 # G2OHIP_LEVEL_KEEP: classify_edges leaves the level of the edges on that side as it is
@@ -238,6 +247,7 @@ def lib() -> C.CDLL:
         "g2ohip_set_dogleg_params": ([P, D, I, D, D], I),
         "g2ohip_set_pair_major": ([P, I], I),
         "g2ohip_pair_major_info": ([P, P], I),
+        "g2ohip_set_sim3_fix_scale": ([P, I], I),
         "g2ohip_dogleg_state": ([P, P, I], I),
         "g2ohip_dogleg_blend": ([D, D, D, D, D, D, P], I),
         "g2ohip_dogleg_next_delta": ([D, D, D], D),
@@ -425,7 +435,7 @@ class SparseOptimizer:
         par = None if es.params is None else np.ascontiguousarray(es.params, np.float64)
         pd = synth.PARAM_DIM.get(es.etype)
         md, D = synth.MEAS_DIM.get(es.etype), synth.ERR_DIM.get(es.etype)
-        if es.etype in (E_V_V_GICP, E_XYZ_VSC):  # the C side reads n * md and n * D * D doubles
+        if es.etype in (E_V_V_GICP, E_XYZ_VSC, E_SIM3):  # the C side reads n * md and n * D * D doubles
             if meas is None or meas.size != len(v0) * md:
                 raise G2OHipError(f"add_edges: edge type {es.etype} takes {md} measurement values per edge, got "
                                   f"{0 if meas is None else meas.size} for {len(v0)} edges")
@@ -487,7 +497,7 @@ class SparseOptimizer:
 
     def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False,
              expmap: bool = False, sba: bool = False, offset: bool = False, camparams: bool = False,
-             icp: bool = False):
+             icp: bool = False, sim3: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
         EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
         (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
@@ -495,10 +505,11 @@ class SparseOptimizer:
         EDGE_PROJECT_P2SC), offset=True the offset and bearing tags (EDGE_SE3_OFFSET, EDGE_SE2_OFFSET,
         EDGE_BEARING_SE2_XY + PARAMS_SE3OFFSET, PARAMS_SE2OFFSET), camparams=True g2o's own BA tags
         (EDGE_PROJECT_XYZ2UV:EXPMAP + PARAMS_CAMERAPARAMETERS), icp=True EDGE_V_V_GICP (point-to-plane, the information
-        Edge_V_V_GICP::read builds; a normal0 parallel to (0,1,0) fails the load); all are skipped otherwise."""
+        Edge_V_V_GICP::read builds; a normal0 parallel to (0,1,0) fails the load), sim3=True VERTEX_SIM3:EXPMAP and
+        EDGE_SIM3:EXPMAP; all are skipped otherwise."""
         flags = ((LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0) |
                  (LOAD_SBA if sba else 0) | (LOAD_OFFSET if offset else 0) | (LOAD_CAMERAPARAMS if camparams else 0) |
-                 (LOAD_ICP if icp else 0))
+                 (LOAD_ICP if icp else 0) | (LOAD_SIM3 if sim3 else 0))
         _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:
@@ -524,6 +535,12 @@ class SparseOptimizer:
     def set_pair_major(self, enable: bool = True):
         """g2ohip_set_pair_major: False keeps a graph of Edge_V_V_GICP edges on the generic slot path."""
         _check(lib().g2ohip_set_pair_major(self.h, int(bool(enable))), "set_pair_major")
+
+    def set_sim3_fix_scale(self, on: bool = True):
+        """VertexSim3Expmap::_fix_scale for every V_SIM3 vertex: oplus zeroes update[6] and EdgeSim3's Jacobians lose
+        column 6, as the reference's numeric ones do. H(6, 6) then holds lambda alone: gn_* and dl_* on such a graph
+        are not positive definite."""
+        _check(lib().g2ohip_set_sim3_fix_scale(self.h, int(bool(on))), "set_sim3_fix_scale")
 
     def pair_major_info(self) -> dict:
         """After a structure build: whether it is pair-major, and its pairs and chunks."""

@@ -36,11 +36,13 @@ int guarded(F&& f) {
 int algorithm_known(const std::string& n) {
   // StructureOnlySolver<3> / <2> (solvers/structure_only/structure_only.cpp:64-65)
   if (n == "structure_only_3" || n == "structure_only_2") return 1;
-  // {gn,lm}_hip_{var,fix6_3,fix3_2,fix3_3,fix6_6} (cf. solver_csparse.cpp:51-84 name parsing)
+  // {gn,lm}_hip_{var,fix6_3,fix3_2,fix3_3,fix6_6,fix7_3} (cf. solver_csparse.cpp:51-84 name parsing; fix7_3 is
+  // BlockSolver_7_3, block_solver.h:196-197, here for Sim3 pose graphs without marginalised points)
   if (n.size() < 6) return 0;
   const std::string m = n.substr(0, 3), rest = n.substr(3);
   if (m != "lm_" && m != "gn_" && m != "dl_") return 0;
-  if (rest == "hip_var" || rest == "hip_fix6_3" || rest == "hip_fix3_2" || rest == "hip_fix3_3" || rest == "hip_fix6_6")
+  if (rest == "hip_var" || rest == "hip_fix6_3" || rest == "hip_fix3_2" || rest == "hip_fix3_3" ||
+      rest == "hip_fix6_6" || rest == "hip_fix7_3")
     return 1;
   // Powell's dogleg needs an exact Gauss-Newton solve: the reference registers dl_* over the Cholesky solvers only
   // (solver_csparse.cpp), never over PCG
@@ -52,7 +54,7 @@ int algorithm_known(const std::string& n) {
   if (m == "lm_" && rest == "pcg6_3_eigen") return 1;
   if (rest == "pcg7_3") {
     g_err = n + ": fixed block size 7_3 is not supported by the device PCG (pose blocks of 3 or 6 only; "
-                "use " + m + "pcg)";
+                "use " + m + "hip_fix7_3)";
     return -1;
   }
   return 0;
@@ -109,7 +111,8 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
 }
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
   if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP | G2OHIP_LOAD_SBA |
-                                    G2OHIP_LOAD_OFFSET | G2OHIP_LOAD_CAMERAPARAMS | G2OHIP_LOAD_ICP))) return G2OHIP_ERR_ARG;
+                                    G2OHIP_LOAD_OFFSET | G2OHIP_LOAD_CAMERAPARAMS | G2OHIP_LOAD_ICP |
+                                    G2OHIP_LOAD_SIM3))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
@@ -218,6 +221,10 @@ int g2ohip_set_algorithm(g2ohip_graph* g, const char* name) {
 int g2ohip_set_pair_major(g2ohip_graph* g, int enable) {
   if (!g) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->set_pair_major(enable); });
+}
+int g2ohip_set_sim3_fix_scale(g2ohip_graph* g, int on) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->set_sim3_fix_scale(on); });
 }
 int g2ohip_pair_major_info(g2ohip_graph* g, int* out) {
   if (!g) return G2OHIP_ERR_ARG;

@@ -135,6 +135,7 @@ void classify(int family, const EdgeArgs& a, int ne, const ClassifyArgs& c, hipS
     case FAM_SE2XY_BEARING: classify_launch<FamilySE2XYBearing>(d, ne, c, s); break;
     case FAM_GICP: classify_launch<FamilyGICP>(d, ne, c, s); break;
     case FAM_VSC: classify_launch<FamilyVSC>(d, ne, c, s); break;
+    case FAM_SIM3: classify_launch<FamilySim3>(d, ne, c, s); break;  // no isDepthPositive in the reference
     case FAM_U_SE2: classify_launch<FamilyUnarySE2>(d, ne, c, s); break;
     case FAM_U_SE2XY: classify_launch<FamilyUnarySE2XY>(d, ne, c, s); break;
     case FAM_U_XY: classify_launch<FamilyUnaryXY>(d, ne, c, s); break;

@@ -1640,6 +1640,261 @@ struct FamilyExpmap {
   }
 };
 
+// ================================================================ types/sim3: VertexSim3Expmap, EdgeSim3
+// A similarity g = (q = x y z w, t, s) acts as x -> s R(q) x + t. State and measurement records are [8]:
+// tx ty tz qx qy qz qw s (one 64-B line). Tangent vectors are (omega, upsilon, sigma).
+DI void sim3_load(const double* p, double* q, double* t, double& s) {
+  t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
+  q[0] = p[3]; q[1] = p[4]; q[2] = p[5]; q[3] = p[6];
+  s = p[7];
+}
+// Sim3::operator* (sim3.h:255-261): r = ra * rb, t = sa (ra * tb) + ta, s = sa sb; nothing is normalised
+DI void sim3_mul(const double* qa, const double* ta, double sa, const double* qb, const double* tb, double sb,
+                 double* qo, double* to, double& so) {
+  double rt[3];
+  qrot(qa, tb, rt);
+  to[0] = sa * rt[0] + ta[0]; to[1] = sa * rt[1] + ta[1]; to[2] = sa * rt[2] + ta[2];
+  qmul(qa, qb, qo);
+  so = sa * sb;
+}
+// Sim3::inverse (sim3.h:223-226): Sim3(conj r, conj r * ((-1 / s) t), 1 / s), whose constructor normalises the rotation
+DI void sim3_inv(const double* q, const double* t, double s, double* qo, double* to, double& so) {
+  qo[0] = -q[0]; qo[1] = -q[1]; qo[2] = -q[2]; qo[3] = q[3];
+  const double f = -1 / s;
+  const double v[3] = {f * t[0], f * t[1], f * t[2]};
+  qrot(qo, v, to);
+  so = 1 / s;
+  qnormalize_pos(qo);
+}
+// The coefficients of W = A Omega + B Omega^2 + C I in the four branches of sim3.h:86-128 / 154-205 (|sigma| < eps or
+// not, small_t: theta < eps in exp, d > 1 - eps in log). With DERIV the derivatives of each branch's own formula in
+// theta and sigma: dc = A_th B_th A_s B_s C_s, zero where the branch takes a constant.
+template <bool DERIV>
+DI void sim3_coef(double theta, double sigma, double s, bool small_t, double& A, double& B, double& C, double* dc) {
+  const double eps = 0.00001;
+  if (DERIV) { dc[0] = dc[1] = dc[2] = dc[3] = dc[4] = 0; }
+  if (fabs(sigma) < eps) {
+    C = 1;
+    if (small_t) {
+      A = 1. / 2.;
+      B = 1. / 6.;
+    } else {
+      const double theta2 = theta * theta, sn = sin(theta), cs = cos(theta);
+      A = (1 - cs) / theta2;
+      B = (theta - sn) / (theta2 * theta);
+      if (DERIV) {
+        dc[0] = sn / theta2 - 2 * A / theta;
+        dc[1] = A / theta - 3 * B / theta;
+      }
+    }
+  } else {
+    C = (s - 1) / sigma;
+    const double Cs = (s - C) / sigma;
+    if (DERIV) dc[4] = Cs;
+    const double sigma2 = sigma * sigma;
+    if (small_t) {
+      A = ((sigma - 1) * s + 1) / sigma2;
+      B = ((0.5 * sigma2 - sigma + 1) * s - 1) / (sigma2 * sigma);
+      if (DERIV) {
+        dc[2] = (s - 2 * A) / sigma;
+        dc[3] = (0.5 * s - 3 * B) / sigma;
+      }
+    } else {
+      const double a = s * sin(theta), b = s * cos(theta);
+      const double theta2 = theta * theta, c = theta2 + sigma2;
+      A = (a * sigma + (1 - b) * theta) / (theta * c);
+      const double G = ((b - 1) * sigma + a * theta) / c;
+      B = (C - G) * 1 / theta2;
+      if (DERIV) {
+        const double itc = 1 / (theta * c), ic = 1 / c;
+        dc[0] = (b * sigma + a * theta + (1 - b)) * itc - A * (c + 2 * theta2) * itc;
+        dc[2] = (a + a * sigma - b * theta) * itc - A * 2 * sigma * ic;
+        const double Gt = (-a * sigma + b * theta + a) * ic - G * 2 * theta * ic;
+        const double Gs = (b * sigma + (b - 1) + a * theta) * ic - G * 2 * sigma * ic;
+        dc[1] = -Gt / theta2 - 2 * B / theta;
+        dc[3] = (Cs - Gs) / theta2;
+      }
+    }
+  }
+}
+// Sim3(Vector7) (sim3.h:66-135): the exponential; R through Eigen's Quaternion(Matrix3), not normalised
+DI void sim3_exp(const double* u, double* q, double* t, double& s) {
+  const double w0 = u[0], w1 = u[1], w2 = u[2], sigma = u[6];
+  const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+  const double Om[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
+  double Om2[9];
+  mat3mul(Om, Om, Om2);
+  s = exp(sigma);
+  const bool small_t = theta < 0.00001;
+  double A, B, C;
+  sim3_coef<false>(theta, sigma, s, small_t, A, B, C, nullptr);
+  double ra = 1, rb = 0.5;  // R = I + ra Omega + rb Omega^2
+  if (!small_t) {
+    ra = sin(theta) / theta;
+    rb = (1 - cos(theta)) / (theta * theta);
+  }
+  double R[9], W[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const double I = (k % 4 == 0) ? 1.0 : 0.0;
+    R[k] = I + ra * Om[k] + rb * Om2[k];
+    W[k] = A * Om[k] + B * Om2[k] + C * I;
+  }
+  R_to_quat(R, q);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) t[r] = W[r * 3] * u[3] + W[r * 3 + 1] * u[4] + W[r * 3 + 2] * u[5];
+}
+// The pieces of M = d log(exp(d) g) / d d at 0, the first derivatives of the closed-form log below:
+//   M = [[Jw, 0, 0], [Q, Wi, m], [0, 0, 1]]  (3x3 blocks row-major, m a column)
+struct Sim3LogJac {
+  double Jw[9], Q[9], Wi[9], m[3];
+};
+// Sim3::log (sim3.h:141-220) of (R = toRotationMatrix(q), t, s), all four branches: e = (omega, upsilon, sigma).
+// upsilon = W^-1 t by the cofactor inverse (the reference solves by LU). With DERIV also L:
+//   omega = k(d) deltaR: d deltaR / d dw = tr(R) I - R, d d / d dw = -deltaR^T / 2, so
+//   Jw = k (tr(R) I - R) - k'(d) / 2 deltaR deltaR^T, k = 1 / 2 (k' = 0) or theta / (2 sin theta)
+//   W upsilon = t: d upsilon = W^-1 (dt - dW upsilon), dt = [-[t]x | I | t] d, dW upsilon = P d omega + ps d sigma,
+//   P = (A_th O u + B_th O^2 u) omega^T / theta - A [u]x - B ([O u]x + O [u]x), ps = A_s O u + B_s O^2 u + C_s u
+//   Q = Wi (-[t]x - P Jw), m = upsilon - Wi ps
+template <bool DERIV>
+DI void sim3_log(const double* R, const double* t, double s, double* e, Sim3LogJac* L) {
+  const double sigma = log(s);
+  const double tr = R[0] + R[4] + R[8];
+  const double d = 0.5 * (tr - 1);
+  const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+  const bool small_t = d > 1 - 0.00001;
+  double theta = 0, k = 0.5, kp = 0;
+  if (!small_t) {
+    theta = acos(d);
+    const double sn = sqrt(1 - d * d);
+    k = theta / (2 * sn);
+    if (DERIV) kp = (d * theta / sn - 1) / (2 * sn * sn);
+  }
+  const double w[3] = {k * dR[0], k * dR[1], k * dR[2]};
+  double A, B, C, dc[5];
+  sim3_coef<DERIV>(theta, sigma, s, small_t, A, B, C, dc);
+  const double Om[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  double Om2[9], W[9];
+  mat3mul(Om, Om, Om2);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) W[i] = A * Om[i] + B * Om2[i] + ((i % 4 == 0) ? C : 0.0);
+  double Wi_[9];
+  double* Wi = DERIV ? L->Wi : Wi_;
+  inv3_cofactor(W, Wi);
+  double u[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) u[r] = Wi[r * 3] * t[0] + Wi[r * 3 + 1] * t[1] + Wi[r * 3 + 2] * t[2];
+  e[0] = w[0]; e[1] = w[1]; e[2] = w[2];
+  e[3] = u[0]; e[4] = u[1]; e[5] = u[2];
+  e[6] = sigma;
+  if (!DERIV) return;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      L->Jw[r * 3 + c] = k * ((r == c ? tr : 0.0) - R[r * 3 + c]) - 0.5 * kp * dR[r] * dR[c];
+  double Ou[3], O2u[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) Ou[r] = Om[r * 3] * u[0] + Om[r * 3 + 1] * u[1] + Om[r * 3 + 2] * u[2];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) O2u[r] = Om[r * 3] * Ou[0] + Om[r * 3 + 1] * Ou[1] + Om[r * 3 + 2] * Ou[2];
+  const double ith = small_t ? 0.0 : 1 / theta;  // (dc[0], dc[1] are zero in the small-angle branches)
+  const double Su[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
+  const double SOu[9] = {0, -Ou[2], Ou[1], Ou[2], 0, -Ou[0], -Ou[1], Ou[0], 0};
+  double OSu[9], P[9];
+  mat3mul(Om, Su, OSu);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      P[r * 3 + c] = (dc[0] * Ou[r] + dc[1] * O2u[r]) * (w[c] * ith) - A * Su[r * 3 + c] -
+                     B * (SOu[r * 3 + c] + OSu[r * 3 + c]);
+  double PJ[9];
+  mat3mul(P, L->Jw, PJ);
+  const double St[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
+#pragma unroll
+  for (int i = 0; i < 9; ++i) PJ[i] = -St[i] - PJ[i];
+  mat3mul(Wi, PJ, L->Q);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double ps[3] = {dc[2] * Ou[0] + dc[3] * O2u[0] + dc[4] * u[0], dc[2] * Ou[1] + dc[3] * O2u[1] + dc[4] * u[1],
+                          dc[2] * Ou[2] + dc[3] * O2u[2] + dc[4] * u[2]};
+    L->m[r] = u[r] - (Wi[r * 3] * ps[0] + Wi[r * 3 + 1] * ps[1] + Wi[r * 3 + 2] * ps[2]);
+  }
+}
+// column j of M, and M^T v
+DI void sim3_M_col(const Sim3LogJac& L, int j, double* c) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    c[r] = j < 3 ? L.Jw[r * 3 + (j < 3 ? j : 0)] : 0.0;
+    c[3 + r] = j < 3 ? L.Q[r * 3 + (j < 3 ? j : 0)] : (j < 6 ? L.Wi[r * 3 + (j < 6 ? j - 3 : 0)] : L.m[r]);
+  }
+  c[6] = j == 6 ? 1.0 : 0.0;
+}
+// Ad(g) = [[R, 0, 0], [[t]x R, s R, -t], [0, 0, 1]] of g = (R, t, s), applied without forming it: column j, and Ad^T v
+DI void sim3_ad_col(const double* R, const double* t, double s, int j, double* c) {
+  if (j < 3) {
+    const double r0 = R[j], r1 = R[3 + j], r2 = R[6 + j];
+    c[0] = r0; c[1] = r1; c[2] = r2;
+    c[3] = t[1] * r2 - t[2] * r1;
+    c[4] = t[2] * r0 - t[0] * r2;
+    c[5] = t[0] * r1 - t[1] * r0;
+    c[6] = 0;
+  } else if (j < 6) {
+    c[0] = c[1] = c[2] = 0;
+    c[3] = s * R[j - 3]; c[4] = s * R[3 + j - 3]; c[5] = s * R[6 + j - 3];
+    c[6] = 0;
+  } else {
+    c[0] = c[1] = c[2] = 0;
+    c[3] = -t[0]; c[4] = -t[1]; c[5] = -t[2];
+    c[6] = 1;
+  }
+}
+DI void sim3_adT_apply(const double* R, const double* t, double s, const double* v, double* o) {
+  // omega: R^T (v_w - t x v_u); upsilon: s R^T v_u; sigma: v_s - t . v_u
+  const double a[3] = {v[0] - (t[1] * v[5] - t[2] * v[4]), v[1] - (t[2] * v[3] - t[0] * v[5]),
+                       v[2] - (t[0] * v[4] - t[1] * v[3])};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    o[c] = R[c] * a[0] + R[3 + c] * a[1] + R[6 + c] * a[2];
+    o[3 + c] = s * (R[c] * v[3] + R[3 + c] * v[4] + R[6 + c] * v[5]);
+  }
+  o[6] = v[6] - (t[0] * v[3] + t[1] * v[4] + t[2] * v[5]);
+}
+
+// ---- EdgeSim3 (types_seven_dof_expmap.h:110-137): v0 = S0, v1 = S1, both Sim3 [8]; meas payload = the measurement C
+// as stored [8] (rotation normalised, w >= 0), info packed upper 28 in (omega, upsilon, sigma) order.
+// error = log(C * S0 * S1^-1). The family has no linearize(): its Jacobians Ji = M Ad(C), Jj = -M Ad(E) are never formed,
+// k_linearize_sim3 (kernels.hip) builds the quadratic form from M^T Omega M and the two adjoints. EdgeData::ue bit 3:
+// the vertices' _fix_scale (column 6 of both Jacobians is zero). ----
+struct FamilySim3 {
+  static constexpr int D = 7, DA = 7, DB = 7, MEAS = 8, INFO = 28;
+  // E = C * S0 * S1^-1 as (R_E, t_E, s_E); with WANT_C also C as (R_C, t_C, s_C)
+  template <bool WANT_C>
+  DI static void error_transform(const EdgeData& d, int e, double* RE, double* tE, double& sE, double* RC, double* tC,
+                                 double& sC) {
+    double qc[4], tc[3], sc, q0[4], t0[3], s0, q1[4], t1[3], s1;
+    sim3_load(d.meas + (size_t)e * 8, qc, tc, sc);
+    sim3_load(d.s0 + (size_t)d.v0[e] * 8, q0, t0, s0);
+    sim3_load(d.s1 + (size_t)d.v1[e] * 8, q1, t1, s1);
+    double qa[4], ta[3], sa, qi[4], ti[3], si, qe[4];
+    sim3_mul(qc, tc, sc, q0, t0, s0, qa, ta, sa);
+    sim3_inv(q1, t1, s1, qi, ti, si);
+    sim3_mul(qa, ta, sa, qi, ti, si, qe, tE, sE);
+    quat_to_R(qe[0], qe[1], qe[2], qe[3], RE);
+    if (WANT_C) {
+      quat_to_R(qc[0], qc[1], qc[2], qc[3], RC);
+      tC[0] = tc[0]; tC[1] = tc[1]; tC[2] = tc[2];
+      sC = sc;
+    }
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double RE[9], tE[3], sE, sC;
+    error_transform<false>(d, e, RE, tE, sE, nullptr, nullptr, sC);
+    sim3_log<false>(RE, tE, sE, err, nullptr);
+  }
+};
+
 // ---- EdgeSE3ProjectXYZOnlyPose (types_six_dof_expmap.h:242-246, .cpp:569-599), unary: v0 = camera SE3Quat [8];
 // meas payload u v | Xw (5), info packed 3, params fx fy cx cy (one shared record when EdgeData::ue bit 1 is set).
 // error = obs - cam_project(T.map(Xw)); the Jacobian in the reference's invz / invz_2 products ----

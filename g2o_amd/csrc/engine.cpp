@@ -33,11 +33,13 @@ static double wall() {
 }
 
 int vertex_dim(int t) {
+  if (t == G2OHIP_V_SIM3) return 7;
   return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT || t == G2OHIP_V_CAM ? 6
          : (t == G2OHIP_V_XYZ || t == G2OHIP_V_SE2 ? 3 : (t == G2OHIP_V_XY ? 2 : -1));
 }
 int vertex_est_dim(int t) {
   if (t == G2OHIP_V_CAM) return 12;  // the VERTEX_CAM line: x y z qx qy qz qw fx fy cx cy baseline
+  if (t == G2OHIP_V_SIM3) return 8;  // tx ty tz qx qy qz qw s
   return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT ? 7 : (t == G2OHIP_V_XY ? 2 : 3);
 }
 int vertex_state_stride(int t) {
@@ -48,11 +50,12 @@ int vertex_state_stride(int t) {
     case G2OHIP_V_SE2: return 3;
     case G2OHIP_V_XY: return 2;
     case G2OHIP_V_CAM: return 12;
+    case G2OHIP_V_SIM3: return 8;
   }
   return 0;
 }
-static bool is_hostj_binary(int e) { return e > G2OHIP_E_HOSTJ(0) && e <= G2OHIP_E_HOSTJ(6); }
-static bool is_hostj_unary(int e) { return e > G2OHIP_E_HOSTJ_UNARY(0) && e <= G2OHIP_E_HOSTJ_UNARY(6); }
+static bool is_hostj_binary(int e) { return e > G2OHIP_E_HOSTJ(0) && e <= G2OHIP_E_HOSTJ(7); }
+static bool is_hostj_unary(int e) { return e > G2OHIP_E_HOSTJ_UNARY(0) && e <= G2OHIP_E_HOSTJ_UNARY(7); }
 // host-Jacobian edge types of either arity
 static bool is_hostj(int e) { return is_hostj_binary(e) || is_hostj_unary(e); }
 // the slam3d landmark edges: EdgeSE3PointXYZ, ...Depth, ...Disparity
@@ -84,6 +87,7 @@ int edge_dim(int e) {
     case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: case G2OHIP_E_SE3_OFFSET: return 6;
     case G2OHIP_E_SE2_OFFSET: return 3;
     case G2OHIP_E_SE2_XY_BEARING: return 1;
+    case G2OHIP_E_SIM3: return 7;
   }
   return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 6 : (e == G2OHIP_E_SE2 ? 3 : -1));
 }
@@ -92,6 +96,7 @@ int edge_meas_dim(int e) {
   if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR || e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 2;
   if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_EXPMAP || e == G2OHIP_E_SE3_OFFSET) return 7;
   if (e == G2OHIP_E_SE2_XY_BEARING) return 1;  // (G2OHIP_E_SE2_OFFSET: x y theta, the default below)
+  if (e == G2OHIP_E_SIM3) return 8;            // the measurement as a Sim3: tx ty tz qx qy qz qw s
   if (is_slam3d_type(e)) return 3;
   if (is_sba_type(e)) return e == G2OHIP_E_PROJECT_P2MC ? 2 : 3;
   if (is_camparams_type(e)) return e == G2OHIP_E_PROJECT_XYZ2UV ? 2 : 3;
@@ -198,6 +203,93 @@ void se3quat_inverse(const double* tq /*t3 q4*/, double* out) {
   out[0] = r[0]; out[1] = r[1]; out[2] = r[2];
   out[3] = qc[0]; out[4] = qc[1]; out[5] = qc[2]; out[6] = qc[3];
 }
+// ---- Sim3 (types/sim3/sim3.h) on the host, for minimal_state and the .g2o lines; records tx ty tz qx qy qz qw s
+void mat3mul_h(const double* A, const double* B, double* C) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
+}
+// A, B, C of W = A Omega + B Omega^2 + C I (sim3.h:86-128, 154-205)
+void sim3_coef_h(double theta, double sigma, double s, bool small_t, double& A, double& B, double& C) {
+  const double eps = 0.00001;
+  if (std::fabs(sigma) < eps) {
+    C = 1;
+    if (small_t) { A = 1. / 2.; B = 1. / 6.; }
+    else {
+      const double theta2 = theta * theta;
+      A = (1 - std::cos(theta)) / theta2;
+      B = (theta - std::sin(theta)) / (theta2 * theta);
+    }
+  } else {
+    C = (s - 1) / sigma;
+    const double sigma2 = sigma * sigma;
+    if (small_t) {
+      A = ((sigma - 1) * s + 1) / sigma2;
+      B = ((0.5 * sigma2 - sigma + 1) * s - 1) / (sigma2 * sigma);
+    } else {
+      const double a = s * std::sin(theta), b = s * std::cos(theta), theta2 = theta * theta, c = theta2 + sigma2;
+      A = (a * sigma + (1 - b) * theta) / (theta * c);
+      B = (C - ((b - 1) * sigma + a * theta) / c) * 1 / theta2;
+    }
+  }
+}
+void sim3_exp_h(const double* u, double* out) {  // Sim3(Vector7), :66-135
+  const double theta = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), sigma = u[6], s = std::exp(sigma);
+  const double Om[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
+  double Om2[9], A, B, C;
+  mat3mul_h(Om, Om, Om2);
+  const bool small_t = theta < 0.00001;
+  sim3_coef_h(theta, sigma, s, small_t, A, B, C);
+  const double ra = small_t ? 1.0 : std::sin(theta) / theta, rb = small_t ? 0.5 : (1 - std::cos(theta)) / (theta * theta);
+  double R[9], W[9];
+  for (int k = 0; k < 9; ++k) {
+    const double I = k % 4 == 0 ? 1.0 : 0.0;
+    R[k] = I + ra * Om[k] + rb * Om2[k];
+    W[k] = A * Om[k] + B * Om2[k] + C * I;
+  }
+  R2q(R, out + 3);
+  for (int r = 0; r < 3; ++r) out[r] = W[r * 3] * u[3] + W[r * 3 + 1] * u[4] + W[r * 3 + 2] * u[5];
+  out[7] = s;
+}
+void sim3_log_h(const double* g, double* out) {  // Sim3::log, :141-220; upsilon = W^-1 t by Cramer's rule
+  double R[9];
+  q2R(g[3], g[4], g[5], g[6], R);
+  const double sigma = std::log(g[7]), d = 0.5 * (R[0] + R[4] + R[8] - 1);
+  const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+  const bool small_t = d > 1 - 0.00001;
+  double theta = 0, k = 0.5;
+  if (!small_t) {
+    theta = std::acos(d);
+    k = theta / (2 * std::sqrt(1 - d * d));
+  }
+  const double w[3] = {k * dR[0], k * dR[1], k * dR[2]};
+  double A, B, C;
+  sim3_coef_h(theta, sigma, g[7], small_t, A, B, C);
+  const double Om[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  double Om2[9], W[9];
+  mat3mul_h(Om, Om, Om2);
+  for (int i = 0; i < 9; ++i) W[i] = A * Om[i] + B * Om2[i] + (i % 4 == 0 ? C : 0.0);
+  auto det3 = [](const double* M) {
+    return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
+  };
+  const double det = det3(W);
+  for (int c = 0; c < 3; ++c) {
+    double Wc[9];
+    for (int i = 0; i < 9; ++i) Wc[i] = W[i];
+    for (int r = 0; r < 3; ++r) Wc[r * 3 + c] = g[r];
+    out[3 + c] = det3(Wc) / det;
+  }
+  out[0] = w[0]; out[1] = w[1]; out[2] = w[2];
+  out[6] = sigma;
+}
+void sim3_inverse_h(const double* g, double* out) {  // Sim3::inverse, :223-226 (the constructor normalises)
+  double qc[4] = {-g[3], -g[4], -g[5], g[6]};
+  const double f = -1 / g[7];
+  const double v[3] = {f * g[0], f * g[1], f * g[2]};
+  qrot_h(qc, v, out);
+  qnorm_pos(qc);
+  out[3] = qc[0]; out[4] = qc[1]; out[5] = qc[2]; out[6] = qc[3];
+  out[7] = 1 / g[7];
+}
 }  // namespace
 
 void set_state_from_est(int vt, const double* est, double* st) {
@@ -222,6 +314,14 @@ void set_state_from_est(int vt, const double* est, double* st) {
       st[0] = est[0]; st[1] = est[1]; st[2] = est[2];
       st[3] = q[0]; st[4] = q[1]; st[5] = q[2]; st[6] = q[3];
       for (int k = 7; k < 12; ++k) st[k] = est[k];
+      break;
+    }
+    case G2OHIP_V_SIM3: {  // Sim3(q, t, s) (sim3.h:53-57): normalizeRotation, w >= 0 and unit length
+      double q[4] = {est[3], est[4], est[5], est[6]};
+      qnorm_pos(q);
+      st[0] = est[0]; st[1] = est[1]; st[2] = est[2];
+      st[3] = q[0]; st[4] = q[1]; st[5] = q[2]; st[6] = q[3];
+      st[7] = est[7];
       break;
     }
   }
@@ -258,6 +358,7 @@ void minimal_from_state(int vt, const double* st, double* out) {
       out[3] = sg * q[0] / n; out[4] = sg * q[1] / n; out[5] = sg * q[2] / n;
       break;
     }
+    case G2OHIP_V_SIM3: sim3_log_h(st, out); break;  // (omega, upsilon, sigma)
     default:
       for (int k = 0; k < vertex_dim(vt); ++k) out[k] = st[k];
       break;
@@ -1241,6 +1342,7 @@ int Engine::add_vertices(int type, int n, const int* ids, const double* est, con
     hg.st[type].resize(o + sd, 0.0);
     set_state_from_est(type, est + (size_t)k * ed, hg.st[type].data() + o);
     if (type == G2OHIP_V_SE3_QUAT) hg.nopl.push_back(0);
+    if (type == G2OHIP_V_SIM3) hg.sim3_cam.insert(hg.sim3_cam.end(), {1.0, 1.0, 0.0, 0.0});  // (:43-57)
   }
   initialized = false;
   device_state_dirty = true;
@@ -1260,6 +1362,7 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
   if (!info && n > 0 && !(gicp && params)) return G2OHIP_ERR_ARG;  // only a plane-to-plane set goes without one
   if (is_sba_type(type) && params) return G2OHIP_ERR_ARG;  // the intrinsics live in the VertexCam
   if (type == G2OHIP_E_SE2_XY_BEARING && params) return G2OHIP_ERR_ARG;  // EdgeSE2PointXYBearing has no parameter
+  if (type == G2OHIP_E_SIM3 && params) return G2OHIP_ERR_ARG;            // nor has EdgeSim3
   const int nm = edge_meas_dim(type);
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
@@ -1345,7 +1448,8 @@ struct ParsedVertex { int type, id; double est[12]; };  // (12: VERTEX_CAM)
 // unary: b = -1, or the SE3 prior's parameter id; pid: the slam3d landmark edges' parameter id
 // (the offset edges: pid the from vertex's parameter id, pid2 the to vertex's; p the two records)
 // (EDGE_V_V_GICP: m the 12 values pos0 normal0 pos1 normal1; at: the start of the line, for a message's line number)
-struct ParsedEdge { int type, a, b; double m[12], info[36], p[14]; int pid = -1, pid2 = -1; const char* at = nullptr; };
+// (info: up to EDGE_SIM3:EXPMAP's 7 x 7)
+struct ParsedEdge { int type, a, b; double m[12], info[49], p[14]; int pid = -1, pid2 = -1; const char* at = nullptr; };
 // PARAMS_SE3OFFSET id x y z qx qy qz qw; camera: PARAMS_CAMERACALIB, the same followed by fx fy cx cy; se2:
 // PARAMS_SE2OFFSET id x y theta; camparams: PARAMS_CAMERAPARAMETERS id focal_length cx cy baseline
 struct ParsedParam { int id; double v[11]; bool camera = false, se2 = false, camparams = false; };
@@ -1386,9 +1490,9 @@ struct Cursor {
 // expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP); sba: VERTEX_CAM, EDGE_PROJECT_P2MC, EDGE_PROJECT_P2SC (G2OHIP_LOAD_SBA)
 // offset: PARAMS_SE3OFFSET, PARAMS_SE2OFFSET, EDGE_SE3_OFFSET, EDGE_SE2_OFFSET, EDGE_BEARING_SE2_XY (G2OHIP_LOAD_OFFSET)
 // camparams: PARAMS_CAMERAPARAMETERS, EDGE_PROJECT_XYZ2UV:EXPMAP (G2OHIP_LOAD_CAMERAPARAMS)
-// icp: EDGE_V_V_GICP (G2OHIP_LOAD_ICP)
+// icp: EDGE_V_V_GICP (G2OHIP_LOAD_ICP); sim3: VERTEX_SIM3:EXPMAP, EDGE_SIM3:EXPMAP (G2OHIP_LOAD_SIM3)
 void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, bool sba, bool offset,
-                 bool camparams, bool icp, ParsedChunk& out) {
+                 bool camparams, bool icp, bool sim3, ParsedChunk& out) {
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1434,6 +1538,32 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
         c.ok = false;
       }
       out.verts.push_back(v);
+    } else if (sim3 && tag == "VERTEX_SIM3:EXPMAP") {
+      // VertexSim3Expmap::read (types_seven_dof_expmap.cpp:66-87): the log of cam2world, then fx fy cx cy of camera 1;
+      // the estimate is Sim3(v).inverse(). A line that ends after the seven values keeps the constructor's intrinsics
+      // 1 1 0 0 (:43-57); any other length fails the load. est[8..11]: the intrinsics, kept on the host for save
+      ParsedVertex v{G2OHIP_V_SIM3, c.i(), {}};
+      double w[11] = {0, 0, 0, 0, 0, 0, 0, 1, 1, 0, 0}, g[8];
+      int nv = 0;
+      while (c.ok && c.more()) {
+        const double x = c.d();
+        if (c.ok && nv < 11) w[nv] = x;
+        ++nv;
+      }
+      if (nv != 7 && nv != 11) c.ok = false;
+      sim3_exp_h(w, g);
+      sim3_inverse_h(g, v.est);
+      std::memcpy(v.est + 8, w + 7, sizeof(double) * 4);
+      out.verts.push_back(v);
+    } else if (sim3 && tag == "EDGE_SIM3:EXPMAP") {  // EdgeSim3::read (:104-122): the measurement is Sim3(m).inverse()
+      ParsedEdge ed{G2OHIP_E_SIM3, c.i(), c.i(), {}, {}, {}};
+      double w[7], g[8];
+      for (double& x : w) x = c.d();
+      sim3_exp_h(w, g);
+      sim3_inverse_h(g, ed.m);
+      for (int r = 0; r < 7; ++r)
+        for (int q = r; q < 7; ++q) ed.info[r * 7 + q] = ed.info[q * 7 + r] = c.d();
+      out.edges.push_back(ed);
     } else if (sba && (tag == "EDGE_PROJECT_P2MC" || tag == "EDGE_PROJECT_P2SC")) {
       // types_sba.cpp:204-237: point, camera, the measurement; the information is the identity
       const int D = tag == "EDGE_PROJECT_P2MC" ? 2 : 3;
@@ -1569,7 +1699,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0,
              expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0, sba = (flags & G2OHIP_LOAD_SBA) != 0,
              offset = (flags & G2OHIP_LOAD_OFFSET) != 0, camparams = (flags & G2OHIP_LOAD_CAMERAPARAMS) != 0,
-             icp = (flags & G2OHIP_LOAD_ICP) != 0;
+             icp = (flags & G2OHIP_LOAD_ICP) != 0, sim3 = (flags & G2OHIP_LOAD_SIM3) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1598,7 +1728,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
       th.emplace_back(
-          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, camparams, icp, chunks[t]); });
+          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, camparams, icp, sim3, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1632,6 +1762,10 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
       mg.push_back((v.type == G2OHIP_V_XYZ || v.type == G2OHIP_V_XY) && marginalize_xyz ? 1 : 0);
     }
   if (int r = flush_v(cur)) return r;
+  for (auto& c : chunks)  // the intrinsics of the VERTEX_SIM3:EXPMAP lines
+    for (auto& v : c.verts)
+      if (v.type == G2OHIP_V_SIM3)
+        std::memcpy(hg.sim3_cam.data() + (size_t)hg.verts[hg.idmap[v.id]].local * 4, v.est + 8, sizeof(double) * 4);
   // edges in file order, batched per run of one type
   std::vector<int> ea, eb;
   std::vector<double> em, ei, ep;
@@ -1679,6 +1813,14 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
             throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: EDGE_SE3:EXPMAP " + std::to_string(ed.a) + " -> " +
                                                   std::to_string(ed.b) + ": vertex " + std::to_string(id) +
                                                   " is missing or no VERTEX_SE3:EXPMAP");
+        }
+      if (ed.type == G2OHIP_E_SIM3)  // both endpoints are VERTEX_SIM3:EXPMAP
+        for (int id : {ed.a, ed.b}) {
+          auto it = hg.idmap.find(id);
+          if (it == hg.idmap.end() || hg.verts[it->second].type != G2OHIP_V_SIM3)
+            throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: EDGE_SIM3:EXPMAP " + std::to_string(ed.a) + " -> " +
+                                                  std::to_string(ed.b) + ": vertex " + std::to_string(id) +
+                                                  " is missing or no VERTEX_SIM3:EXPMAP");
         }
       if (is_sba_type(ed.type)) {  // v0 a VERTEX_XYZ point, v1 a VERTEX_CAM
         const char* tg = ed.type == G2OHIP_E_PROJECT_P2MC ? "EDGE_PROJECT_P2MC " : "EDGE_PROJECT_P2SC ";
@@ -1896,6 +2038,15 @@ int Engine::save(const char* path) {
         case G2OHIP_V_SE2: L.tag("VERTEX_SE2"); break;
         case G2OHIP_V_XY: L.tag("VERTEX_XY"); ne = 2; break;
         case G2OHIP_V_CAM: L.tag("VERTEX_CAM"); ne = 12; break;  // types_sba.cpp:114-131
+        case G2OHIP_V_SIM3: {  // types_seven_dof_expmap.cpp:89-102: log of cam2world, then fx fy cx cy of camera 1
+          double g[8];
+          L.tag("VERTEX_SIM3:EXPMAP");
+          sim3_inverse_h(e, g);
+          sim3_log_h(g, e);
+          std::memcpy(e + 7, hg.sim3_cam.data() + (size_t)v.local * 4, sizeof(double) * 4);
+          ne = 11;
+          break;
+        }
       }
       L.i(v.id);
       for (int q = 0; q < ne; ++q) L.d(e[q]);
@@ -1942,6 +2093,14 @@ int Engine::save(const char* path) {
           L.tag("EDGE_SE3:EXPMAP"); L.i(a); L.i(b);
           for (int q = 0; q < 7; ++q) L.d(w[q]);
           for (int r = 0; r < 6; ++r) for (int q = r; q < 6; ++q) L.d(I[r * 6 + q]);
+        } else if (es.type == G2OHIP_E_SIM3) {  // types_seven_dof_expmap.cpp:124-137: log of the inverse measurement
+          double c[8], g[8], w[7];
+          set_state_from_est(G2OHIP_V_SIM3, m, c);  // the measurement as the edge holds it: rotation normalised
+          sim3_inverse_h(c, g);
+          sim3_log_h(g, w);
+          L.tag("EDGE_SIM3:EXPMAP"); L.i(a); L.i(b);
+          for (int q = 0; q < 7; ++q) L.d(w[q]);
+          for (int r = 0; r < 7; ++r) for (int q = r; q < 7; ++q) L.d(I[r * 7 + q]);
         } else if (is_sba_type(es.type)) {  // types_sba.cpp:215-244: the measurement alone (g2ohip_save_g2o has
                                             // refused a graph whose information is not the identity)
           L.tag(es.type == G2OHIP_E_PROJECT_P2MC ? "EDGE_PROJECT_P2MC" : "EDGE_PROJECT_P2SC"); L.i(a); L.i(b);
@@ -2135,6 +2294,7 @@ static int family_of(int etype, int& vtA, int& vtB) {
     case G2OHIP_E_SE2_XY_BEARING: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY_BEARING;
     case G2OHIP_E_V_V_GICP: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_GICP;
     case G2OHIP_E_XYZ_VSC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_QUAT; return FAM_VSC;
+    case G2OHIP_E_SIM3: vtA = vtB = G2OHIP_V_SIM3; return FAM_SIM3;
     // unary types: vtB = 0 (no second vertex)
     case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
     case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
@@ -2231,7 +2391,11 @@ int Engine::initialize_level(int level) {  // sparse_optimizer.cpp:201-279 + bui
   for (int vi : ivmap) {
     const HVertex& v = hg.verts[vi];
     if (!v.marg) {
-      if (pd && pd != v.dim) return G2OHIP_ERR_UNSUPPORTED;  // BlockSolver<p, l>: one pose block size
+      if (pd && pd != v.dim)  // BlockSolver<p, l>: one pose block size
+        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                          "the free non-marginalised vertices have dimensions " + std::to_string(pd) + " and " +
+                              std::to_string(v.dim) + " (vertex " + std::to_string(v.id) +
+                              "): BlockSolver<p, l> takes one pose block size");
       pd = v.dim;
       ++num_poses;
     } else {
@@ -2245,6 +2409,10 @@ int Engine::initialize_level(int level) {  // sparse_optimizer.cpp:201-279 + bui
   size_landmarks = num_landmarks * ld;
   do_schur = num_landmarks > 0;  // optimization_algorithm_with_hessian.cpp:48-73
   // the Schur kernels are instantiated for BlockSolver_6_3 and BlockSolver_3_2 (block_solver.h:188-201)
+  if (do_schur && pd == 7 && ld == 3)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                      "marginalised points under Sim3 poses need BlockSolver_7_3, whose 7/3 Schur kernels do not "
+                      "exist; fix the points (EdgeSim3ProjectXYZ enters as G2OHIP_E_HOSTJ(2) from a fixed point)");
   if (do_schur && !((pd == 6 && ld == 3) || (pd == 3 && ld == 2))) return G2OHIP_ERR_UNSUPPORTED;
   // landmark-landmark edges have no place in BlockSolver's Schur layout here (a prior on a landmark is no such edge:
   // it lands in the landmark's own Hll block)
@@ -2458,7 +2626,7 @@ EdgeArgs Engine::group_args(const EGroup& g) const {
   a.D = g.D;
   a.DA = g.DA;
   a.DB = g.DB;
-  a.ue = g.ue;
+  a.ue = g.ue | (g.family == FAM_SIM3 && sim3_fix_scale_ ? 8 : 0);
   return a;
 }
 
@@ -2527,6 +2695,7 @@ void Engine::fill_group_device(EGroup& g) {
     case FAM_SE2XY_BEARING: mmeas = 1; break;
     case FAM_GICP: mmeas = 6; break;            // pos0 | pos1 (the normals stay on the host, for save)
     case FAM_VSC: mmeas = 3; break;
+    case FAM_SIM3: mmeas = 8; break;            // the measurement as a Sim3, one 64-byte record
   }
   const bool gicp_plpl = g.family == FAM_GICP && !es.params.empty();
   // device parameter record: the BA intrinsics as given (a CameraParameters record expanded: ba_device_params);
@@ -2615,6 +2784,8 @@ void Engine::fill_group_device(EGroup& g) {
       for (int j = 0; j < 3; ++j) mo[j] = m[j];
       for (int j = 0; j < 4; ++j) mo[3 + j] = q[j] / n;
       mo[7] = 0;
+    } else if (g.family == FAM_SIM3) {  // Sim3(q, t, s), sim3.h:53-57: normalizeRotation (w >= 0, unit)
+      set_state_from_est(G2OHIP_V_SIM3, m, mo);
     } else if (is_pose_only_family(g.family)) {  // caller's record Xw fx fy cx cy (bf) -> payload obs | Xw, intrinsics
       const int np = edge_param_dim(es.type);
       const double* p = es.params.data() + (size_t)e * np;
@@ -2643,7 +2814,7 @@ void Engine::fill_group_device(EGroup& g) {
     g.ue = 0;
     if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family) ||
          is_sba_family(g.family) || is_offset_family(g.family) || g.family == FAM_SE2XY_BEARING ||
-         g.family == FAM_GICP || g.family == FAM_VSC) && gne > 1 &&
+         g.family == FAM_GICP || g.family == FAM_VSC || g.family == FAM_SIM3) && gne > 1 &&
         !(ev && atoi(ev) == 0)) {
       auto uniform = [&](const std::vector<double>& v, int st) {
         for (int k = 1; k < gne; ++k)
@@ -3116,6 +3287,10 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
                       algorithm + ": Powell's dogleg is not supported on a sharded graph (" + std::to_string(nranks) +
                           " ranks): it multiplies by Hpp (multiplyHessian), and a landmark shard's Hpp diagonal "
                           "blocks are partial sums; use lm_hip_* or gn_hip_* there");
+  if ((use_pcg() || use_cgls()) && pd == 7)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                      algorithm + ": the device PCG and the matrix-free CGLS take pose blocks of 3 or 6, a Sim3 graph has "
+                                  "blocks of 7; use lm_hip_var or lm_hip_fix7_3");
   if (use_cgls())
     for (const HEdgeSet& es : hg.esets)
       if (is_slam3d_type(es.type) && !es.ev0.empty())
@@ -3374,7 +3549,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
   db.zero(stream);
   dx.resize(std::max<long long>(n, 1));
   dx.zero(stream);
-  for (int d : {2, 3, 6})  // the fused BA path needs no slots
+  for (int d : {2, 3, 6, 7})  // the fused BA path needs no slots
     dslot[d].resize((size_t)std::max<long long>(ba_fused ? 1 : nslot[d], 1) * (d * (d + 1) / 2 + d));
   // vertex incidence lists (hessian order): code = slot index in the arena of the vertex's dimension, in
   // group / edge order (a fixed summation order)
@@ -4256,6 +4431,7 @@ void Engine::update_async(const double* x) {  // sparse_optimizer.cpp:441-454
     L.xoff[L.cnt] = d_xoff[t].get();
     L.st[L.cnt] = dstate[t].get();
     if (t == G2OHIP_V_SE3_QUAT) L.nopl = dnopl.get();
+    if (t == G2OHIP_V_SIM3) L.sim3_fix_scale = sim3_fix_scale_ ? 1 : 0;
     ++L.cnt;
   }
   launch::oplus_multi(L, x ? x : dx.get(), stream);
@@ -4582,6 +4758,14 @@ int Engine::set_pair_major(int enable) {
   if (pm_force_slot != (enable == 0)) {
     pm_force_slot = enable == 0;
     structure_built = false;  // the edge order, the slots and the incidence lists follow the path
+  }
+  return G2OHIP_OK;
+}
+int Engine::set_sim3_fix_scale(int on) {
+  if (on != 0 && on != 1) return G2OHIP_ERR_ARG;
+  if (sim3_fix_scale_ != (on == 1)) {
+    sim3_fix_scale_ = on == 1;
+    built_ver = 0;  // a system assembled ahead of time holds the other Jacobians
   }
   return G2OHIP_OK;
 }
@@ -5154,7 +5338,8 @@ double Engine::kernel_bytes(const std::string& name) const {
       by += g.ne * (8.0 + (g.vtB ? 4.0 : 0.0) + g.D * 8.0 + ((g.ue & 1) ? 0.0 : g.D * (g.D + 1) / 2 * 8.0) +
                     ((g.ue & 2) ? 0.0 : np * 8.0));
     }
-    for (int t : {G2OHIP_V_SE3_EXPMAP, G2OHIP_V_SE3_QUAT, G2OHIP_V_SE2, G2OHIP_V_CAM}) by += dstate[t].bytes();
+    for (int t : {G2OHIP_V_SE3_EXPMAP, G2OHIP_V_SE3_QUAT, G2OHIP_V_SE2, G2OHIP_V_CAM, G2OHIP_V_SIM3})
+      by += dstate[t].bytes();
     return by;
   }
   if (name == "backsub") return local_lm.size() * (3 * 8.0 * 2 + 72) + npl * (pb + 4) + size_poses * 8.0;

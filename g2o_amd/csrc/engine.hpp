@@ -21,7 +21,7 @@
 
 namespace g2ohip {
 
-constexpr int NVT = 7;  // vertex type codes 1..6 (G2OHIP_V_*)
+constexpr int NVT = 8;  // vertex type codes 1..7 (G2OHIP_V_*)
 int vertex_dim(int vtype);
 int vertex_est_dim(int vtype);
 int vertex_state_stride(int vtype);
@@ -58,6 +58,7 @@ struct HostGraph {
   std::vector<double> st[NVT];            // per type, device layout
   std::vector<std::vector<int>> by_type = std::vector<std::vector<int>>(NVT);  // local -> vertex
   std::vector<int> nopl;                // VertexSE3 oplus counters (per local SE3QUAT vertex)
+  std::vector<double> sim3_cam;         // per local Sim3 vertex: fx fy cx cy of its VERTEX_SIM3:EXPMAP line (1 1 0 0)
   std::vector<HEdgeSet> esets;          // in first-seen type order
   long long num_edges() const {
     long long n = 0;
@@ -249,6 +250,8 @@ class Engine {
   int set_dogleg_params(double initial_delta, int max_trials, double initial_lambda, double lambda_factor);
   int set_pair_major(int enable);
   int pair_major_info(int* out) const;  // out[0] path taken (1 pair-major), out[1] pairs, out[2] chunks
+  // VertexSim3Expmap::_fix_scale of every Sim3 vertex: oplus zeroes update[6], EdgeSim3's Jacobians lose column 6
+  int set_sim3_fix_scale(int on);
   // [delta, lastStep, lastNumTries, currentLambda, wasPDInAllIterations] after the last dogleg iteration
   void dogleg_state(double* out) const;
 
@@ -405,9 +408,9 @@ class Engine {
   bool ev_valid_ = false;
   DevBuf<int> d_xoff[NVT];         // per type local -> x offset or -1
   DevBuf<int> d_hidx[NVT];         // per type local -> hessian index (-1 fixed)
-  // per-vertex-side slot arenas by vertex dimension (2, 3, 6): packed upper H + b, one slot per (edge, side)
-  DevBuf<double> dslot[7];
-  long long nslot[7] = {0, 0, 0, 0, 0, 0, 0};
+  // per-vertex-side slot arenas by vertex dimension (2, 3, 6, 7): packed upper H + b, one slot per (edge, side)
+  DevBuf<double> dslot[8];
+  long long nslot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double* slot_arena(int dim) { return dslot[dim].get(); }
   // off-diagonal blocks several local edges share: per-edge slots reduced in edge order, one launch per block size
   DevBuf<double> doffslot;
@@ -422,6 +425,7 @@ class Engine {
   // one rank (unary priors may be present and keep k_linearize_unary). The group's edges are sorted by vertex pair and
   // cut into chunks of <= 64; pm_force_slot (g2ohip_set_pair_major(g, 0)) keeps such a graph on the slot path
   bool pair_major = false, pm_force_slot = false;
+  bool sim3_fix_scale_ = false;
   int pm_nchunks = 0, pm_npairs = 0;
   DevBuf<int4> pm_chunks;      // (first edge, edges, pair, bit 0: both ends free)
   DevBuf<int2> pm_range;       // per pair its chunk range

@@ -309,6 +309,174 @@ __global__ void __launch_bounds__(256)
   wave_copy_out(slot0 + (size_t)ebase * SA, sw, nw * SA, lane);
 }
 
+// EdgeSim3 (FamilySim3, D = DA = DB = 7): constructQuadraticForm without either 7 x 7 Jacobian. With E = C S0 S1^-1,
+// e = log E and M = d log(exp(d) E) / d d the Jacobians are Ji = M Ad(C), Jj = -M Ad(E), so with K = M^T Omega M (packed
+// upper 28) and g = -M^T Omega e (both with Omega scaled by rho' under a robust kernel)
+//   H00 = Ad(C)^T K Ad(C),  H11 = Ad(E)^T K Ad(E),  H01 = -Ad(C)^T K Ad(E),  b0 = Ad(C)^T g,  b1 = -Ad(E)^T g,
+// formed column by column: x = K (Ad e_j), then Ad^T x; the adjoints are applied from (R, t, s), M from its four
+// blocks. One lane per edge; live per lane: K 28, g 7, (R, t, s) of C and of E 26 doubles. fix_scale (EdgeData::ue bit 3)
+// zeroes row and column 6 of every block and entry 6 of b0 and b1.
+// Slot contract of k_linearize: the same slot layout (packed upper 28 + 7), off_dst / off_tr / shared-block slots, wave
+// staged coalesced stores, a fixed summation order. The LDS image holds 35 doubles per lane (70 KB per workgroup, under
+// k_linearize's 72 KB at D = 6), so the 49-double off-diagonal block goes out in two passes of 32 lanes.
+__global__ void __launch_bounds__(256)
+    k_linearize_sim3(EdgeData d, int ne, const int* __restrict__ h0, const int* __restrict__ h1,
+                     double* __restrict__ slot0, double* __restrict__ slot1, const long long* __restrict__ off_dst,
+                     const unsigned char* __restrict__ off_tr, double* __restrict__ off_base,
+                     double* __restrict__ off_slot) {
+  constexpr int SA = 35, SH = 49;
+  __shared__ __attribute__((aligned(16))) double stage[4][64 * SA];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int e = blockIdx.x * blockDim.x + tid;
+  const int ebase = e - lane, nw = min(64, ne - ebase);  // the wave's edges [ebase, ebase + nw)
+  if (nw <= 0) return;                                  // wave-uniform
+  double* sw = stage[tid >> 6];
+  const bool in = e < ne;
+  const bool nfA = in && h0[d.v0[e]] >= 0, nfB = in && h1[d.v1[e]] >= 0;
+  const bool fs = (d.ue & 8) != 0;
+  double K[28], g[7], RC[9], tC[3], sC = 1, RE[9], tE[3], sE = 1;
+  if (nfA || nfB) {
+    double err[7];
+    Sim3LogJac L;
+    FamilySim3::error_transform<true>(d, e, RE, tE, sE, RC, tC, sC);
+    sim3_log<true>(RE, tE, sE, err, &L);
+    double Om[28];  // packed upper
+    const double* ip = info_rec(d, e, 28);
+#pragma unroll
+    for (int i = 0; i < 28; ++i) Om[i] = ip[i];
+    auto om = [&](int r, int c) { return Om[r <= c ? up_idx(r, c) : up_idx(c, r)]; };
+    double w[7];  // Omega e
+#pragma unroll
+    for (int r = 0; r < 7; ++r) {
+      double s = 0;
+#pragma unroll
+      for (int c = 0; c < 7; ++c) s += om(r, c) * err[c];
+      w[r] = s;
+    }
+    double r1 = 1;
+    if (d.rk) {  // robust branch of constructQuadraticForm (base_binary_edge.hpp:104-135)
+      double chi = 0;
+#pragma unroll
+      for (int i = 0; i < 7; ++i) chi += err[i] * w[i];
+      double r0;
+      robustify(d.rk, d.rk_delta, chi, r0, r1);
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      double cj[7], tj[7];
+      sim3_M_col(L, j, cj);
+#pragma unroll
+      for (int r = 0; r < 7; ++r) {
+        double s = 0;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) s += om(r, c) * cj[c];
+        tj[r] = s * r1;
+      }
+      double gj = 0;
+#pragma unroll
+      for (int r = 0; r < 7; ++r) gj += cj[r] * w[r];
+      g[j] = -(gj * r1);
+#pragma unroll
+      for (int i = 0; i <= j; ++i) {
+        double ci[7];
+        sim3_M_col(L, i, ci);
+        double s = 0;
+#pragma unroll
+        for (int r = 0; r < 7; ++r) s += ci[r] * tj[r];
+        K[up_idx(i, j)] = s;
+      }
+    }
+  }
+  auto kmul = [&](const double* a, double* x) {  // x = K a
+#pragma unroll
+    for (int r = 0; r < 7; ++r) {
+      double s = 0;
+#pragma unroll
+      for (int c = 0; c < 7; ++c) s += K[r <= c ? up_idx(r, c) : up_idx(c, r)] * a[c];
+      x[r] = s;
+    }
+  };
+  // side A slot (edges whose side A is fixed leave garbage in their slot: never read)
+  if (nfA) {
+    double* o = sw + lane * SA;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      double a[7], x[7], hc[7];
+      sim3_ad_col(RC, tC, sC, j, a);
+      kmul(a, x);
+      sim3_adT_apply(RC, tC, sC, x, hc);
+      const bool zc = fs && j == 6;
+#pragma unroll
+      for (int r = 0; r <= j; ++r) o[up_idx(r, j)] = (zc || (fs && r == 6)) ? 0.0 : hc[r];
+    }
+    double b0[7];
+    sim3_adT_apply(RC, tC, sC, g, b0);
+    if (fs) b0[6] = 0;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) o[28 + i] = b0[i];
+  }
+  wave_sync();
+  wave_copy_out(slot0 + (size_t)ebase * SA, sw, nw * SA, lane);
+  wave_sync();
+  // off-diagonal block, as k_linearize: staged when the wave's blocks are consecutive with one orientation, else written
+  // by the lane; bit 62: a per-edge slot of a block several edges share
+  constexpr long long SLOT_BIT = 1LL << 62;
+  const long long od_raw = (nfA && nfB) ? off_dst[e] : -1;
+  const bool in_slot = od_raw >= 0 && (od_raw & SLOT_BIT);
+  const long long od = od_raw >= 0 ? (od_raw & ~SLOT_BIT) : -1;
+  const bool tr = nfA && nfB && off_tr[e];
+  const long long od0 = __shfl(od, 0, 64);
+  const bool tr0 = __shfl((int)tr, 0, 64) != 0;
+  const bool slot0f = __shfl((int)in_slot, 0, 64) != 0;
+  const bool run = __all(!in || (od >= 0 && od0 >= 0 && od == od0 + (long long)lane * SH && tr == tr0 && in_slot == slot0f));
+  double* const obase = in_slot ? off_slot : off_base;
+  for (int pass = 0; pass < 2; ++pass) {  // lanes [32 pass, 32 pass + 32)
+    if (od >= 0 && (lane >> 5) == pass) {
+      double* H = run ? sw + (lane & 31) * SH : obase + od;
+      // column j of H10 = -Ad(E)^T K Ad(C) is row j of H01; H01(i, j) lives at j * 7 + i, transposed at i * 7 + j
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        double a[7], x[7], hc[7];
+        sim3_ad_col(RC, tC, sC, j, a);
+        kmul(a, x);
+        sim3_adT_apply(RE, tE, sE, x, hc);
+        const bool zc = fs && j == 6;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+          const double v = (zc || (fs && i == 6)) ? 0.0 : -hc[i];  // H01(j, i)
+          H[tr ? j * 7 + i : i * 7 + j] = v;
+        }
+      }
+    }
+    if (run) {
+      wave_sync();
+      const int l0 = 32 * pass, cnt = min(32, nw - l0);
+      if (cnt > 0) wave_copy_out((slot0f ? off_slot : off_base) + od0 + (long long)l0 * SH, sw, cnt * SH, lane);
+      wave_sync();
+    }
+  }
+  if (nfB) {
+    double* o = sw + lane * SA;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      double a[7], x[7], hc[7];
+      sim3_ad_col(RE, tE, sE, j, a);
+      kmul(a, x);
+      sim3_adT_apply(RE, tE, sE, x, hc);
+      const bool zc = fs && j == 6;
+#pragma unroll
+      for (int r = 0; r <= j; ++r) o[up_idx(r, j)] = (zc || (fs && r == 6)) ? 0.0 : hc[r];
+    }
+    double b1[7];
+    sim3_adT_apply(RE, tE, sE, g, b1);
+    if (fs) b1[6] = 0;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) o[28 + i] = -b1[i];
+  }
+  wave_sync();
+  wave_copy_out(slot1 + (size_t)ebase * SA, sw, nw * SA, lane);
+}
+
 // ------------------------------------------------------------------------------ vertex reduction
 // One group of LANES lanes per vertex; lane l sums slots l, l+LANES, ... in order; butterfly
 // reduction in a fixed pattern keeps the result bitwise reproducible.
@@ -1299,6 +1467,23 @@ __device__ __forceinline__ void d_oplus_cam(int v, const int* __restrict__ xoff,
   s[3] = qn[0] / n; s[4] = qn[1] / n; s[5] = qn[2] / n; s[6] = qn[3] / n;
 }
 
+// VertexSim3Expmap::oplusImpl (types_seven_dof_expmap.h:73-82): update[6] zeroed under _fix_scale, then
+// Sim3(update) * estimate; neither the constructor from a 7-vector nor operator* normalises the rotation
+__device__ __forceinline__ void d_oplus_sim3(int v, const int* __restrict__ xoff, const double* __restrict__ x,
+                                             double* __restrict__ st, int fix_scale) {
+  if (xoff[v] < 0) return;
+  const double* up = x + xoff[v];
+  const double u[7] = {up[0], up[1], up[2], up[3], up[4], up[5], fix_scale ? 0.0 : up[6]};
+  double* s = st + (size_t)v * 8;
+  double qu[4], tu[3], su, q[4], t[3], sc, qn[4], tn[3], sn;
+  sim3_exp(u, qu, tu, su);
+  sim3_load(s, q, t, sc);
+  sim3_mul(qu, tu, su, q, t, sc, qn, tn, sn);
+  s[0] = tn[0]; s[1] = tn[1]; s[2] = tn[2];
+  s[3] = qn[0]; s[4] = qn[1]; s[5] = qn[2]; s[6] = qn[3];
+  s[7] = sn;
+}
+
 // SparseOptimizer::update (sparse_optimizer.cpp:441-454) over every vertex type in one launch: block ranges per type
 __global__ void __launch_bounds__(256) k_oplus_multi(launch::OplusList L, const double* __restrict__ x) {
   int t = 0;
@@ -1312,6 +1497,7 @@ __global__ void __launch_bounds__(256) k_oplus_multi(launch::OplusList L, const 
     case 4: d_oplus_se2(v, L.xoff[t], x, L.st[t], L.nopl); break;
     case 5: d_oplus_xy(v, L.xoff[t], x, L.st[t], L.nopl); break;
     case 6: d_oplus_cam(v, L.xoff[t], x, L.st[t], L.nopl); break;
+    case 7: d_oplus_sim3(v, L.xoff[t], x, L.st[t], L.sim3_fix_scale); break;
   }
 }
 
@@ -1792,20 +1978,22 @@ static EdgeData mk(const EdgeArgs& a) {
   return EdgeData{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, a.rk, a.rk_delta, a.ue};
 }
 
-// host-Jacobian families: runtime (D, DA, DB) -> FamilyHostJ<D, DA, DB> (vertex dims 2, 3 or 6, D = 1..6)
+// host-Jacobian families: runtime (D, DA, DB) -> FamilyHostJ<D, DA, DB> (vertex dims 2, 3, 6 or 7, D = 1..7)
 template <int D, int DA, class Fn>
 static void hj_b(int DB, Fn& fn) {
   if (DB == 2) fn(FamilyHostJ<D, DA, 2>{});
   else if (DB == 3) fn(FamilyHostJ<D, DA, 3>{});
   else if (DB == 6) fn(FamilyHostJ<D, DA, 6>{});
-  else throw std::runtime_error("host-Jacobian edge: vertex dimension must be 2, 3 or 6");
+  else if (DB == 7) fn(FamilyHostJ<D, DA, 7>{});
+  else throw std::runtime_error("host-Jacobian edge: vertex dimension must be 2, 3, 6 or 7");
 }
 template <int D, class Fn>
 static void hj_a(int DA, int DB, Fn& fn) {
   if (DA == 2) hj_b<D, 2>(DB, fn);
   else if (DA == 3) hj_b<D, 3>(DB, fn);
   else if (DA == 6) hj_b<D, 6>(DB, fn);
-  else throw std::runtime_error("host-Jacobian edge: vertex dimension must be 2, 3 or 6");
+  else if (DA == 7) hj_b<D, 7>(DB, fn);
+  else throw std::runtime_error("host-Jacobian edge: vertex dimension must be 2, 3, 6 or 7");
 }
 // unary families; host-Jacobian ones: runtime (D, DA) -> FamilyHostJUnary<D, DA>
 template <int D, class Fn>
@@ -1813,7 +2001,8 @@ static void hju_a(int DA, Fn& fn) {
   if (DA == 2) fn(FamilyHostJUnary<D, 2>{});
   else if (DA == 3) fn(FamilyHostJUnary<D, 3>{});
   else if (DA == 6) fn(FamilyHostJUnary<D, 6>{});
-  else throw std::runtime_error("host-Jacobian unary edge: vertex dimension must be 2, 3 or 6");
+  else if (DA == 7) fn(FamilyHostJUnary<D, 7>{});
+  else throw std::runtime_error("host-Jacobian unary edge: vertex dimension must be 2, 3, 6 or 7");
 }
 template <class Fn>
 static void unary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
@@ -1833,7 +2022,8 @@ static void unary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
         case 4: hju_a<4>(a.DA, fn); break;
         case 5: hju_a<5>(a.DA, fn); break;
         case 6: hju_a<6>(a.DA, fn); break;
-        default: throw std::runtime_error("host-Jacobian unary edge: error dimension must be 1..6");
+        case 7: hju_a<7>(a.DA, fn); break;
+        default: throw std::runtime_error("host-Jacobian unary edge: error dimension must be 1..7");
       }
       break;
     default: throw std::runtime_error("unknown unary edge family");
@@ -1867,6 +2057,7 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_SE2XY_BEARING: fn(FamilySE2XYBearing{}); break;
     case FAM_GICP: fn(FamilyGICP{}); break;
     case FAM_VSC: fn(FamilyVSC{}); break;
+    case FAM_SIM3: fn(FamilySim3{}); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;
@@ -1875,7 +2066,8 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
         case 4: hj_a<4>(a.DA, a.DB, fn); break;
         case 5: hj_a<5>(a.DA, a.DB, fn); break;
         case 6: hj_a<6>(a.DA, a.DB, fn); break;
-        default: throw std::runtime_error("host-Jacobian edge: error dimension must be 1..6");
+        case 7: hj_a<7>(a.DA, a.DB, fn); break;
+        default: throw std::runtime_error("host-Jacobian edge: error dimension must be 1..7");
       }
       break;
     default: throw std::runtime_error("unknown edge family");
@@ -1898,8 +2090,12 @@ void linearize(int family, const EdgeArgs& a, int ne, const int* h0, const int* 
   const unsigned g = grid_for(ne, 256);
   binary_dispatch(family, a, [&](auto fam) {
     using F = decltype(fam);
-    hipLaunchKernelGGL(k_linearize<F>, g, 256, 0, s, mk(a), ne, h0, h1, slot0, slot1, off_dst, off_tr, off_base,
-                       off_slot);
+    if constexpr (std::is_same_v<F, FamilySim3>)  // never the generic kernel at D = DA = DB = 7 (k_linearize_sim3)
+      hipLaunchKernelGGL(k_linearize_sim3, g, 256, 0, s, mk(a), ne, h0, h1, slot0, slot1, off_dst, off_tr, off_base,
+                         off_slot);
+    else
+      hipLaunchKernelGGL(k_linearize<F>, g, 256, 0, s, mk(a), ne, h0, h1, slot0, slot1, off_dst, off_tr, off_base,
+                         off_slot);
   });
   KERNEL_CHECK();
 }
@@ -1927,10 +2123,14 @@ static void vreduce_dim(int nv, int lanes, const int* ptr, const int* code, cons
     case 4: hipLaunchKernelGGL((k_vertex_reduce<DIM, 4>), g, 256, 0, s, nv, ptr, code, slots, H, b, boff); break;
     case 8: hipLaunchKernelGGL((k_vertex_reduce<DIM, 8>), g, 256, 0, s, nv, ptr, code, slots, H, b, boff); break;
     case 64:
-      if (vr_wide())
-        hipLaunchKernelGGL((k_vertex_reduce_wide<DIM>), nv, 256, 0, s, nv, ptr, code, slots, H, b, boff);
-      else
-        hipLaunchKernelGGL((k_vertex_reduce<DIM, 64>), g, 256, 0, s, nv, ptr, code, slots, H, b, boff);
+      // (the wide kernel reads one slot per half-wave: dimension 7's 35 doubles do not fit and take the 64-lane one)
+      if constexpr (DIM * (DIM + 1) / 2 + DIM <= 32) {
+        if (vr_wide()) {
+          hipLaunchKernelGGL((k_vertex_reduce_wide<DIM>), nv, 256, 0, s, nv, ptr, code, slots, H, b, boff);
+          break;
+        }
+      }
+      hipLaunchKernelGGL((k_vertex_reduce<DIM, 64>), g, 256, 0, s, nv, ptr, code, slots, H, b, boff);
       break;
     default: hipLaunchKernelGGL((k_vertex_reduce<DIM, 256>), g, 256, 0, s, nv, ptr, code, slots, H, b, boff); break;
   }
@@ -1943,6 +2143,7 @@ void vertex_reduce(int dim, int nv, int lanes, const int* ptr, const int* code, 
   if (dim == 2) vreduce_dim<2>(nv, lanes, ptr, code, slots, H, b, boff, s);
   else if (dim == 3) vreduce_dim<3>(nv, lanes, ptr, code, slots, H, b, boff, s);
   else if (dim == 6) vreduce_dim<6>(nv, lanes, ptr, code, slots, H, b, boff, s);
+  else if (dim == 7) vreduce_dim<7>(nv, lanes, ptr, code, slots, H, b, boff, s);
   else throw std::runtime_error("vertex_reduce: unsupported dim");
 }
 
@@ -2140,7 +2341,8 @@ void block_symv(int pd, int n, const int* rptr, const int2* ent, const int* diag
   const unsigned g = grid_for(n, 256);
   if (pd == 6) hipLaunchKernelGGL(k_block_symv<6>, g, 256, 0, s, n, rptr, ent, diag, vals, lam, x, y, b, r2, b2);
   else if (pd == 3) hipLaunchKernelGGL(k_block_symv<3>, g, 256, 0, s, n, rptr, ent, diag, vals, lam, x, y, b, r2, b2);
-  else throw std::runtime_error("block_symv: block dimension must be 3 or 6");
+  else if (pd == 7) hipLaunchKernelGGL(k_block_symv<7>, g, 256, 0, s, n, rptr, ent, diag, vals, lam, x, y, b, r2, b2);
+  else throw std::runtime_error("block_symv: block dimension must be 3, 6 or 7");
   KERNEL_CHECK();
 }
 void scale_terms(long long n, const double* x, const double* b, const double* lam, double* out, hipStream_t s) {
@@ -2161,7 +2363,10 @@ static void dl_symv_dots(const DoglegSymv& H, long long n, const double* v, cons
   else if (H.pd == 3)
     hipLaunchKernelGGL(k_dl_symv_dots<3>, nsb + nps, RED_BLOCK, 0, s, H.npose, n, nsb, nps, H.rptr, H.ent, H.diag,
                        H.vals, v, w, partial);
-  else throw std::runtime_error("dogleg: block dimension must be 3 or 6");
+  else if (H.pd == 7)
+    hipLaunchKernelGGL(k_dl_symv_dots<7>, nsb + nps, RED_BLOCK, 0, s, H.npose, n, nsb, nps, H.rptr, H.ent, H.diag,
+                       H.vals, v, w, partial);
+  else throw std::runtime_error("dogleg: block dimension must be 3, 6 or 7");
   KERNEL_CHECK();
 }
 void dl_alpha(const DoglegSymv& H, long long n, const double* b, double* partial, double* p, hipStream_t s) {

@@ -27,7 +27,9 @@ enum Family {
   // Edge_V_V_GICP between two VertexSE3 (types_icp): FamilyGICP, point-to-plane or plane-to-plane per edge set
   FAM_GICP = 25,
   // Edge_XYZ_VSC (point, VertexSCam = a VertexSE3 camera): FamilyVSC, the landmark first as in the BA families
-  FAM_VSC = 26
+  FAM_VSC = 26,
+  // EdgeSim3 between two VertexSim3Expmap (types/sim3): FamilySim3, linearized by k_linearize_sim3
+  FAM_SIM3 = 27
 };
 // the fused landmark-major assembly's families (point, VertexSE3Expmap camera)
 inline bool is_ba_family(int f) { return f == FAM_BA || f == FAM_BA_STEREO || f == FAM_BA_UVU; }
@@ -51,7 +53,8 @@ struct EdgeArgs {
   int rk = 0;          // robust kernel (G2OHIP_RK_*), uniform over the edge group
   double rk_delta = 1.0;
   int D = 0, DA = 0, DB = 0;  // host-J family dimensions
-  int ue = 0;                 // uniform records (EdgeData::ue): bit 0 information, bit 1 intrinsics; bit 2 GICP plane-to-plane
+  int ue = 0;                 // uniform records (EdgeData::ue): bit 0 information, bit 1 intrinsics; bit 2 GICP plane-to-plane;
+                              // bit 3: the Sim3 vertices' _fix_scale (FamilySim3)
 };
 
 namespace launch {
@@ -177,13 +180,15 @@ void backsub(int pd, int ld, int nl, const int* lm_ptr, const int* blk_pose, con
 // back-substitution from the G blocks of an assembly-time Schur split: x_l = U^-T (c_l - G^T x_p)
 void backsub_g(int pd, int ld, int nl, const int* lm_ptr, const int* blk_pose, const double* G, const double* Ufac,
                const double* cl_all, int size_poses, int lm0, double* x, hipStream_t s);
-// vertex oplus of every type in one launch: per type (vertex type id 1..5, count, x offsets, states)
+// vertex oplus of up to five types in one launch: per type (vertex type id G2OHIP_V_*, count, x offsets, states); a
+// graph holding more types takes a second launch (Engine::update_async)
 struct OplusList {
   int cnt = 0;
   int vt[5], n[5], blk0[5];
   const int* xoff[5];
   double* st[5];
   int* nopl = nullptr;
+  int sim3_fix_scale = 0;  // VertexSim3Expmap::_fix_scale: oplus zeroes update[6]
 };
 void oplus_multi(const OplusList& L, const double* x, hipStream_t s);
 size_t sum_partials(long long n);

@@ -34,6 +34,8 @@ Recipes:
     correspondences between VERTEX_SE3:QUAT scans, point-to-plane or plane-to-plane; Edge_XYZ_VSC stereo
     observations of marginalised points): the scenes of gicp_demo.cpp and gicp_sba_demo.cpp, and a ring of scans
     with many correspondences per scan pair.
+  * ``sim3_pose_graph`` - a 7-DoF pose graph in the types/sim3 vocabulary (VERTEX_SIM3:EXPMAP keyframes joined by
+    EDGE_SIM3:EXPMAP odometry and loop closures), the shape of a monocular essential graph with scale drift.
 """
 from __future__ import annotations
 
@@ -71,19 +73,23 @@ E_PROJECT_XYZ2UV, E_PROJECT_XYZ2UVU = 23, 24
 # cov0 | cov1 packed upper = plane-to-plane), Edge_XYZ_VSC from a V_XYZ point to a V_SE3_QUAT camera (params fx fy cx
 # cy baseline)
 E_V_V_GICP, E_XYZ_VSC = 25, 26
-EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12}
+# types/sim3: VertexSim3Expmap, estimate tx ty tz qx qy qz qw s (world->camera); EdgeSim3 between two of them, meas a
+# Sim3 in the same layout, info 7x7 in (omega, upsilon, sigma) order
+V_SIM3 = 7
+E_SIM3 = 27
+EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12, V_SIM3: 8}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
             E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
             E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
             E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 7, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
-            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 12, E_XYZ_VSC: 3}
+            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 12, E_XYZ_VSC: 3, E_SIM3: 8}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
            E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 6, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
-           E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 3, E_XYZ_VSC: 3}
+           E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 3, E_XYZ_VSC: 3, E_SIM3: 7}
 # parameter values per edge of the types that take a record (EdgeSet.params; where None is allowed it is the identity)
 PARAM_DIM = {E_SE3_PROJECT_XYZ: 4, E_STEREO_SE3_PROJECT_XYZ: 5, E_SE3_PRIOR: 7, E_SE3_XYZ: 7, E_SE3_XYZ_DEPTH: 11,
              E_SE3_XYZ_DISPARITY: 11, E_SE3_PROJECT_XYZ_ONLYPOSE: 7, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 8,
@@ -1343,4 +1349,68 @@ def icp_twin(prob: Problem) -> Problem:
             edges.append(EdgeSet(32 + 3, es.v0.copy(), es.v1.copy(), None, info, None))
         else:
             edges.append(es)
+    return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)
+
+
+# ---------------------------------------------------------------- Sim3 pose graphs
+def _sim3_mul(a, b):
+    """(R, t, s) * (R, t, s) of similarity transforms x -> s R x + t, batched."""
+    (Ra, ta, sa), (Rb, tb, sb) = a, b
+    return Ra @ Rb, sa[:, None] * np.einsum("nij,nj->ni", Ra, tb) + ta, sa * sb
+
+
+def _sim3_inv(a):
+    R, t, s = a
+    Rt = np.transpose(R, (0, 2, 1))
+    return Rt, -np.einsum("nij,nj->ni", Rt, t) / s[:, None], 1.0 / s
+
+
+def _sim3_vec(a):
+    R, t, s = a
+    return np.concatenate([t, rot_to_quat(R), s[:, None]], axis=1)
+
+
+def sim3_pose_graph(num_poses: int = 40, loops: int = 80, rot_noise: float = 0.02, trans_noise: float = 0.03,
+                    scale_noise: float = 0.02, drift: float = 0.03, seed: int = SEED) -> Problem:
+    """A 7-DoF pose graph (VertexSim3Expmap keyframes, EdgeSim3): ``num_poses`` world->camera similarities on a ring
+    of radius 5, the camera looking along the direction of travel, whose scale drifts as a monocular map's does: log
+    s_i is a random walk of step ``drift``.  Odometry (i, i + 1) and ``loops`` closures (i, j), j > i + 1.  With the
+    edge's error log(C Si Sj^-1) the measurement is C = N Sj Si^-1 of the true keyframes, N a random similarity of
+    rotation angle ~ ``rot_noise``, translation ~ ``trans_noise`` and log scale +-(1 .. 2) ``scale_noise``: at the
+    true keyframes an edge's error is log N.  Information: sigma^-1 (I + A)(I + A)^T sigma^-1 in (omega, upsilon,
+    sigma) order, A random per edge: SPD, not diagonal.  Keyframe 0 is fixed; the others start at the truth moved by a
+    similarity of 0.03 rad, 0.05 and 3 % of scale, so that every edge's rotation error stays far below 2 rad."""
+    n = num_poses
+    rng = _rng(seed, 80)
+    th = 2 * math.pi * np.arange(n) / max(n, 8)
+    pos = np.stack([5 * np.cos(th), 5 * np.sin(th), 0.05 * np.arange(n)], 1)
+    zero, one = np.zeros(n), np.ones(n)
+    Rc = np.stack([np.stack([np.cos(th), zero, -np.sin(th)], 1), np.stack([np.sin(th), zero, np.cos(th)], 1),
+                   np.stack([zero, -one, zero], 1)], 1) @ _small_rot(rng, n, 0.1)
+    s = np.exp(np.cumsum(np.concatenate([[0.0], rng.standard_normal(n - 1) * drift])))
+    Rw = np.transpose(Rc, (0, 2, 1))
+    truth = (Rw, -s[:, None] * np.einsum("nij,nj->ni", Rw, pos), s)
+    a, b = _loop_pairs(rng, n, loops)
+    m = len(a)
+    sel = lambda S, k: (S[0][k], S[1][k], S[2][k])  # noqa: E731
+    sn = np.exp(rng.choice([-1.0, 1.0], m) * scale_noise * (1.0 + rng.random(m)))
+    noise = (_small_rot(rng, m, rot_noise), rng.standard_normal((m, 3)) * trans_noise, sn)
+    meas = _sim3_vec(_sim3_mul(noise, _sim3_mul(sel(truth, b), _sim3_inv(sel(truth, a)))))
+    info = _spd_info(rng, m, np.array([rot_noise] * 3 + [trans_noise] * 3 + [scale_noise]))
+    move = (_small_rot(rng, n, 0.03), rng.standard_normal((n, 3)) * 0.05, np.exp(rng.standard_normal(n) * 0.03))
+    est = _sim3_vec(_sim3_mul(move, truth))
+    est[0] = _sim3_vec(truth)[0]
+    fixed = np.zeros(n, np.int32)
+    fixed[0] = 1
+    ids = np.arange(n, dtype=np.int32)
+    verts = VertexSet(V_SIM3, ids, est, fixed, np.zeros(n, np.int32))
+    edges = EdgeSet(E_SIM3, ids[a].copy(), ids[b].copy(), meas, info)
+    return Problem(f"sim3_{n}l{loops}", [verts], [edges], 7, 0)
+
+
+def sim3_twin(prob: Problem) -> Problem:
+    """The host-Jacobian twin of a Sim3 graph: every E_SIM3 set as an E_HOSTJ(7) set (39) between the same vertices
+    with the same information; the caller supplies the payload."""
+    edges = [EdgeSet(32 + 7, es.v0.copy(), es.v1.copy(), None, es.info.copy(), None) if es.etype == E_SIM3 else es
+             for es in prob.edges]
     return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)

@@ -11,7 +11,7 @@
  *        + SparseOptimizer::optimize (core/sparse_optimizer.cpp:374-439) ... g2ohip_optimize
  *   OptimizableGraph::load / save (core/optimizable_graph.cpp:397-679) .. g2ohip_load_g2o / g2ohip_save_g2o
  *   OptimizationAlgorithmFactory::construct (core/optimization_algorithm_factory.cpp:84-93)
- *        .. g2ohip_set_algorithm("lm_hip_fix6_3" | "lm_hip_fix3_3" | "lm_hip_fix6_6" | "lm_hip_var" | "gn_hip_*"
+ *        .. g2ohip_set_algorithm("lm_hip_fix6_3" | "lm_hip_fix3_3" | "lm_hip_fix6_6" | "lm_hip_fix7_3" | "lm_hip_var" | "gn_hip_*"
  *           | "dl_hip_*" (Powell's dogleg, core/optimization_algorithm_dogleg.cpp:57-208; the same suffixes)
  *           | "structure_only_3" | "structure_only_2" (StructureOnlySolver<PointDoF>, solvers/structure_only/
  *             structure_only.cpp:64-65, structure_only_solver.h:60-229; g2ohip_structure_only_calc is its calc())
@@ -46,6 +46,14 @@ extern "C" {
                                  q = q * (u[3:6], sqrt(1 - |u[3:6]|^2)), normalised; no sign flip of w, no identity
                                  fallback: for |u[3:6]|^2 > 1 the square root and with it the rotation are NaN, as in
                                  the reference (the LM / GN / dogleg decisions reject the non-finite chi2) */
+#define G2OHIP_V_SIM3 7       /* VertexSim3Expmap, types_seven_dof_expmap.h:61-105, dimension 7. The estimate is a Sim3,
+                                 8 doubles: tx ty tz qx qy qz qw s (world->camera, as G2OHIP_V_SE3_EXPMAP; x -> s R x + t).
+                                 On entry q is normalised to unit length with w >= 0 (Sim3::normalizeRotation); the device
+                                 state is one 64-byte line per vertex. g2ohip_minimal_state gives Sim3::log() in the
+                                 reference's order (omega, upsilon, sigma). oplus is Sim3(update) * estimate
+                                 (sim3.h:66-135, 255-261) with all four branches of the exponential, and nothing is
+                                 normalised afterwards: neither the 7-vector constructor nor operator* does in the
+                                 reference. See g2ohip_set_sim3_fix_scale */
 /* ---- edge types ---- */
 #define G2OHIP_E_SE3_PROJECT_XYZ 1 /* EdgeSE3ProjectXYZ, types_six_dof_expmap.h:201-229: v0 point, v1 camera;
                                       meas u v; info 2x2; params fx fy cx cy */
@@ -115,11 +123,11 @@ extern "C" {
                                       marginalised landmarks it runs on the 3/2 Schur path, in structure_only_2 and
                                       on landmark shards, as G2OHIP_E_SE2_XY does */
 /* An edge type the device does not know (any BaseBinaryEdge<D, E, Vi, Vj> between registered vertices of
- * dimension 2, 3 or 6): the host's own linearizeOplus (the type's analytic one, or BaseBinaryEdge's numeric
+ * dimension 2, 3, 6 or 7): the host's own linearizeOplus (the type's analytic one, or BaseBinaryEdge's numeric
  * central differences, base_binary_edge.hpp:198-266) supplies the error and both Jacobians, see
  * g2ohip_set_host_jacobians; the device assembles, marginalises and solves. meas unused (may be NULL);
  * info D*D. Several host-J types (different D) may coexist with the device types in one graph. */
-#define G2OHIP_E_HOSTJ(D) (32 + (D)) /* D = error dimension, 1..6 */
+#define G2OHIP_E_HOSTJ(D) (32 + (D)) /* D = error dimension, 1..7 */
 /* ---- unary edge types (BaseUnaryEdge, core/base_unary_edge.hpp:49-78): one vertex, v0; g2ohip_add_edges takes them
  * with v1 == NULL (a non-NULL v1 is G2OHIP_ERR_ARG, as a NULL v1 is for the binary types). A unary edge on a fixed
  * vertex is inactive (sparse_optimizer.cpp:241, allVerticesFixed): it adds nothing to chi2, H or b. A vertex whose
@@ -190,10 +198,26 @@ extern "C" {
                                 marginalised points the 6/3 Schur kernels, structure_only_3 and landmark shards, as
                                 the other 6/3 projections. No .g2o file carries it (the reference's read / write
                                 return false): g2ohip_save_g2o refuses a graph that holds it */
-/* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3 or 6 (an edge type of the application's own, say): the
+/* ---- types/sim3 (types_seven_dof_expmap.h): 7-DoF pose graphs, the vocabulary of monocular loop closing. A graph of
+ * Sim3 poses is BlockSolver_7_3 without marginalised vertices: {lm,gn,dl}_hip_fix7_3 or *_hip_var. A free marginalised
+ * point beside Sim3 poses is refused by the structure build (G2OHIP_ERR_UNSUPPORTED: the 7/3 Schur kernels do not
+ * exist), a free non-marginalised one by the one-pose-block-size rule; lm_pcg*, gn_pcg* and lm_pcg6_3_eigen refuse a
+ * Sim3 graph (pose blocks of 3 or 6 only). EdgeSim3ProjectXYZ and EdgeInverseSim3ProjectXYZ, numerically differentiated
+ * in the reference, enter as G2OHIP_E_HOSTJ(2) between a fixed G2OHIP_V_XYZ point and a Sim3 vertex (ORB-SLAM's
+ * OptimizeSim3, where the points are fixed). ---- */
+#define G2OHIP_E_SIM3 27 /* EdgeSim3 (EDGE_SIM3:EXPMAP), types_seven_dof_expmap.h:110-137: v0, v1 both G2OHIP_V_SIM3; meas
+                            the Sim3 C, 8 doubles in the vertex layout, normalised on entry as a vertex estimate is; info
+                            7x7 in (omega, upsilon, sigma) order; params must be NULL (non-NULL is G2OHIP_ERR_ARG).
+                            error = log(C * S0 * S1^-1) with all four branches of Sim3::log (sim3.h:141-220) as written.
+                            The reference has no linearizeOplus for this edge and differentiates numerically; the device
+                            uses the exact first derivatives of that closed-form log under the vertex's oplus:
+                            Ji = M Ad(C), Jj = -M Ad(E), E = C S0 S1^-1, M = d log(exp(d) E) / d d. No isDepthPositive
+                            (depth_positive != NULL or check_depth is G2OHIP_ERR_ARG); robust kernels, edge levels,
+                            g2ohip_edge_chi2 and g2ohip_classify_edges take it like any device type */
+/* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3, 6 or 7 (an edge type of the application's own, say): the
  * host supplies the error and the Jacobian as for G2OHIP_E_HOSTJ, payload [e (D) | Ji (D x dim(v0))] row-major per
  * edge. meas unused (may be NULL); info D*D. */
-#define G2OHIP_E_HOSTJ_UNARY(D) (48 + (D)) /* D = error dimension, 1..6 */
+#define G2OHIP_E_HOSTJ_UNARY(D) (48 + (D)) /* D = error dimension, 1..7 */
 
 /* robust kernels (robust_kernel_impl.cpp; RobustKernelFactory names) */
 #define G2OHIP_RK_NONE 0
@@ -317,6 +341,16 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * load with G2OHIP_ERR_ARG (g2ohip_last_error names the line number) and nothing of it is stored. An endpoint that is
  * missing or no VERTEX_SE3:QUAT and a short line fail the load too. Without the flag the tag is skipped. */
 #define G2OHIP_LOAD_ICP 64u
+/* G2OHIP_LOAD_SIM3 (may be combined with the other flags): VERTEX_SIM3:EXPMAP id v0..v6 fx fy cx cy loads as
+ * G2OHIP_V_SIM3: the seven values are the log of cam2world and the estimate is Sim3(v).inverse()
+ * (types_seven_dof_expmap.cpp:66-87); the four intrinsics (_focal_length1, _principle_point1) stay on the host for
+ * g2ohip_save_g2o. A line with exactly 7 values takes the constructor's defaults 1 1 0 0; any other length fails the
+ * load, g2ohip_last_error naming the tag. EDGE_SIM3:EXPMAP v0 v1 m0..m6 and the 28 upper-triangle information values
+ * loads as G2OHIP_E_SIM3 with the measurement Sim3(m).inverse() (:104-122); a short line or an endpoint that is no
+ * VERTEX_SIM3:EXPMAP fails the load. Without the flag both tags are skipped like any unknown one. EDGE_PROJECT_SIM3_XYZ:EXPMAP
+ * and EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP are always skipped: their lines carry no intrinsics. g2ohip_save_g2o writes both
+ * tags the reference's way (:89-102, 124-137): the log of the inverse, the intrinsics, the upper triangle. */
+#define G2OHIP_LOAD_SIM3 128u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
@@ -388,6 +422,13 @@ int g2ohip_set_algorithm(g2ohip_graph* g, const char* name);
  * comparisons), 1 (the default) takes the pair-major path where it applies. Takes effect at the next structure build.
  * g2ohip_pair_major_info: out[0] = 1 when the built structure is pair-major, out[1] its pairs, out[2] its chunks. */
 int g2ohip_set_pair_major(g2ohip_graph* g, int enable);
+/* VertexSim3Expmap::_fix_scale (types_seven_dof_expmap.h:77-78, 101), for every G2OHIP_V_SIM3 vertex of the handle: on = 1
+ * makes oplus zero update[6], so the scale of no vertex moves. The reference differentiates EdgeSim3 numerically
+ * through oplusImpl, so under _fix_scale column 6 of both of its Jacobians is zero; the device zeroes that column too.
+ * H(6, 6) of every vertex block then holds lambda alone: Levenberg-Marquardt works, Gauss-Newton and the undamped
+ * dogleg solve on such a graph are not positive definite. That is the reference's behaviour. Host-Jacobian edges on Sim3
+ * vertices must supply such Jacobians themselves. on other than 0 or 1: G2OHIP_ERR_ARG. */
+int g2ohip_set_sim3_fix_scale(g2ohip_graph* g, int on);
 int g2ohip_pair_major_info(g2ohip_graph* g, int out[3]);
 int g2ohip_set_dogleg_params(g2ohip_graph* g, double initial_delta, int max_trials_after_failure,
                              double initial_lambda, double lambda_factor);
