@@ -726,6 +726,7 @@ class SparseOptimizer:
         _check(lib().g2ohip_solver_set_eta(self.h, float(eta)), "set_eta")
 
     def linear_iterations(self) -> int:
+        """Iterations of the last iterative linear solve (the CGLS under lm_pcg6_3_eigen, else the block-Jacobi PCG)."""
         return int(lib().g2ohip_solver_linear_iterations(self.h))
 
     def diag_absmax(self) -> float:

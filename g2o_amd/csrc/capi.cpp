@@ -185,7 +185,7 @@ int g2ohip_solver_set_eta(g2ohip_graph* g, double eta) {
   g->e->cgls.eta = eta;
   return G2OHIP_OK;
 }
-int g2ohip_solver_linear_iterations(g2ohip_graph* g) { return g ? g->e->cgls.last_iterations : G2OHIP_ERR_ARG; }
+int g2ohip_solver_linear_iterations(g2ohip_graph* g) { return g ? g->e->linear_iterations() : G2OHIP_ERR_ARG; }
 int g2ohip_solver_diag_absmax(g2ohip_graph* g, double* out) {
   if (!g || !out) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->diag_absmax(out); });

@@ -3022,7 +3022,8 @@ void Engine::setup_edges_device() {
       std::vector<char> seen(local_lm.size(), 0);
       for (int k = 0; k < g.ne; ++k) {
         const int h = hidx[es.ev0[g.edges[k]]];
-        if (h < num_poses) continue;
+        // a fixed landmark (hidx -1): its edges sort before every free landmark's, so the prefix sum starts past them
+        if (h < num_poses) { lm_eptr_h[0]++; continue; }
         const int l = h - num_poses - lm_b;
         lm_eptr_h[l + 1]++;
         if (!seen[l]) { seen[l] = 1; erng[l].x = k; }

@@ -497,6 +497,8 @@ class Engine {
   bool use_pcg() const { return algorithm.find("_pcg") != std::string::npos && !use_cgls(); }
  public:
   DeviceCGLS cgls;  // lm_pcg6_3_eigen: the fork's matrix-free CGLS (JacobiSolver_6_3 + LinearSolverPCGEigen)
+  // iterations of the last iterative linear solve: the block-Jacobi PCG's under *_pcg*, else the CGLS's
+  int linear_iterations() const { return use_pcg() ? pcg.last_iterations : cgls.last_iterations; }
  private:
   // scalars: [0] lambda, [1] chi2, [2] scale, [3] maxdiag
   DevBuf<double> dscal;

@@ -552,7 +552,8 @@ int g2ohip_solver_diag_absmax(g2ohip_graph* g, double* out);
 /* Solver::setEta (core/solver.h:137, jacobi_solver.h:142): forcing term of the lm_pcg6_3_eigen CGLS (stop when
  * s.s < eta s0.s0, linear_solver_pcg_eigen.h:170-176); default 0.1 (core/linear_solver.h:66). */
 int g2ohip_solver_set_eta(g2ohip_graph* g, double eta);
-/* G2OBatchStatistics::iterationsLinearSolver of the last lm_pcg6_3_eigen solve */
+/* G2OBatchStatistics::iterationsLinearSolver of the last iterative linear solve: the CGLS's under lm_pcg6_3_eigen,
+ * the block-Jacobi PCG's under the other *_pcg* algorithms */
 int g2ohip_solver_linear_iterations(g2ohip_graph* g);
 /* ||(A + lambda I) x - b|| / ||b|| of the last Solver::solve, evaluated on the device (A = the Schur complement
  * with Schur, else Hpp): a size-independent check of the factorization at any problem size. With landmark shards

@@ -2,7 +2,8 @@
 solver "lm_pcg6_3_eigen" (solvers/eigen/solver_eigen.cpp:80,126):
 
 * JacobiSolver<6,3>::buildSystem (core/jacobi_solver.hpp:479-700): J with two rows per observation scaled by
-  sqrt(Omega(0,0)), columns [cameras (6 each) | points (3 each)] in Hessian order, one identity row per unknown
+  sqrt(Omega(0,0)), columns [cameras (6 each) | points (3 each)] in Hessian order (none for a fixed camera or a fixed
+  point: `columns`), one identity row per unknown
   below it scaled by sqrt(lambda) (setLambda, :703-718); b = -sum J^T Omega e (copyB).
 * LinearSolverPCGEigen::solve (solvers/eigen/linear_solver_pcg_eigen.h:70-248) with computeRc_inverse /
   computeRp_inverse (:378-517): R_b from the Householder QR of each camera's / point's column block of J (lambda rows
@@ -38,8 +39,44 @@ def jacobian(payload, cam_col, pt_col, sqrt_info, ncam, npt):
     return J
 
 
-def cgls_solve(J, b, ncam, npt, sqrt_lam, eta=0.1):
-    """LinearSolverPCGEigen::solve. J: dense (2 ne + n) x n with the lambda rows still zero. Returns (x, iterations)."""
+def columns(prob):
+    """Hessian columns of a pure BA problem (cameras | points, each by ascending id; fixed vertices have none).
+    Returns (cam_col, pt_col, ncam, npt): per edge the camera / point block index or -1, and the block counts."""
+    cams, pts = prob.vertices
+    e = prob.edges[0]
+    cam_idx = {int(i): k for k, i in enumerate(np.sort(cams.ids[cams.fixed == 0]))}
+    pt_idx = {int(i): k for k, i in enumerate(np.sort(pts.ids[pts.fixed == 0]))}
+    cam_col = np.array([cam_idx.get(int(c), -1) for c in e.v1])
+    pt_col = np.array([pt_idx.get(int(p), -1) for p in e.v0])
+    return cam_col, pt_col, len(cam_idx), len(pt_idx)
+
+
+def linear_system(host, prob, cols=None):
+    """JacobiSolver<6,3>::buildSystem at the estimates of `host` (an oracle graph of `prob`): J with its lambda rows
+    still zero, scaled by sqrt(Omega(0,0)), and b = -sum J^T Omega e with the full information (copyB).
+    Returns (J, b, ncam, npt)."""
+    cam_col, pt_col, ncam, npt = cols if cols is not None else columns(prob)
+    e = prob.edges[0]
+    ne = len(e.v0)
+    pay = host.edge_payload(np.arange(ne), 20 * ne, numeric=False)
+    J = jacobian(pay, cam_col, pt_col, np.sqrt(e.info[:, 0, 0]), ncam, npt)
+    P = pay.reshape(-1, 20)
+    b = np.zeros(6 * ncam + 3 * npt)
+    for k in range(ne):
+        om = e.info[k] @ P[k, :2]
+        if pt_col[k] >= 0:
+            o = 6 * ncam + 3 * pt_col[k]
+            b[o:o + 3] -= P[k, 2:8].reshape(2, 3).T @ om
+        if cam_col[k] >= 0:
+            o = 6 * cam_col[k]
+            b[o:o + 6] -= P[k, 8:20].reshape(2, 6).T @ om
+    return J, b, ncam, npt
+
+
+def cgls_solve(J, b, ncam, npt, sqrt_lam, eta=0.1, gammas=None):
+    """LinearSolverPCGEigen::solve. J: dense (2 ne + n) x n with the lambda rows still zero. Returns (x, iterations).
+    `gammas`, a list, receives eta * gamma_0 and then the gamma of every stop test (the last one is the one that
+    stopped the loop, unless the iteration limit did)."""
     n = J.shape[1]
     rows = J.shape[0] - n
     J = J.copy()
@@ -77,7 +114,11 @@ def cgls_solve(J, b, ncam, npt, sqrt_lam, eta=0.1):
     gamma_old = gamma
     thr = eta * float(s @ s)
     it = 0
+    if gammas is not None:
+        gammas.append(thr)
     while it < maxit:
+        if gammas is not None:
+            gammas.append(gamma)
         if gamma < thr:
             break
         even = it % 2 == 0
@@ -105,33 +146,12 @@ def cgls_solve(J, b, ncam, npt, sqrt_lam, eta=0.1):
 def jacobi_lm(host, prob, iterations, eta=0.1, max_trials=10):
     """OptimizationAlgorithmLevenberg + JacobiSolver_6_3 + LinearSolverPCGEigen on a pure BA problem; host is an
     oracle graph of `prob` (errors, Jacobians, update, push/pop). Returns [(chi2, trials, lambda, cg_iters)]."""
-    cams, pts = prob.vertices
-    e = prob.edges[0]
-    free = cams.fixed == 0
-    cam_idx = {int(i): k for k, i in enumerate(np.sort(cams.ids[free]))}
-    pt_idx = {int(i): k for k, i in enumerate(np.sort(pts.ids))}
-    ncam, npt = len(cam_idx), len(pt_idx)
-    cam_col = np.array([cam_idx.get(int(c), -1) for c in e.v1])
-    pt_col = np.array([pt_idx.get(int(p), -1) for p in e.v0])
-    sqrt_info = np.sqrt(e.info[:, 0, 0])
-    idx = np.arange(len(e.v0))
-    n = 6 * ncam + 3 * npt
+    cols = columns(prob)  # fixed cameras and fixed points have no column
     stats = []
     lam, ni = None, 2.0
     for it in range(iterations):
         current = host.chi2()
-        pay = host.edge_payload(idx, 20 * len(idx), numeric=False)
-        J = jacobian(pay, cam_col, pt_col, sqrt_info, ncam, npt)
-        P = pay.reshape(-1, 20)
-        b = np.zeros(n)  # copyB: b = -sum J^T Omega e with the full information
-        for k in range(len(idx)):
-            om = e.info[k] @ P[k, :2]
-            if pt_col[k] >= 0:
-                o = 6 * ncam + 3 * pt_col[k]
-                b[o:o + 3] -= P[k, 2:8].reshape(2, 3).T @ om
-            if cam_col[k] >= 0:
-                o = 6 * cam_col[k]
-                b[o:o + 6] -= P[k, 8:20].reshape(2, 6).T @ om
+        J, b, ncam, npt = linear_system(host, prob, cols)
         if it == 0:
             lam = 1e-5 * float(np.max(np.abs(np.einsum("ij,ij->j", J, J))))
             ni = 2.0

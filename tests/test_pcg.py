@@ -5,6 +5,10 @@ absolute residual. GPU: the device PCG behind the `lm_pcg*` algorithms against t
 reduced system the engine stages. Tolerance: both sides run the same recurrence in a different
 summation order, stopping at a relative preconditioned residual of 1e-6, so the iterates agree to
 1e-5 relative (not bitwise); both are equally inexact against the direct solution.
+
+The small end (test_gpu_pcg_small_systems, test_gpu_pcg_carried_residual_between_solves): pose graphs of 1 to 5 free
+blocks, n = 3 to 30, where the iteration limit n is below one captured chunk of the device loop and, with one block,
+the system has no off-diagonal entry; iteration counts are compared too.
 """
 import numpy as np
 import pytest
@@ -103,6 +107,99 @@ def test_gpu_pcg_matches_restatement(g2o_amd_mod, name, algo, pd):
     x_direct = np.linalg.solve(A, bs)
     e_g, e_r = np.linalg.norm(xg - x_direct), np.linalg.norm(x_ref - x_direct)
     assert abs(e_g - e_r) <= PCG_RTOL * np.linalg.norm(x_direct)
+
+
+def _first_poses(pd, nfree):
+    """The first nfree + 1 poses (pose 0 fixed) of the SE2 grid (pd 3) or the sphere (pd 6) with the edges among them:
+    n = pd * nfree is 3 to 30. Below 16 the whole solve is the uncaptured tail of the device loop (maxit = n is less
+    than a captured chunk); with one free block the system has no off-diagonal entry."""
+    base = synth.se2_grid(num_poses=40) if pd == 3 else synth.sphere(nodes_per_level=4, laps=3)
+    v, e = base.vertices[0], base.edges[0]
+    nv = nfree + 1
+    keep = (e.v0 < nv) & (e.v1 < nv)
+    assert v.fixed[0] == 1 and not v.fixed[1:nv].any() and keep.sum() >= nfree
+    # the generators chain the estimates from the odometry: moved off it, or the odometry edges' errors (all of b
+    # with one free pose) are zero
+    rng = np.random.default_rng(10 * pd + nfree)
+    est = v.est[:nv].copy()
+    if pd == 3:
+        est[1:] += rng.standard_normal((nfree, 3)) * (0.05, 0.05, 0.02)
+    else:
+        est[1:, :3] += rng.standard_normal((nfree, 3)) * 0.05
+        est[1:, 3:] += rng.standard_normal((nfree, 4)) * 0.01
+        est[1:, 3:] /= np.linalg.norm(est[1:, 3:], axis=1, keepdims=True)
+    vs = synth.VertexSet(v.vtype, v.ids[:nv], est, v.fixed[:nv], v.marginalized[:nv])
+    es = synth.EdgeSet(e.etype, e.v0[keep], e.v1[keep], e.meas[keep], e.info[keep], None)
+    return synth.Problem(f"{base.name}_first{nv}", [vs], [es], pd, 0)
+
+
+def _small_lambda(A0):
+    return 1e-3 * float(np.max(np.diag(A0)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nfree", [1, 2, 3, 5])
+@pytest.mark.parametrize("pd", [3, 6])
+def test_gpu_pcg_small_systems(g2o_amd_mod, pd, nfree):
+    """Pose graphs of 1, 2, 3 and 5 free blocks through stage(lambda): x and the iteration count against the
+    restatement on the system the device staged; one block: block-Jacobi is exact, one iteration gives the direct
+    solution to 1e-12."""
+    prob = _first_poses(pd, nfree)
+    opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+    opt.set_algorithm("lm_pcg")
+    lam = _small_lambda(opt.stage(0.0)["Hschur"])
+    opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)  # a fresh handle: no residual carried from the probe
+    opt.set_algorithm("lm_pcg")
+    g = opt.stage(lam)
+    A, b = g["Hschur"], g["bschur"]
+    assert A.shape == (pd * nfree, pd * nfree) and np.linalg.norm(b) > 0
+    x_ref, it, _ = pcg_ref.pcg_solve(A, b, pd)
+    xg = g["x"][:g["np"]]
+    itg = opt.linear_iterations()
+    err = np.linalg.norm(xg - x_ref) / np.linalg.norm(x_ref)
+    print(f"pd {pd} blocks {nfree}: iterations {itg} / {it}, x {err:.3e}")
+    assert 0 < it <= len(b) and itg == it, (itg, it)
+    assert err <= PCG_RTOL, err
+    if nfree == 1:
+        xd = np.linalg.solve(A, b)
+        assert it == 1 and np.linalg.norm(xg - xd) <= 1e-12 * np.linalg.norm(xd), np.linalg.norm(xg - xd)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pd,nfree", [(3, 5), (6, 5)])
+def test_gpu_pcg_carried_residual_between_solves(g2o_amd_mod, pd, nfree):
+    """Solver mode, outside the LM loop: two solve() calls on one handle at the same lambda, then one at a larger
+    lambda; every solve starts from the absolute residual the one before it left (linear_solver_pcg.hpp:125-128,
+    153), as pcg_solve(..., residual=) does."""
+    prob = _first_poses(pd, nfree)
+    probe = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+    probe.set_algorithm("lm_pcg")
+    g0 = probe.stage(0.0)
+    A0, b = g0["Hschur"], g0["bschur"]
+    lam = _small_lambda(A0)
+    opt = g2o_amd_mod.SparseOptimizer(0).add_problem(prob)
+    opt.set_algorithm("lm_pcg")
+    opt.initialize_optimization()
+    opt.build_structure()
+    opt.build_system()
+    assert np.linalg.norm(opt.b() - b) <= 1e-12 * np.linalg.norm(b)
+    res = -1.0
+    n = len(b)
+    # the third solve: at the larger lambda tolerance * dn_0 falls below the carried residual, which then is the stop
+    # threshold (at the same lambda the carried 0.5 dn is below tolerance * dn_0 and changes nothing)
+    for lm in (lam, lam, 1e3 * lam):
+        opt.set_lambda(lm)
+        assert opt.solve()
+        A = A0 + lm * np.eye(n)
+        x_ref, it, res_new = pcg_ref.pcg_solve(A, b, pd, residual=res)
+        _, it_plain, _ = pcg_ref.pcg_solve(A, b, pd)
+        xg, itg = opt.x(), opt.linear_iterations()
+        print(f"pd {pd} lambda {lm:.3g}: iterations {itg} / {it} (without the carried residual {it_plain})")
+        assert itg == it, (lm, itg, it)
+        assert np.linalg.norm(xg - x_ref) <= PCG_RTOL * np.linalg.norm(x_ref), (lm, it)
+        res = res_new
+    if pd == 3:  # on the SE2 graph the carried residual cuts the last solve short (3 iterations instead of 4)
+        assert it < it_plain, (it, it_plain)
 
 
 @pytest.mark.gpu
