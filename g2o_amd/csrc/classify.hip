@@ -14,6 +14,7 @@
 #include "../../include/g2o_hip.h"
 #include "common.hpp"
 #include "device_types.hpp"
+#include "family_dispatch.hpp"
 #include "kernels.hpp"
 
 namespace g2ohip {
@@ -98,53 +99,28 @@ __global__ void __launch_bounds__(CL_BLOCK) k_classify_final(const long long* __
 }
 
 namespace launch {
-bool family_has_depth(int family) {
-  return family == FAM_BA || family == FAM_BA_STEREO || family == FAM_U_POSE_ONLY || family == FAM_U_STEREO_POSE_ONLY;
-}
 int classify_blocks(int ne) { return (int)grid_for((size_t)(ne > 0 ? ne : 1), CL_BLOCK); }
-
-template <class F>
-static void classify_launch(const EdgeData& d, int ne, const ClassifyArgs& c, hipStream_t s) {
-  hipLaunchKernelGGL(k_classify<F>, classify_blocks(ne), CL_BLOCK, 0, s, d, ne, c);
-}
 
 void classify(int family, const EdgeArgs& a, int ne, const ClassifyArgs& c, hipStream_t s) {
   if (ne <= 0) {
     if (c.level) HIP_CHECK(hipMemsetAsync(c.counts, 0, sizeof(long long) * 3, s));
     return;
   }
-  if ((c.depth || c.check_depth) && !family_has_depth(family))
-    throw std::runtime_error("classify: the edge family has no depth test");
   if (c.level && (!c.part || !c.counts)) throw std::runtime_error("classify: no count buffers");
   const EdgeData d{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, 0, 1.0, a.ue};  // raw chi2: no robust kernel
-  switch (family) {
-    case FAM_BA: classify_launch<FamilyBA>(d, ne, c, s); break;
-    case FAM_BA_STEREO: classify_launch<FamilyStereo>(d, ne, c, s); break;
-    case FAM_BA_UVU: classify_launch<FamilyUVU>(d, ne, c, s); break;  // no isDepthPositive in the reference
-    case FAM_SE3: classify_launch<FamilySE3>(d, ne, c, s); break;
-    case FAM_SE2: classify_launch<FamilySE2>(d, ne, c, s); break;
-    case FAM_SE2XY: classify_launch<FamilySE2XY>(d, ne, c, s); break;
-    case FAM_SE3_XYZ: classify_launch<FamilySE3XYZ>(d, ne, c, s); break;
-    case FAM_SE3_XYZ_DEPTH: classify_launch<FamilySE3XYZDepth>(d, ne, c, s); break;
-    case FAM_SE3_XYZ_DISPARITY: classify_launch<FamilySE3XYZDisparity>(d, ne, c, s); break;
-    case FAM_EXPMAP: classify_launch<FamilyExpmap>(d, ne, c, s); break;
-    case FAM_SBA_MONO: classify_launch<FamilySBAMono>(d, ne, c, s); break;
-    case FAM_SBA_STEREO: classify_launch<FamilySBAStereo>(d, ne, c, s); break;
-    case FAM_SE3_OFFSET: classify_launch<FamilySE3Offset>(d, ne, c, s); break;
-    case FAM_SE2_OFFSET: classify_launch<FamilySE2Offset>(d, ne, c, s); break;
-    case FAM_SE2XY_BEARING: classify_launch<FamilySE2XYBearing>(d, ne, c, s); break;
-    case FAM_GICP: classify_launch<FamilyGICP>(d, ne, c, s); break;
-    case FAM_VSC: classify_launch<FamilyVSC>(d, ne, c, s); break;
-    case FAM_SIM3: classify_launch<FamilySim3>(d, ne, c, s); break;  // no isDepthPositive in the reference
-    case FAM_U_SE2: classify_launch<FamilyUnarySE2>(d, ne, c, s); break;
-    case FAM_U_SE2XY: classify_launch<FamilyUnarySE2XY>(d, ne, c, s); break;
-    case FAM_U_XY: classify_launch<FamilyUnaryXY>(d, ne, c, s); break;
-    case FAM_U_SE3: classify_launch<FamilyUnarySE3>(d, ne, c, s); break;
-    case FAM_U_XYZ: classify_launch<FamilyUnaryXYZ>(d, ne, c, s); break;
-    case FAM_U_POSE_ONLY: classify_launch<FamilyPoseOnly>(d, ne, c, s); break;
-    case FAM_U_STEREO_POSE_ONLY: classify_launch<FamilyStereoPoseOnly>(d, ne, c, s); break;
-    default: throw std::runtime_error("classify: no device family (host-Jacobian edges hold their errors on the host)");
-  }
+  auto go = [&](auto fam) {
+    using F = decltype(fam);
+    if constexpr (is_hostj_type<F>::value) {  // (no k_classify exists for them)
+      throw std::runtime_error("classify: no device family (host-Jacobian edges hold their errors on the host)");
+    } else {
+      if ((c.depth || c.check_depth) && !has_depth<F>::value)
+        throw std::runtime_error("classify: the edge family has no depth test");
+      hipLaunchKernelGGL(k_classify<F>, classify_blocks(ne), CL_BLOCK, 0, s, d, ne, c);
+    }
+  };
+  // (the binary families first: the order the kernels are instantiated in, and so laid out in the code object)
+  if (!is_unary_family(family)) binary_dispatch(family, a, go);
+  else unary_dispatch(family, a, go);
   KERNEL_CHECK();
   if (c.level) {
     hipLaunchKernelGGL(k_classify_final, 1, CL_BLOCK, 0, s, c.part, classify_blocks(ne), c.counts);

@@ -382,7 +382,7 @@ DI void inv3_cofactor(const double* a, double* out) {
 
 // ---- EdgeSE3ProjectXYZ: v0 = point (3), v1 = camera SE3Quat (6) ----
 struct FamilyBA {
-  static constexpr int D = 2, DA = 3, DB = 6, MEAS = 2, INFO = 3;
+  static constexpr int D = 2, DA = 3, DB = 6, MEAS = 2, INFO = 3, PAR = 4;
   static constexpr int SA = 8 /*unused*/, S0 = 3, S1 = 8;  // state strides
   // the error, and the point's z in the camera frame (isDepthPositive, types_six_dof_expmap.h:218-222)
   DI static double depth(const EdgeData& d, int e, double* err) {
@@ -558,7 +558,7 @@ using FamilyUVU = FamilyStereoT<true>;
 
 // ---- EdgeSE3 (Isometry3): meas payload = Zinv [12], info packed upper 21 ----
 struct FamilySE3 {
-  static constexpr int D = 6, DA = 6, DB = 6, MEAS = 12, INFO = 21;
+  static constexpr int D = 6, DA = 6, DB = 6, MEAS = 12, INFO = 21, PAR = 0;
   DI static void error(const EdgeData& d, int e, double* err) {
     const double* Xi = d.s0 + (size_t)d.v0[e] * 12;
     const double* Xj = d.s1 + (size_t)d.v1[e] * 12;
@@ -665,7 +665,7 @@ struct FamilySE3 {
 
 // ---- EdgeSE2: meas payload = inverse measurement (x y theta), info packed 6 ----
 struct FamilySE2 {
-  static constexpr int D = 3, DA = 3, DB = 3, MEAS = 3, INFO = 6;
+  static constexpr int D = 3, DA = 3, DB = 3, MEAS = 3, INFO = 6, PAR = 0;
   DI static void compose(const double* a, const double* b, double* o) {
     const double c = cos(a[2]), s = sin(a[2]);
     o[0] = a[0] + (c * b[0] - s * b[1]);
@@ -709,7 +709,7 @@ struct FamilySE2 {
 // error = v0^-1 * l - z (edge_se2_pointxy.h:44-49, SE2::inverse se2.h:82-87, SE2 * Vector2 = t + R v se2.h:77-80),
 // Jacobians edge_se2_pointxy.cpp:63-87 ----
 struct FamilySE2XY {
-  static constexpr int D = 2, DA = 3, DB = 2, MEAS = 2, INFO = 3;
+  static constexpr int D = 2, DA = 3, DB = 2, MEAS = 2, INFO = 3, PAR = 0;
   DI static void error(const EdgeData& d, int e, double* err) {
     const double* xi = d.s0 + (size_t)d.v0[e] * 3;
     const double* l = d.s1 + (size_t)d.v1[e] * 2;
@@ -861,7 +861,7 @@ using FamilySE3XYZDisparity = FamilySlam3d<SLAM3D_DISPARITY>;
 // edge; there is no parameter record and no depth test (the reference types have no isDepthPositive). ----
 template <bool STEREO>
 struct FamilySBA {
-  static constexpr int D = STEREO ? 3 : 2, DA = 3, DB = 6, MEAS = D, INFO = D * (D + 1) / 2;
+  static constexpr int D = STEREO ? 3 : 2, DA = 3, DB = 6, MEAS = D, INFO = D * (D + 1) / 2, PAR = 0;
   static constexpr int S0 = 3, S1 = 12;  // state strides
   // pc = R^T (pw - t); Rt = R^T row-major
   DI static void to_camera(const double* c, const double* p, double* Rt, double* pc) {
@@ -1158,7 +1158,7 @@ struct FamilySE2Offset {
 // error = normalize_theta(z - atan2(d.y, d.x)). The reference has no analytic Jacobian; these are the exact ones: with
 // g = (-d.y, d.x) / |d|^2, Ji = [ g R(theta)^T | 1 ], Jj = -g R(theta)^T. Singular at d = 0, as the reference. ----
 struct FamilySE2XYBearing {
-  static constexpr int D = 1, DA = 3, DB = 2, MEAS = 1, INFO = 1;
+  static constexpr int D = 1, DA = 3, DB = 2, MEAS = 1, INFO = 1, PAR = 0;
   // d = v0^-1 * l
   DI static void to_sensor(const double* xi, const double* l, double* dd) {
     const double a[3] = {xi[0], xi[1], xi[2]};
@@ -1382,7 +1382,7 @@ struct FamilyHostJ {
 // ---- EdgeSE2Prior (edge_se2_prior.h:39-77): meas payload = inverse measurement (x y theta), info packed 6.
 // error = (Z^-1 * x).toVector(); J = [R(Z^-1) 0; 0 1] ----
 struct FamilyUnarySE2 {
-  static constexpr int D = 3, DA = 3, MEAS = 3, INFO = 6;
+  static constexpr int D = 3, DA = 3, MEAS = 3, INFO = 6, PAR = 0;
   DI static void error(const EdgeData& d, int e, double* err) {
     const double* xi = d.s0 + (size_t)d.v0[e] * 3;
     const double* mi = d.meas + (size_t)e * 3;
@@ -1401,7 +1401,7 @@ struct FamilyUnarySE2 {
 
 // ---- EdgeSE2XYPrior (edge_se2_xyprior.h:39-71, .cpp:60-63): error = translation - z, J = [I 0] ----
 struct FamilyUnarySE2XY {
-  static constexpr int D = 2, DA = 3, MEAS = 2, INFO = 3;
+  static constexpr int D = 2, DA = 3, MEAS = 2, INFO = 3, PAR = 0;
   DI static void error(const EdgeData& d, int e, double* err) {
     const double* xi = d.s0 + (size_t)d.v0[e] * 3;
     const double* m = d.meas + (size_t)e * 2;
@@ -1419,7 +1419,7 @@ struct FamilyUnarySE2XY {
 // error = estimate - z, J = I ----
 template <int N>
 struct FamilyUnaryPoint {
-  static constexpr int D = N, DA = N, MEAS = N, INFO = N * (N + 1) / 2;
+  static constexpr int D = N, DA = N, MEAS = N, INFO = N * (N + 1) / 2, PAR = 0;
   DI static void error(const EdgeData& d, int e, double* err) {
     const double* p = d.s0 + (size_t)d.v0[e] * N;
     const double* m = d.meas + (size_t)e * N;
@@ -1439,7 +1439,7 @@ using FamilyUnaryXYZ = FamilyUnaryPoint<3>;
 // error = toVectorMQT(Z^-1 * (X * P)) (the cache's n2w = X * P); Jacobian computeEdgeSE3PriorGradient
 // (isometry3d_gradients.h:265-325, the gcc branch): A = Z^-1 X, B = P, E = A B ----
 struct FamilyUnarySE3 {
-  static constexpr int D = 6, DA = 6, MEAS = 24, INFO = 21;
+  static constexpr int D = 6, DA = 6, MEAS = 24, INFO = 21, PAR = 0;
   DI static void load(const EdgeData& d, int e, double* X, double* Zi, double* P) {
     const double* x = d.s0 + (size_t)d.v0[e] * 12;
     const double* m = d.meas + (size_t)e * 24;
@@ -1601,7 +1601,7 @@ DI void se3q_adj(const double* q, const double* t, double sgn, double* J) {
 // Jacobians, exact at zero error only. The error is finished before the Jacobians start, so that the temporaries of
 // the log and of the two adjoints are not live together. ----
 struct FamilyExpmap {
-  static constexpr int D = 6, DA = 6, DB = 6, MEAS = 8, INFO = 21;
+  static constexpr int D = 6, DA = 6, DB = 6, MEAS = 8, INFO = 21, PAR = 0;
   DI static void load(const double* p, double* q, double* t) {
     t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
     q[0] = p[3]; q[1] = p[4]; q[2] = p[5]; q[3] = p[6];
@@ -1868,7 +1868,7 @@ DI void sim3_adT_apply(const double* R, const double* t, double s, const double*
 // k_linearize_sim3 (kernels.hip) builds the quadratic form from M^T Omega M and the two adjoints. EdgeData::ue bit 3:
 // the vertices' _fix_scale (column 6 of both Jacobians is zero). ----
 struct FamilySim3 {
-  static constexpr int D = 7, DA = 7, DB = 7, MEAS = 8, INFO = 28;
+  static constexpr int D = 7, DA = 7, DB = 7, MEAS = 8, INFO = 28, PAR = 0;
   // E = C * S0 * S1^-1 as (R_E, t_E, s_E); with WANT_C also C as (R_C, t_C, s_C)
   template <bool WANT_C>
   DI static void error_transform(const EdgeData& d, int e, double* RE, double* tE, double& sE, double* RC, double* tC,

@@ -32,11 +32,6 @@ static double wall() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-int vertex_dim(int t) {
-  if (t == G2OHIP_V_SIM3) return 7;
-  return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT || t == G2OHIP_V_CAM ? 6
-         : (t == G2OHIP_V_XYZ || t == G2OHIP_V_SE2 ? 3 : (t == G2OHIP_V_XY ? 2 : -1));
-}
 int vertex_est_dim(int t) {
   if (t == G2OHIP_V_CAM) return 12;  // the VERTEX_CAM line: x y z qx qy qz qw fx fy cx cy baseline
   if (t == G2OHIP_V_SIM3) return 8;  // tx ty tz qx qy qz qw s
@@ -54,88 +49,17 @@ int vertex_state_stride(int t) {
   }
   return 0;
 }
-static bool is_hostj_binary(int e) { return e > G2OHIP_E_HOSTJ(0) && e <= G2OHIP_E_HOSTJ(7); }
-static bool is_hostj_unary(int e) { return e > G2OHIP_E_HOSTJ_UNARY(0) && e <= G2OHIP_E_HOSTJ_UNARY(7); }
-// host-Jacobian edge types of either arity
-static bool is_hostj(int e) { return is_hostj_binary(e) || is_hostj_unary(e); }
-// the slam3d landmark edges: EdgeSE3PointXYZ, ...Depth, ...Disparity
-static bool is_slam3d_type(int e) { return e >= G2OHIP_E_SE3_XYZ && e <= G2OHIP_E_SE3_XYZ_DISPARITY; }
-// the sba types on a VertexCam: EdgeProjectP2MC, EdgeProjectP2SC
-static bool is_sba_type(int e) { return e == G2OHIP_E_PROJECT_P2MC || e == G2OHIP_E_PROJECT_P2SC; }
-// the edges between two sensor frames, with two offset parameters: EdgeSE3Offset, EdgeSE2Offset
-static bool is_offset_type(int e) { return e == G2OHIP_E_SE3_OFFSET || e == G2OHIP_E_SE2_OFFSET; }
-// g2o's own BA edges on a CameraParameters parameter: EdgeProjectXYZ2UV, EdgeProjectXYZ2UVU
-static bool is_camparams_type(int e) { return e == G2OHIP_E_PROJECT_XYZ2UV || e == G2OHIP_E_PROJECT_XYZ2UVU; }
-// types_icp: Edge_V_V_GICP between two VertexSE3, Edge_XYZ_VSC from a point to a VertexSCam (a VertexSE3)
-static bool is_icp_type(int e) { return e == G2OHIP_E_V_V_GICP || e == G2OHIP_E_XYZ_VSC; }
-// BaseUnaryEdge types: the five priors, the two pose-only projections (EdgeSE3ProjectXYZOnlyPose and its stereo
-// sibling, on a VertexSE3Expmap) and the unary host-J escape
-static bool is_unary_type(int e) {
-  return (e >= G2OHIP_E_SE2_PRIOR && e <= G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE) || is_hostj_unary(e);
-}
-int edge_dim(int e) {
-  if (is_hostj_binary(e)) return e - G2OHIP_E_HOSTJ(0);
-  if (is_hostj_unary(e)) return e - G2OHIP_E_HOSTJ_UNARY(0);
-  switch (e) {
-    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: case G2OHIP_E_SE2_PRIOR: case G2OHIP_E_XYZ_PRIOR: return 3;
-    case G2OHIP_E_SE3_XYZ: case G2OHIP_E_SE3_XYZ_DEPTH: case G2OHIP_E_SE3_XYZ_DISPARITY: return 3;
-    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: case G2OHIP_E_PROJECT_P2SC: return 3;
-    case G2OHIP_E_PROJECT_P2MC: case G2OHIP_E_PROJECT_XYZ2UV: return 2;
-    case G2OHIP_E_PROJECT_XYZ2UVU: return 3;
-    case G2OHIP_E_V_V_GICP: case G2OHIP_E_XYZ_VSC: return 3;
-    case G2OHIP_E_SE2_XY_PRIOR: case G2OHIP_E_XY_PRIOR: case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: return 2;
-    case G2OHIP_E_SE3_PRIOR: case G2OHIP_E_SE3_EXPMAP: case G2OHIP_E_SE3_OFFSET: return 6;
-    case G2OHIP_E_SE2_OFFSET: return 3;
-    case G2OHIP_E_SE2_XY_BEARING: return 1;
-    case G2OHIP_E_SIM3: return 7;
-  }
-  return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 6 : (e == G2OHIP_E_SE2 ? 3 : -1));
-}
-int edge_meas_dim(int e) {
-  if (is_hostj(e)) return 0;
-  if (e == G2OHIP_E_SE2_XY_PRIOR || e == G2OHIP_E_XY_PRIOR || e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 2;
-  if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_EXPMAP || e == G2OHIP_E_SE3_OFFSET) return 7;
-  if (e == G2OHIP_E_SE2_XY_BEARING) return 1;  // (G2OHIP_E_SE2_OFFSET: x y theta, the default below)
-  if (e == G2OHIP_E_SIM3) return 8;            // the measurement as a Sim3: tx ty tz qx qy qz qw s
-  if (is_slam3d_type(e)) return 3;
-  if (is_sba_type(e)) return e == G2OHIP_E_PROJECT_P2MC ? 2 : 3;
-  if (is_camparams_type(e)) return e == G2OHIP_E_PROJECT_XYZ2UV ? 2 : 3;
-  if (e == G2OHIP_E_V_V_GICP) return 12;  // pos0 normal0 pos1 normal1, the file order (G2OHIP_E_XYZ_VSC: u v u_r, below)
-  return e == G2OHIP_E_SE3_PROJECT_XYZ || e == G2OHIP_E_SE2_XY ? 2 : (e == G2OHIP_E_SE3_QUAT ? 7 : 3);
-}
-// doubles of an edge type's per-edge parameter record: camera intrinsics fx fy cx cy, stereo + bf; the SE3 prior's
-// sensor offset x y z qx qy qz qw (optional: NULL = identity), as EdgeSE3PointXYZ's; the slam3d camera types' offset
-// followed by fx fy cx cy; the pose-only projections' Xw fx fy cx cy (stereo + bf); EdgeSE3Offset / EdgeSE2Offset: the
-// offset of the from vertex, then of the to vertex (2 x 7 / 2 x 3, optional: NULL = both the identity);
-// EdgeProjectXYZ2UV / XYZ2UVU: the CameraParameters focal_length cx cy baseline; Edge_V_V_GICP: cov0 | cov1, each
-// packed upper 6 (optional: NULL = point-to-plane, the information is the caller's); Edge_XYZ_VSC: VertexSCam's static
-// fx fy cx cy baseline
-int edge_param_dim(int e) {
-  if (e == G2OHIP_E_V_V_GICP) return 12;
-  if (e == G2OHIP_E_XYZ_VSC) return 5;
-  if (is_camparams_type(e)) return 4;
-  if (e == G2OHIP_E_SE3_OFFSET) return 14;
-  if (e == G2OHIP_E_SE2_OFFSET) return 6;
-  if (e == G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE) return 7;
-  if (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE) return 8;
-  if (e == G2OHIP_E_SE3_PRIOR || e == G2OHIP_E_SE3_XYZ) return 7;
-  if (e == G2OHIP_E_SE3_XYZ_DEPTH || e == G2OHIP_E_SE3_XYZ_DISPARITY) return 11;
-  return e == G2OHIP_E_SE3_PROJECT_XYZ ? 4 : (e == G2OHIP_E_STEREO_SE3_PROJECT_XYZ ? 5 : 0);
-}
-static int family_of(int etype, int& vtA, int& vtB);
-// doubles of a BA-family edge type's parameter record on the device: the caller's, but a CameraParameters record as
-// f f cx cy (FamilyBA's fx fy cx cy; the baseline stays on the host) or f f cx cy b (FamilyUVU)
-static int ba_device_param_dim(int e) {
-  return e == G2OHIP_E_PROJECT_XYZ2UV ? 4 : (e == G2OHIP_E_PROJECT_XYZ2UVU ? 5 : edge_param_dim(e));
-}
-static void ba_device_params(int e, const double* p, double* out) {
-  if (is_camparams_type(e)) {
+// a BA-family edge's parameter record as the device holds it: the caller's, but a CameraParameters record
+// (focal_length cx cy baseline) as f f cx cy (FamilyBA's fx fy cx cy; the baseline stays on the host) or f f cx cy b
+// (FamilyUVU)
+static void ba_device_params(const EdgeTypeInfo& t, const double* p, double* out) {
+  if (t.type == G2OHIP_E_PROJECT_XYZ2UV || t.type == G2OHIP_E_PROJECT_XYZ2UVU) {
     out[0] = out[1] = p[0];
     out[2] = p[1];
     out[3] = p[2];
-    if (e == G2OHIP_E_PROJECT_XYZ2UVU) out[4] = p[3];
+    if (t.type == G2OHIP_E_PROJECT_XYZ2UVU) out[4] = p[3];
   } else {
-    for (int j = 0; j < edge_param_dim(e); ++j) out[j] = p[j];
+    for (int j = 0; j < t.np; ++j) out[j] = p[j];
   }
 }
 // doubles of one host-J edge's payload: [e | Ji | Jj], a unary edge's [e | Ji]
@@ -1351,19 +1275,22 @@ int Engine::add_vertices(int type, int n, const int* ids, const double* est, con
 
 int Engine::add_edges(int type, int n, const int* v0, const int* v1, const double* meas, const double* info,
                       const double* params) {
-  const int D = edge_dim(type);
-  if (D < 0 || n < 0) return G2OHIP_ERR_ARG;
-  const bool unary = is_unary_type(type);
+  const EdgeTypeInfo* t = edge_type_info(type);
+  if ((!t && !is_hostj(type)) || n < 0) return G2OHIP_ERR_ARG;
+  // (host-Jacobian types: the error dimension from the code, neither measurement nor parameters)
+  const int D = t ? t->D : hostj_dim(type), nm = t ? t->nm : 0, np = t ? t->np : 0;
+  const bool unary = t ? t->vtB == 0 : is_hostj_unary(type);
   if (unary != (v1 == nullptr) && (n > 0 || v1)) return G2OHIP_ERR_ARG;  // v1 is NULL for the unary types, only for them
-  const int np = edge_param_dim(type);
   const bool gicp = type == G2OHIP_E_V_V_GICP;
-  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ && !is_offset_type(type) && !gicp)
+  // the parameter record is optional for the offsets (NULL: the identity) and the GICP covariances
+  if (np > 0 && !params && type != G2OHIP_E_SE3_PRIOR && type != G2OHIP_E_SE3_XYZ && type != G2OHIP_E_SE3_OFFSET &&
+      type != G2OHIP_E_SE2_OFFSET && !gicp)
     return G2OHIP_ERR_ARG;
   if (!info && n > 0 && !(gicp && params)) return G2OHIP_ERR_ARG;  // only a plane-to-plane set goes without one
-  if (is_sba_type(type) && params) return G2OHIP_ERR_ARG;  // the intrinsics live in the VertexCam
-  if (type == G2OHIP_E_SE2_XY_BEARING && params) return G2OHIP_ERR_ARG;  // EdgeSE2PointXYBearing has no parameter
-  if (type == G2OHIP_E_SIM3 && params) return G2OHIP_ERR_ARG;            // nor has EdgeSim3
-  const int nm = edge_meas_dim(type);
+  // no parameter at all: the sba types (the intrinsics live in the VertexCam), EdgeSE2PointXYBearing, EdgeSim3
+  if (params && (type == G2OHIP_E_PROJECT_P2MC || type == G2OHIP_E_PROJECT_P2SC || type == G2OHIP_E_SE2_XY_BEARING ||
+                 type == G2OHIP_E_SIM3))
+    return G2OHIP_ERR_ARG;
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
     if (!hg.idmap.count(v0[k]) || (!unary && !hg.idmap.count(v1[k]))) return G2OHIP_ERR_ARG;
@@ -1485,14 +1412,15 @@ struct Cursor {
   }
   bool more() { ws(); return p < e; }
 };
-// unary: the unary edge tags and PARAMS_SE3OFFSET are parsed (G2OHIP_LOAD_UNARY), else skipped as unknown tags;
-// slam3d: VERTEX_TRACKXYZ, PARAMS_SE3OFFSET, PARAMS_CAMERACALIB and the three landmark edge tags (G2OHIP_LOAD_SLAM3D)
-// expmap: EDGE_SE3:EXPMAP (G2OHIP_LOAD_EXPMAP); sba: VERTEX_CAM, EDGE_PROJECT_P2MC, EDGE_PROJECT_P2SC (G2OHIP_LOAD_SBA)
-// offset: PARAMS_SE3OFFSET, PARAMS_SE2OFFSET, EDGE_SE3_OFFSET, EDGE_SE2_OFFSET, EDGE_BEARING_SE2_XY (G2OHIP_LOAD_OFFSET)
-// camparams: PARAMS_CAMERAPARAMETERS, EDGE_PROJECT_XYZ2UV:EXPMAP (G2OHIP_LOAD_CAMERAPARAMS)
-// icp: EDGE_V_V_GICP (G2OHIP_LOAD_ICP); sim3: VERTEX_SIM3:EXPMAP, EDGE_SIM3:EXPMAP (G2OHIP_LOAD_SIM3)
-void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool expmap, bool sba, bool offset,
-                 bool camparams, bool icp, bool sim3, ParsedChunk& out) {
+// the row of the edge type a tag loads as under the G2OHIP_LOAD_* flags; nullptr: no edge tag, or one the flags skip
+const EdgeTypeInfo* tagged_type(const std::string& tag, unsigned flags) {
+  for (const EdgeTypeInfo& t : EDGE_TYPES)
+    if (t.tag && tag == t.tag) return !t.load_flag || (flags & t.load_flag) ? &t : nullptr;
+  return nullptr;
+}
+// flags: G2OHIP_LOAD_*; a vertex, parameter or edge tag whose flag is not set is skipped as an unknown tag
+void parse_chunk(const char* b, const char* e, unsigned flags, ParsedChunk& out) {
+  const auto on = [flags](unsigned f) { return (flags & f) != 0; };
   while (b < e) {
     const char* nl = static_cast<const char*>(std::memchr(b, '\n', (size_t)(e - b)));
     const char* le = nl ? nl : e;
@@ -1512,7 +1440,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
         std::memcpy(v.est, w, sizeof w);
       }
       out.verts.push_back(v);
-    } else if (tag == "VERTEX_XYZ" || tag == "VERTEX_SE2" || (slam3d && tag == "VERTEX_TRACKXYZ")) {
+    } else if (tag == "VERTEX_XYZ" || tag == "VERTEX_SE2" || (on(G2OHIP_LOAD_SLAM3D) && tag == "VERTEX_TRACKXYZ")) {
       // (VERTEX_TRACKXYZ: VertexPointXYZ, vertex_pointxyz.cpp: x y z)
       ParsedVertex v{tag == "VERTEX_SE2" ? G2OHIP_V_SE2 : G2OHIP_V_XYZ, c.i(), {}};
       for (int k = 0; k < 3; ++k) v.est[k] = c.d();
@@ -1521,7 +1449,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       ParsedVertex v{G2OHIP_V_XY, c.i(), {}};
       for (int k = 0; k < 2; ++k) v.est[k] = c.d();
       out.verts.push_back(v);
-    } else if (sba && tag == "VERTEX_CAM") {
+    } else if (on(G2OHIP_LOAD_SBA) && tag == "VERTEX_CAM") {
       // VertexCam::read (types_sba.cpp:74-112): x y z qx qy qz qw, then fx fy cx cy baseline or, when the line ends
       // after the pose, the defaults 300 300 320 320 0.1. Any other length fails the load.
       ParsedVertex v{G2OHIP_V_CAM, c.i(), {}};
@@ -1538,7 +1466,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
         c.ok = false;
       }
       out.verts.push_back(v);
-    } else if (sim3 && tag == "VERTEX_SIM3:EXPMAP") {
+    } else if (on(G2OHIP_LOAD_SIM3) && tag == "VERTEX_SIM3:EXPMAP") {
       // VertexSim3Expmap::read (types_seven_dof_expmap.cpp:66-87): the log of cam2world, then fx fy cx cy of camera 1;
       // the estimate is Sim3(v).inverse(). A line that ends after the seven values keeps the constructor's intrinsics
       // 1 1 0 0 (:43-57); any other length fails the load. est[8..11]: the intrinsics, kept on the host for save
@@ -1555,7 +1483,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       sim3_inverse_h(g, v.est);
       std::memcpy(v.est + 8, w + 7, sizeof(double) * 4);
       out.verts.push_back(v);
-    } else if (sim3 && tag == "EDGE_SIM3:EXPMAP") {  // EdgeSim3::read (:104-122): the measurement is Sim3(m).inverse()
+    } else if (on(G2OHIP_LOAD_SIM3) && tag == "EDGE_SIM3:EXPMAP") {  // EdgeSim3::read (:104-122): the measurement is Sim3(m).inverse()
       ParsedEdge ed{G2OHIP_E_SIM3, c.i(), c.i(), {}, {}, {}};
       double w[7], g[8];
       for (double& x : w) x = c.d();
@@ -1564,7 +1492,7 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       for (int r = 0; r < 7; ++r)
         for (int q = r; q < 7; ++q) ed.info[r * 7 + q] = ed.info[q * 7 + r] = c.d();
       out.edges.push_back(ed);
-    } else if (sba && (tag == "EDGE_PROJECT_P2MC" || tag == "EDGE_PROJECT_P2SC")) {
+    } else if (on(G2OHIP_LOAD_SBA) && (tag == "EDGE_PROJECT_P2MC" || tag == "EDGE_PROJECT_P2SC")) {
       // types_sba.cpp:204-237: point, camera, the measurement; the information is the identity
       const int D = tag == "EDGE_PROJECT_P2MC" ? 2 : 3;
       ParsedEdge ed{D == 2 ? G2OHIP_E_PROJECT_P2MC : G2OHIP_E_PROJECT_P2SC, c.i(), c.i(), {}, {}, {}};
@@ -1585,35 +1513,11 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       ed.info[0] = o0; ed.info[1] = o1; ed.info[2] = o1; ed.info[3] = o2;
       for (int k = 0; k < 4; ++k) ed.p[k] = c.d();  // fx fy cx cy
       out.edges.push_back(ed);
-    } else if (camparams && tag == "PARAMS_CAMERAPARAMETERS") {  // types_six_dof_expmap.h:59-75: id f cx cy baseline
+    } else if (on(G2OHIP_LOAD_CAMERAPARAMS) && tag == "PARAMS_CAMERAPARAMETERS") {  // types_six_dof_expmap.h:59-75: id f cx cy baseline
       ParsedParam pp{c.i(), {}, false, false, true};
       for (int k = 0; k < 4; ++k) pp.v[k] = c.d();
       out.params.push_back(pp);
-    } else if (camparams && tag == "EDGE_PROJECT_XYZ2UV:EXPMAP") {
-      // types_six_dof_expmap.cpp:248-263: point, camera, the parameter id, u v, the upper triangle of the information.
-      // (EDGE_PROJECT_XYZ2UVU:EXPMAP stays an unknown tag: its reader, :335-346, reads no parameter id, so the edge
-      // has no camera and OptimizableGraph::addEdge drops it, optimizable_graph.cpp:277-280)
-      ParsedEdge ed{G2OHIP_E_PROJECT_XYZ2UV, c.i(), c.i(), {}, {}, {}};
-      ed.pid = c.i();
-      ed.m[0] = c.d(); ed.m[1] = c.d();
-      const double o0 = c.d(), o1 = c.d(), o2 = c.d();
-      ed.info[0] = o0; ed.info[1] = o1; ed.info[2] = o1; ed.info[3] = o2;
-      out.edges.push_back(ed);
-    } else if (tag == "EDGE_SE2_XY") {  // edge_se2_pointxy.cpp:46-52
-      ParsedEdge ed{G2OHIP_E_SE2_XY, c.i(), c.i(), {}, {}, {}};
-      ed.m[0] = c.d(); ed.m[1] = c.d();
-      const double o0 = c.d(), o1 = c.d(), o2 = c.d();
-      ed.info[0] = o0; ed.info[1] = o1; ed.info[2] = o1; ed.info[3] = o2;
-      out.edges.push_back(ed);
-    } else if (tag == "EDGE_SE3:QUAT" || tag == "EDGE_SE2") {  // edge_se3.cpp:42-65, edge_se2.cpp:41-53
-      const bool se3 = tag == "EDGE_SE3:QUAT";
-      const int D = se3 ? 6 : 3, nm = se3 ? 7 : 3;
-      ParsedEdge ed{se3 ? G2OHIP_E_SE3_QUAT : G2OHIP_E_SE2, c.i(), c.i(), {}, {}, {}};
-      for (int k = 0; k < nm; ++k) ed.m[k] = c.d();
-      for (int r = 0; r < D; ++r)
-        for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
-      out.edges.push_back(ed);
-    } else if (expmap && tag == "EDGE_SE3:EXPMAP") {  // types_six_dof_expmap.cpp:114-129: the seven values are
+    } else if (on(G2OHIP_LOAD_EXPMAP) && tag == "EDGE_SE3:EXPMAP") {  // types_six_dof_expmap.cpp:114-129: the seven values are
                                                       // cam2world, the measurement their inverse; information as is
       ParsedEdge ed{G2OHIP_E_SE3_EXPMAP, c.i(), c.i(), {}, {}, {}};
       double w[7];
@@ -1622,67 +1526,38 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
       for (int r = 0; r < 6; ++r)
         for (int q = r; q < 6; ++q) ed.info[r * 6 + q] = ed.info[q * 6 + r] = c.d();
       out.edges.push_back(ed);
-    } else if (offset && tag == "PARAMS_SE2OFFSET") {  // parameter_se2_offset.cpp:50-57: id x y theta
+    } else if (on(G2OHIP_LOAD_OFFSET) && tag == "PARAMS_SE2OFFSET") {  // parameter_se2_offset.cpp:50-57: id x y theta
       ParsedParam pp{c.i(), {}, false, true};
       for (int k = 0; k < 3; ++k) pp.v[k] = c.d();
       out.params.push_back(pp);
-    } else if (offset && (tag == "EDGE_SE3_OFFSET" || tag == "EDGE_SE2_OFFSET")) {
-      // edge_se3_offset.cpp:59-88, edge_se2_offset.cpp:59-84: the two parameter ids, the measurement, the upper
-      // triangle of the information row-wise
-      const bool se3 = tag == "EDGE_SE3_OFFSET";
-      const int D = se3 ? 6 : 3, nm = se3 ? 7 : 3;
-      ParsedEdge ed{se3 ? G2OHIP_E_SE3_OFFSET : G2OHIP_E_SE2_OFFSET, c.i(), c.i(), {}, {}, {}};
-      ed.pid = c.i();
-      ed.pid2 = c.i();
-      for (int k = 0; k < nm; ++k) ed.m[k] = c.d();
-      for (int r = 0; r < D; ++r)
-        for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
-      out.edges.push_back(ed);
-    } else if (icp && tag == "EDGE_V_V_GICP") {  // types_icp.cpp:124-160: pos0 normal0 pos1 normal1; the information
+    } else if (on(G2OHIP_LOAD_ICP) && tag == "EDGE_V_V_GICP") {  // types_icp.cpp:124-160: pos0 normal0 pos1 normal1; the information
                                                  // is built from normal0 when the edges are added (Engine::load)
       ParsedEdge ed{G2OHIP_E_V_V_GICP, c.i(), c.i(), {}, {}, {}};
       for (int k = 0; k < 12; ++k) ed.m[k] = c.d();
       ed.at = t0;
       out.edges.push_back(ed);
-    } else if (offset && tag == "EDGE_BEARING_SE2_XY") {  // edge_se2_pointxy_bearing.cpp:56-60: angle, information
-      ParsedEdge ed{G2OHIP_E_SE2_XY_BEARING, c.i(), c.i(), {}, {}, {}};
-      ed.m[0] = c.d();
-      ed.info[0] = c.d();
-      out.edges.push_back(ed);
-    } else if ((unary || slam3d || offset) && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
+    } else if (on(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_OFFSET) && tag == "PARAMS_SE3OFFSET") {  // parameter_se3_offset.cpp: id, then the offset as toVectorQT
       ParsedParam pp{c.i(), {}};
       for (int k = 0; k < 7; ++k) pp.v[k] = c.d();
       out.params.push_back(pp);
-    } else if (slam3d && tag == "PARAMS_CAMERACALIB") {  // parameter_camera.cpp:62-85: id, offset, fx fy cx cy
+    } else if (on(G2OHIP_LOAD_SLAM3D) && tag == "PARAMS_CAMERACALIB") {  // parameter_camera.cpp:62-85: id, offset, fx fy cx cy
       ParsedParam pp{c.i(), {}, true};
       for (double& x : pp.v) x = c.d();
       out.params.push_back(pp);
-    } else if (slam3d && (tag == "EDGE_SE3_TRACKXYZ" || tag == "EDGE_PROJECT_DEPTH" || tag == "EDGE_PROJECT_DISPARITY")) {
-      // edge_se3_pointxyz.cpp:57-86 and its siblings: pose, point, parameter id, measurement, upper triangle of the
-      // information row-wise
-      ParsedEdge ed{tag == "EDGE_SE3_TRACKXYZ"    ? G2OHIP_E_SE3_XYZ
-                    : tag == "EDGE_PROJECT_DEPTH" ? G2OHIP_E_SE3_XYZ_DEPTH
-                                                  : G2OHIP_E_SE3_XYZ_DISPARITY,
-                    c.i(), c.i(), {}, {}, {}};
-      ed.pid = c.i();
-      for (int k = 0; k < 3; ++k) ed.m[k] = c.d();
-      for (int r = 0; r < 3; ++r)
-        for (int q = r; q < 3; ++q) ed.info[r * 3 + q] = ed.info[q * 3 + r] = c.d();
-      out.edges.push_back(ed);
-    } else if (unary && (tag == "EDGE_PRIOR_SE2" || tag == "EDGE_PRIOR_SE2_XY" || tag == "EDGE_PRIOR_XY" ||
-                         tag == "EDGE_POINTXYZ_PRIOR" || tag == "EDGE_SE3_PRIOR")) {
-      // edge_se2_prior.cpp:43-55, edge_se2_xyprior.cpp:36-48, edge_xy_prior.cpp:45-57, edge_xyz_prior.cpp:37-52,
-      // edge_se3_prior.cpp:55-75 (the parameter id ahead of the measurement): measurement, upper triangle of the
-      // information row-wise
-      const int type = tag == "EDGE_PRIOR_SE2"        ? G2OHIP_E_SE2_PRIOR
-                       : tag == "EDGE_PRIOR_SE2_XY"   ? G2OHIP_E_SE2_XY_PRIOR
-                       : tag == "EDGE_PRIOR_XY"       ? G2OHIP_E_XY_PRIOR
-                       : tag == "EDGE_POINTXYZ_PRIOR" ? G2OHIP_E_XYZ_PRIOR
-                                                      : G2OHIP_E_SE3_PRIOR;
-      ParsedEdge ed{type, c.i(), -1, {}, {}, {}};
-      if (type == G2OHIP_E_SE3_PRIOR) ed.b = c.i();
-      const int D = edge_dim(type), nm = edge_meas_dim(type);
-      for (int k = 0; k < nm; ++k) ed.m[k] = c.d();
+    } else if (const EdgeTypeInfo* t = tagged_type(tag, flags); t && t->info_upper) {
+      // the regular edge lines (edge_se3.cpp:42-65, edge_se2.cpp:41-53, edge_se2_pointxy.cpp:46-52,
+      // edge_se2_pointxy_bearing.cpp:56-60, edge_se3_offset.cpp:59-88, edge_se2_offset.cpp:59-84, edge_se3_pointxyz.cpp:
+      // 57-86 and its siblings, the priors' edge_se2_prior.cpp:43-55, edge_se2_xyprior.cpp:36-48, edge_xy_prior.cpp:45-57,
+      // edge_xyz_prior.cpp:37-52, edge_se3_prior.cpp:55-75, types_six_dof_expmap.cpp:248-263): the vertices, the
+      // parameter ids, the measurement, the upper triangle of the information row-wise.
+      // (EDGE_PROJECT_XYZ2UVU:EXPMAP stays an unknown tag: its reader, types_six_dof_expmap.cpp:335-346, reads no
+      // parameter id, so the edge has no camera and OptimizableGraph::addEdge drops it, optimizable_graph.cpp:277-280)
+      ParsedEdge ed{t->type, c.i(), t->vtB ? c.i() : -1, {}, {}, {}};
+      if (!t->vtB && t->npid) ed.b = c.i();  // EDGE_SE3_PRIOR: the parameter id in the place of the second vertex
+      else if (t->npid) ed.pid = c.i();
+      if (t->npid == 2) ed.pid2 = c.i();
+      const int D = t->D;
+      for (int k = 0; k < t->nm; ++k) ed.m[k] = c.d();
       for (int r = 0; r < D; ++r)
         for (int q = r; q < D; ++q) ed.info[r * D + q] = ed.info[q * D + r] = c.d();
       out.edges.push_back(ed);
@@ -1696,10 +1571,6 @@ void parse_chunk(const char* b, const char* e, bool unary, bool slam3d, bool exp
 }  // namespace
 
 int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
-  const bool unary = (flags & G2OHIP_LOAD_UNARY) != 0, slam3d = (flags & G2OHIP_LOAD_SLAM3D) != 0,
-             expmap = (flags & G2OHIP_LOAD_EXPMAP) != 0, sba = (flags & G2OHIP_LOAD_SBA) != 0,
-             offset = (flags & G2OHIP_LOAD_OFFSET) != 0, camparams = (flags & G2OHIP_LOAD_CAMERAPARAMS) != 0,
-             icp = (flags & G2OHIP_LOAD_ICP) != 0, sim3 = (flags & G2OHIP_LOAD_SIM3) != 0;
   FILE* f = fopen(path, "rb");
   if (!f) return G2OHIP_ERR_ARG;
   std::vector<char> buf;
@@ -1728,7 +1599,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
     std::vector<std::thread> th;
     for (int t = 0; t < nthreads; ++t)
       th.emplace_back(
-          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], unary, slam3d, expmap, sba, offset, camparams, icp, sim3, chunks[t]); });
+          [&, t] { parse_chunk(base + cut[t], base + cut[t + 1], flags, chunks[t]); });
     for (auto& x : th) x.join();
   }
   std::vector<std::string> warned;
@@ -1772,8 +1643,9 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
   auto flush_e = [&](int type) -> int {
     if (ea.empty()) return G2OHIP_OK;
     // (a loaded Edge_V_V_GICP is point-to-plane: no parameter record)
-    const int r = add_edges(type, (int)ea.size(), ea.data(), is_unary_type(type) ? nullptr : eb.data(), em.data(),
-                            ei.data(), edge_param_dim(type) && type != G2OHIP_E_V_V_GICP ? ep.data() : nullptr);
+    const EdgeTypeInfo& t = *edge_type_info(type);
+    const int r = add_edges(type, (int)ea.size(), ea.data(), t.vtB ? eb.data() : nullptr, em.data(), ei.data(),
+                            t.np && type != G2OHIP_E_V_V_GICP ? ep.data() : nullptr);
     ea.clear(); eb.clear(); em.clear(); ei.clear(); ep.clear();
     return r;
   };
@@ -1789,10 +1661,9 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
         if (int r = flush_e(cur)) return r;
         cur = ed.type;
       }
-      const int D = edge_dim(ed.type), nm = edge_meas_dim(ed.type);
-      if (is_unary_type(ed.type)) {  // the vertex type is checked here: a message names the line's vertex
-        int vtA, vtB;
-        family_of(ed.type, vtA, vtB);
+      const EdgeTypeInfo& t = *edge_type_info(ed.type);  // (the parser stores types of the table only)
+      const int D = t.D, nm = t.nm, vtA = t.vtA, vtB = t.vtB;
+      if (!vtB) {  // a unary edge; the vertex type is checked here: a message names the line's vertex
         auto it = hg.idmap.find(ed.a);
         if (it == hg.idmap.end() || hg.verts[it->second].type != vtA)
           throw StatusError(G2OHIP_ERR_ARG, "g2o_hip load: unary edge (type " + std::to_string(ed.type) + ") on vertex " +
@@ -1822,8 +1693,8 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                   std::to_string(ed.b) + ": vertex " + std::to_string(id) +
                                                   " is missing or no VERTEX_SIM3:EXPMAP");
         }
-      if (is_sba_type(ed.type)) {  // v0 a VERTEX_XYZ point, v1 a VERTEX_CAM
-        const char* tg = ed.type == G2OHIP_E_PROJECT_P2MC ? "EDGE_PROJECT_P2MC " : "EDGE_PROJECT_P2SC ";
+      if (is_sba_family(t.family)) {  // v0 a VERTEX_XYZ point, v1 a VERTEX_CAM
+        const std::string tg = std::string(t.tag) + " ";
         auto ia = hg.idmap.find(ed.a), ib = hg.idmap.find(ed.b);
         if (ia == hg.idmap.end() || hg.verts[ia->second].type != G2OHIP_V_XYZ)
           throw StatusError(G2OHIP_ERR_ARG, std::string("g2o_hip load: ") + tg + std::to_string(ed.a) + " -> " +
@@ -1834,12 +1705,10 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                 std::to_string(ed.b) + ": vertex " + std::to_string(ed.b) +
                                                 " is missing or no VERTEX_CAM");
       }
-      if (is_offset_type(ed.type) || ed.type == G2OHIP_E_SE2_XY_BEARING) {
+      const bool offset_edge = ed.type == G2OHIP_E_SE3_OFFSET || ed.type == G2OHIP_E_SE2_OFFSET;
+      if (offset_edge || ed.type == G2OHIP_E_SE2_XY_BEARING) {
         const bool se3 = ed.type == G2OHIP_E_SE3_OFFSET;
-        const std::string tg = se3 ? "EDGE_SE3_OFFSET " : ed.type == G2OHIP_E_SE2_OFFSET ? "EDGE_SE2_OFFSET " : "EDGE_BEARING_SE2_XY ";
-        const std::string where = "g2o_hip load: " + tg + std::to_string(ed.a) + " -> " + std::to_string(ed.b);
-        int vtA, vtB;
-        family_of(ed.type, vtA, vtB);
+        const std::string where = std::string("g2o_hip load: ") + t.tag + " " + std::to_string(ed.a) + " -> " + std::to_string(ed.b);
         const char* vname[2] = {se3 ? "VERTEX_SE3:QUAT" : "VERTEX_SE2", vtB == G2OHIP_V_XY ? "VERTEX_XY" : (se3 ? "VERTEX_SE3:QUAT" : "VERTEX_SE2")};
         const int want[2] = {vtA, vtB}, end[2] = {ed.a, ed.b};
         for (int h = 0; h < 2; ++h) {
@@ -1847,7 +1716,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
           if (it == hg.idmap.end() || hg.verts[it->second].type != want[h])
             throw StatusError(G2OHIP_ERR_ARG, where + ": vertex " + std::to_string(end[h]) + " is missing or no " + vname[h]);
         }
-        if (is_offset_type(ed.type)) {
+        if (offset_edge) {
           const int pid[2] = {ed.pid, ed.pid2}, np = se3 ? 7 : 3;
           const char* pname = se3 ? "PARAMS_SE3OFFSET" : "PARAMS_SE2OFFSET";
           for (int h = 0; h < 2; ++h) {
@@ -1910,7 +1779,7 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
             ed.info[r * 3 + q] = s;
           }
       }
-      if (is_slam3d_type(ed.type)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
+      if (is_slam3d_family(t.family)) {  // the offset of EDGE_SE3_TRACKXYZ, the camera of the projections
         const bool cam = ed.type != G2OHIP_E_SE3_XYZ;
         auto po = offsets.find(ed.pid);
         if (po == offsets.end() || po->second->camera != cam || po->second->se2 || po->second->camparams)
@@ -1918,13 +1787,13 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                 std::to_string(ed.a) + " -> " + std::to_string(ed.b) +
                                                 " names parameter id " + std::to_string(ed.pid) + ", which no " +
                                                 (cam ? "PARAMS_CAMERACALIB" : "PARAMS_SE3OFFSET") + " line defines");
-        std::memcpy(ed.p, po->second->v, sizeof(double) * (cam ? 11 : 7));
+        std::memcpy(ed.p, po->second->v, sizeof(double) * t.np);
       }
       ea.push_back(ed.a);
       eb.push_back(ed.b);
       em.insert(em.end(), ed.m, ed.m + nm);
       ei.insert(ei.end(), ed.info, ed.info + D * D);
-      if (ed.type != G2OHIP_E_V_V_GICP) ep.insert(ep.end(), ed.p, ed.p + edge_param_dim(ed.type));
+      if (ed.type != G2OHIP_E_V_V_GICP) ep.insert(ep.end(), ed.p, ed.p + t.np);
     }
   if (int r = flush_e(cur)) return r;
   for (auto& c : chunks)
@@ -1978,11 +1847,10 @@ int Engine::save(const char* path) {
     }
   };
   // parameters first (optimizable_graph.cpp:663-667): one PARAMS_SE3OFFSET line per distinct offset of the SE3 priors,
-  // ids in first-seen order; prior_pid[k] = the id edge k's line names
-  // The slam3d landmark edges' offsets and cameras (PARAMS_CAMERACALIB, parameter_camera.cpp:75-85) follow in the
-  // same id space; pids[set][k] = the id edge k of that set names. Track points: the G2OHIP_V_XYZ vertices such an
-  // edge touches, written as VERTEX_TRACKXYZ.
-  std::vector<int> prior_pid;
+  // ids in first-seen order. The slam3d landmark edges' offsets and cameras (PARAMS_CAMERACALIB,
+  // parameter_camera.cpp:75-85) follow in the same id space, then the offset edges' and the CameraParameters;
+  // pids[set][npid k + h] = the h-th id edge k of that set names. Track points: the G2OHIP_V_XYZ vertices a slam3d edge
+  // touches, written as VERTEX_TRACKXYZ.
   std::vector<std::vector<int>> pids(hg.esets.size());
   std::vector<char> track(hg.verts.size(), 0);
   {
@@ -1990,7 +1858,8 @@ int Engine::save(const char* path) {
                                                           // 4 CameraParameters: f cx cy baseline)
     // (the offset edges hold two records of np = 7 / 3 per edge: ids of 2 n half-records, from then to)
     auto ids_of = [&](const HEdgeSet& es, std::vector<int>& ids) {
-      const int per = is_offset_type(es.type) ? 2 : 1, np = edge_param_dim(es.type) / per;
+      const EdgeTypeInfo& t = *edge_type_info(es.type);
+      const int per = t.npid, np = t.np / per;
       ids.resize(es.ev0.size() * per);
       for (size_t k = 0; k < ids.size(); ++k) {
         const double* p = es.params.data() + k * np;
@@ -2010,16 +1879,15 @@ int Engine::save(const char* path) {
         ids[k] = (int)j;
       }
     };
-    if (const HEdgeSet* ps = hg.set_of(G2OHIP_E_SE3_PRIOR)) ids_of(*ps, prior_pid);
-    for (size_t si = 0; si < hg.esets.size(); ++si)
-      if (is_slam3d_type(hg.esets[si].type)) {
+    // (the id space is first-seen in this order of the parameter kinds, whatever the order of the edge sets)
+    for (unsigned kind : {G2OHIP_LOAD_UNARY, G2OHIP_LOAD_SLAM3D, G2OHIP_LOAD_OFFSET, G2OHIP_LOAD_CAMERAPARAMS})
+      for (size_t si = 0; si < hg.esets.size(); ++si) {
+        const EdgeTypeInfo* t = edge_type_info(hg.esets[si].type);
+        if (!t || !t->npid || t->load_flag != kind) continue;
         ids_of(hg.esets[si], pids[si]);
-        for (int v : hg.esets[si].ev1) track[v] = 1;
+        if (kind == G2OHIP_LOAD_SLAM3D)
+          for (int v : hg.esets[si].ev1) track[v] = 1;
       }
-    for (size_t si = 0; si < hg.esets.size(); ++si)
-      if (is_offset_type(hg.esets[si].type)) ids_of(hg.esets[si], pids[si]);
-    for (size_t si = 0; si < hg.esets.size(); ++si)  // one PARAMS_CAMERAPARAMETERS line per distinct record
-      if (hg.esets[si].type == G2OHIP_E_PROJECT_XYZ2UV) ids_of(hg.esets[si], pids[si]);
     flush();
   }
   parallel_ranges(hg.verts.size(), nt, [&](int t, size_t lo, size_t hi) {
@@ -2062,35 +1930,18 @@ int Engine::save(const char* path) {
       continue;
     }
     const int D = es.D, nm = es.nm;
-    parallel_ranges(es.ev0.size(), nt, [&](int t, size_t lo, size_t hi) {
-      LineBuf& L = out[t];
+    const EdgeTypeInfo& t = *edge_type_info(es.type);  // (g2ohip_save_g2o has refused the types without a tag)
+    parallel_ranges(es.ev0.size(), nt, [&](int th, size_t lo, size_t hi) {
+      LineBuf& L = out[th];
       L.s.reserve((hi - lo) * 200);
       for (size_t k = lo; k < hi; ++k) {
         const int a = hg.verts[es.ev0[k]].id, b = es.unary ? -1 : hg.verts[es.ev1[k]].id;
         const double* m = es.meas.data() + k * nm;
         const double* I = es.info.data() + k * D * D;
-        if (es.unary) {  // edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58, edge_xy_prior.cpp:59-67,
-                         // edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86 (the parameter id first)
-          L.tag(es.type == G2OHIP_E_SE2_PRIOR      ? "EDGE_PRIOR_SE2"
-                : es.type == G2OHIP_E_SE2_XY_PRIOR ? "EDGE_PRIOR_SE2_XY"
-                : es.type == G2OHIP_E_XY_PRIOR     ? "EDGE_PRIOR_XY"
-                : es.type == G2OHIP_E_XYZ_PRIOR    ? "EDGE_POINTXYZ_PRIOR"
-                                                   : "EDGE_SE3_PRIOR");
-          L.i(a);
-          if (es.type == G2OHIP_E_SE3_PRIOR) L.i(prior_pid[k]);
-          for (int q = 0; q < nm; ++q) L.d(m[q]);
-          for (int r = 0; r < D; ++r) for (int q = r; q < D; ++q) L.d(I[r * D + q]);
-        } else if (is_slam3d_type(es.type)) {  // edge_se3_pointxyz.cpp:88-96 and its siblings: the parameter id first
-          L.tag(es.type == G2OHIP_E_SE3_XYZ         ? "EDGE_SE3_TRACKXYZ"
-                : es.type == G2OHIP_E_SE3_XYZ_DEPTH ? "EDGE_PROJECT_DEPTH"
-                                                    : "EDGE_PROJECT_DISPARITY");
-          L.i(a); L.i(b); L.i(pids[si][k]);
-          for (int q = 0; q < 3; ++q) L.d(m[q]);
-          for (int r = 0; r < 3; ++r) for (int q = r; q < 3; ++q) L.d(I[r * 3 + q]);
-        } else if (es.type == G2OHIP_E_SE3_EXPMAP) {  // types_six_dof_expmap.cpp:131-140: the inverse measurement
+        if (es.type == G2OHIP_E_SE3_EXPMAP) {  // types_six_dof_expmap.cpp:131-140: the inverse measurement
           double w[7];
           se3quat_inverse(m, w);
-          L.tag("EDGE_SE3:EXPMAP"); L.i(a); L.i(b);
+          L.tag(t.tag); L.i(a); L.i(b);
           for (int q = 0; q < 7; ++q) L.d(w[q]);
           for (int r = 0; r < 6; ++r) for (int q = r; q < 6; ++q) L.d(I[r * 6 + q]);
         } else if (es.type == G2OHIP_E_SIM3) {  // types_seven_dof_expmap.cpp:124-137: log of the inverse measurement
@@ -2098,36 +1949,28 @@ int Engine::save(const char* path) {
           set_state_from_est(G2OHIP_V_SIM3, m, c);  // the measurement as the edge holds it: rotation normalised
           sim3_inverse_h(c, g);
           sim3_log_h(g, w);
-          L.tag("EDGE_SIM3:EXPMAP"); L.i(a); L.i(b);
+          L.tag(t.tag); L.i(a); L.i(b);
           for (int q = 0; q < 7; ++q) L.d(w[q]);
           for (int r = 0; r < 7; ++r) for (int q = r; q < 7; ++q) L.d(I[r * 7 + q]);
-        } else if (is_sba_type(es.type)) {  // types_sba.cpp:215-244: the measurement alone (g2ohip_save_g2o has
-                                            // refused a graph whose information is not the identity)
-          L.tag(es.type == G2OHIP_E_PROJECT_P2MC ? "EDGE_PROJECT_P2MC" : "EDGE_PROJECT_P2SC"); L.i(a); L.i(b);
-          for (int q = 0; q < nm; ++q) L.d(m[q]);
-        } else if (is_offset_type(es.type)) {  // edge_se3_offset.cpp:90-100, edge_se2_offset.cpp:86-94: the two ids first
-          L.tag(es.type == G2OHIP_E_SE3_OFFSET ? "EDGE_SE3_OFFSET" : "EDGE_SE2_OFFSET"); L.i(a); L.i(b);
-          L.i(pids[si][2 * k]); L.i(pids[si][2 * k + 1]);
-          for (int q = 0; q < nm; ++q) L.d(m[q]);
-          for (int r = 0; r < D; ++r) for (int q = r; q < D; ++q) L.d(I[r * D + q]);
-        } else if (es.type == G2OHIP_E_PROJECT_XYZ2UV) {  // types_six_dof_expmap.cpp:265-276: the parameter id first
-          L.tag("EDGE_PROJECT_XYZ2UV:EXPMAP"); L.i(a); L.i(b); L.i(pids[si][k]);
-          L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
-        } else if (es.type == G2OHIP_E_V_V_GICP) {  // types_icp.cpp:206-222: pos0 normal0 pos1 normal1, nothing else
-          L.tag("EDGE_V_V_GICP"); L.i(a); L.i(b);
-          for (int q = 0; q < 12; ++q) L.d(m[q]);
-        } else if (es.type == G2OHIP_E_SE2_XY_BEARING) {  // edge_se2_pointxy_bearing.cpp:62-66
-          L.tag("EDGE_BEARING_SE2_XY"); L.i(a); L.i(b); L.d(m[0]); L.d(I[0]);
-        } else if (es.type == G2OHIP_E_SE2_XY) {  // edge_se2_pointxy.cpp:54-61
-          L.tag("EDGE_SE2_XY"); L.i(a); L.i(b);
-          L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
-        } else if (es.type == G2OHIP_E_SE3_PROJECT_XYZ) {  // types_six_dof_expmap.cpp:380-393
+        } else if (es.type == G2OHIP_E_SE3_PROJECT_XYZ) {  // types_six_dof_expmap.cpp:380-393: the intrinsics behind it
           const double* p = es.params.data() + k * 4;
-          L.tag("EDGE_SE3_PROJECT_XYZ:EXPMAP"); L.i(a); L.i(b);
+          L.tag(t.tag); L.i(a); L.i(b);
           L.d(m[0]); L.d(m[1]); L.d(I[0]); L.d(I[1]); L.d(I[3]);
           for (int q = 0; q < 4; ++q) L.d(p[q]);
-        } else {  // edge_se3.cpp:67-75, edge_se2.cpp:55-63: measurement, upper triangle of the information row-wise
-          L.tag(es.type == G2OHIP_E_SE3_QUAT ? "EDGE_SE3:QUAT" : "EDGE_SE2"); L.i(a); L.i(b);
+        } else if (!t.info_upper) {
+          // the measurement alone. types_sba.cpp:215-244 (g2ohip_save_g2o has refused a graph whose information is not
+          // the identity); types_icp.cpp:206-222: pos0 normal0 pos1 normal1
+          L.tag(t.tag); L.i(a); L.i(b);
+          for (int q = 0; q < nm; ++q) L.d(m[q]);
+        } else {
+          // the regular lines: the vertices, the parameter ids, the measurement, the upper triangle of the information
+          // row-wise. edge_se3.cpp:67-75, edge_se2.cpp:55-63, edge_se2_pointxy.cpp:54-61, edge_se2_pointxy_bearing.cpp:
+          // 62-66, edge_se3_offset.cpp:90-100, edge_se2_offset.cpp:86-94, edge_se3_pointxyz.cpp:88-96 and its siblings,
+          // types_six_dof_expmap.cpp:265-276; the priors: edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
+          // edge_xy_prior.cpp:59-67, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86
+          L.tag(t.tag); L.i(a);
+          if (!es.unary) L.i(b);
+          for (int h = 0; h < t.npid; ++h) L.i(pids[si][t.npid * k + h]);
           for (int q = 0; q < nm; ++q) L.d(m[q]);
           for (int r = 0; r < D; ++r) for (int q = r; q < D; ++q) L.d(I[r * D + q]);
         }
@@ -2272,42 +2115,6 @@ int Engine::minimal_state(double* out) {
 }
 
 // ------------------------------------------------------------------ Engine: structure
-// device family of an edge type (host-J types: any endpoint vertex types)
-static int family_of(int etype, int& vtA, int& vtB) {
-  switch (etype) {
-    case G2OHIP_E_SE3_PROJECT_XYZ: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA;
-    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA_STEREO;
-    // CameraParameters edges: the monocular one is FamilyBA's arithmetic with fx = fy = focal_length
-    case G2OHIP_E_PROJECT_XYZ2UV: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA;
-    case G2OHIP_E_PROJECT_XYZ2UVU: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_EXPMAP; return FAM_BA_UVU;
-    case G2OHIP_E_SE3_QUAT: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3;
-    case G2OHIP_E_SE2: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2;
-    case G2OHIP_E_SE2_XY: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY;
-    case G2OHIP_E_SE3_XYZ: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ;
-    case G2OHIP_E_SE3_XYZ_DEPTH: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DEPTH;
-    case G2OHIP_E_SE3_XYZ_DISPARITY: vtA = G2OHIP_V_SE3_QUAT; vtB = G2OHIP_V_XYZ; return FAM_SE3_XYZ_DISPARITY;
-    case G2OHIP_E_SE3_EXPMAP: vtA = vtB = G2OHIP_V_SE3_EXPMAP; return FAM_EXPMAP;
-    case G2OHIP_E_PROJECT_P2MC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_CAM; return FAM_SBA_MONO;
-    case G2OHIP_E_PROJECT_P2SC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_CAM; return FAM_SBA_STEREO;
-    case G2OHIP_E_SE3_OFFSET: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_SE3_OFFSET;
-    case G2OHIP_E_SE2_OFFSET: vtA = vtB = G2OHIP_V_SE2; return FAM_SE2_OFFSET;
-    case G2OHIP_E_SE2_XY_BEARING: vtA = G2OHIP_V_SE2; vtB = G2OHIP_V_XY; return FAM_SE2XY_BEARING;
-    case G2OHIP_E_V_V_GICP: vtA = vtB = G2OHIP_V_SE3_QUAT; return FAM_GICP;
-    case G2OHIP_E_XYZ_VSC: vtA = G2OHIP_V_XYZ; vtB = G2OHIP_V_SE3_QUAT; return FAM_VSC;
-    case G2OHIP_E_SIM3: vtA = vtB = G2OHIP_V_SIM3; return FAM_SIM3;
-    // unary types: vtB = 0 (no second vertex)
-    case G2OHIP_E_SE2_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2;
-    case G2OHIP_E_SE2_XY_PRIOR: vtA = G2OHIP_V_SE2; vtB = 0; return FAM_U_SE2XY;
-    case G2OHIP_E_XY_PRIOR: vtA = G2OHIP_V_XY; vtB = 0; return FAM_U_XY;
-    case G2OHIP_E_SE3_PRIOR: vtA = G2OHIP_V_SE3_QUAT; vtB = 0; return FAM_U_SE3;
-    case G2OHIP_E_XYZ_PRIOR: vtA = G2OHIP_V_XYZ; vtB = 0; return FAM_U_XYZ;
-    case G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE: vtA = G2OHIP_V_SE3_EXPMAP; vtB = 0; return FAM_U_POSE_ONLY;
-    case G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: vtA = G2OHIP_V_SE3_EXPMAP; vtB = 0; return FAM_U_STEREO_POSE_ONLY;
-  }
-  vtA = vtB = 0;
-  return is_hostj_binary(etype) ? FAM_HOSTJ : (is_hostj_unary(etype) ? FAM_U_HOSTJ : FAM_NONE);
-}
-
 // type checks and the vertices that have edges at the level (act: per edge set, per edge, 1 active; an empty list:
 // every edge) (initialize / update_initialization); a unary set checks one vertex
 static int mark_edge_vertices(const HostGraph& hg, const std::vector<std::vector<char>>& act, std::vector<char>& has,
@@ -2315,19 +2122,18 @@ static int mark_edge_vertices(const HostGraph& hg, const std::vector<std::vector
   hostj = unary = false;
   for (size_t si = 0; si < hg.esets.size(); ++si) {
     const HEdgeSet& es = hg.esets[si];
-    int vtA, vtB;
-    const int fam = family_of(es.type, vtA, vtB);
-    if (fam == FAM_NONE) return G2OHIP_ERR_UNSUPPORTED;
-    hostj |= is_hostj_family(fam);
+    const EdgeTypeInfo* t = edge_type_info(es.type);  // (nullptr: a host-J type, on any endpoint vertex types)
+    if (!t && !is_hostj(es.type)) return G2OHIP_ERR_UNSUPPORTED;
+    hostj |= !t;
     const std::vector<char>* on = si < act.size() && !act[si].empty() ? &act[si] : nullptr;
     for (size_t k = 0; k < es.ev0.size(); ++k) {
       const HVertex& a = hg.verts[es.ev0[k]];
-      if (!is_hostj_family(fam) && a.type != vtA)
+      if (t && a.type != t->vtA)
         throw StatusError(G2OHIP_ERR_UNSUPPORTED, "edge type " + std::to_string(es.type) + " on vertex " +
                                                       std::to_string(a.id) + " of vertex type " + std::to_string(a.type));
       if (!es.unary) {
         const HVertex& b = hg.verts[es.ev1[k]];
-        if (!is_hostj_family(fam) && b.type != vtB)
+        if (t && b.type != t->vtB)
           throw StatusError(G2OHIP_ERR_UNSUPPORTED, "edge type " + std::to_string(es.type) + " on vertex " +
                                                         std::to_string(b.id) + " of vertex type " + std::to_string(b.type));
       }
@@ -2538,14 +2344,12 @@ int Engine::eval_edges(int type, bool classify, double* chi2, unsigned char* dep
   HEdgeSet* es = hg.set_of(type);
   if (!es) throw StatusError(G2OHIP_ERR_ARG, "the graph holds no edge of type " + std::to_string(type));
   const size_t si = es - hg.esets.data();
-  int vtA, vtB;
-  const int fam = family_of(type, vtA, vtB);
-  // (EdgeProjectXYZ2UV runs as FAM_BA, but the reference type has no isDepthPositive)
-  if ((depth || check_depth) && (!launch::family_has_depth(fam) || is_camparams_type(type)))
+  const EdgeTypeInfo* t = edge_type_info(type);
+  if ((depth || check_depth) && !(t && t->depth))
     throw StatusError(G2OHIP_ERR_ARG, "edge type " + std::to_string(type) + " has no isDepthPositive()");
   if (classify && ((inlier < 0 && inlier != G2OHIP_LEVEL_KEEP) || (outlier < 0 && outlier != G2OHIP_LEVEL_KEEP)))
     throw StatusError(G2OHIP_ERR_ARG, "classify_edges: a level is >= 0 or G2OHIP_LEVEL_KEEP");
-  if (is_hostj_family(fam) || fam == FAM_NONE)
+  if (!t)
     throw StatusError(G2OHIP_ERR_UNSUPPORTED, "per-edge chi2 of host-Jacobian edges (type " + std::to_string(type) +
                                                   ") is not computed on the device: the host holds their errors itself");
   if (nranks > 1)
@@ -2559,12 +2363,12 @@ int Engine::eval_edges(int type, bool classify, double* chi2, unsigned char* dep
     auto v = std::make_unique<EdgeView>();
     EGroup& g = v->g;
     g.set = (int)si;
-    g.family = fam;
-    g.vtA = vtA;
-    g.vtB = vtB;
+    g.family = t->family;
+    g.vtA = t->vtA;
+    g.vtB = t->vtB;
     g.D = es->D;
-    g.DA = vertex_dim(vtA);
-    g.DB = vtB ? vertex_dim(vtB) : 0;
+    g.DA = vertex_dim(g.vtA);
+    g.DB = g.vtB ? vertex_dim(g.vtB) : 0;
     g.edges.resize(n);
     std::iota(g.edges.begin(), g.edges.end(), 0);
     g.ne = n;
@@ -2589,7 +2393,7 @@ int Engine::eval_edges(int type, bool classify, double* chi2, unsigned char* dep
     V.level.upload(lv, stream);
   }
   timer.begin("classify", stream);
-  launch::classify(fam, group_args(V.g), n, c, stream);
+  launch::classify(V.g.family, group_args(V.g), n, c, stream);
   timer.end(stream);
   std::vector<int> lv;
   long long cnt[3] = {0, 0, 0};
@@ -2676,40 +2480,18 @@ void Engine::fill_group_device(EGroup& g) {
   const int D = g.D, nm = es.nm, gne = g.ne;
   std::vector<int> v0(std::max(gne, 1), 0), v1(std::max(gne, 1), 0);
   const int minfo = D * (D + 1) / 2;
-  int mmeas = g.family == FAM_BA || g.family == FAM_SE2XY
-                  ? 2
-                  : (g.family == FAM_SE3 ? 12
-                     : (g.family == FAM_SE2 || g.family == FAM_BA_STEREO || g.family == FAM_BA_UVU ? 3 : 0));
-  switch (g.family) {  // unary families: the payload k_linearize_unary's family reads (device_types.hpp)
-    case FAM_U_SE2: case FAM_U_XYZ: mmeas = 3; break;
-    case FAM_U_SE2XY: case FAM_U_XY: mmeas = 2; break;
-    case FAM_U_SE3: mmeas = 24; break;
-    case FAM_SE3_XYZ: case FAM_SE3_XYZ_DEPTH: case FAM_SE3_XYZ_DISPARITY: mmeas = 3; break;
-    case FAM_EXPMAP: mmeas = 8; break;              // the measurement as an SE3Quat, padded to a 64-byte record
-    case FAM_U_POSE_ONLY: mmeas = 5; break;         // u v | Xw
-    case FAM_U_STEREO_POSE_ONLY: mmeas = 6; break;  // u_l v u_r | Xw
-    case FAM_SBA_MONO: mmeas = 2; break;
-    case FAM_SBA_STEREO: mmeas = 3; break;
-    case FAM_SE3_OFFSET: mmeas = 12; break;     // Z^-1 as an isometry, as FAM_SE3
-    case FAM_SE2_OFFSET: mmeas = 3; break;      // the inverse measurement, as FAM_SE2
-    case FAM_SE2XY_BEARING: mmeas = 1; break;
-    case FAM_GICP: mmeas = 6; break;            // pos0 | pos1 (the normals stay on the host, for save)
-    case FAM_VSC: mmeas = 3; break;
-    case FAM_SIM3: mmeas = 8; break;            // the measurement as a Sim3, one 64-byte record
-  }
+  // the strides the family's kernels index the measurement and parameter buffers with (EDGE_TYPES, checked against
+  // F::MEAS and F::PAR where the launchers pick the family). Measurement: what the family reads (device_types.hpp).
+  // Parameter record: the BA intrinsics as given (a CameraParameters record expanded: ba_device_params); slam3d: the
+  // inverse offset as an isometry (12), the camera types' fx fy cx cy behind it; the pose-only projections: the
+  // intrinsics (the point Xw ahead of them in the caller's record goes into the measurement payload); EdgeSE3Offset: the
+  // two offsets as isometries [R (9) | t (3)] (24); EdgeSE2Offset: the two offsets x y theta as given (6); Edge_V_V_GICP:
+  // cov0 | cov1 packed upper as given, no record at all in a point-to-plane set. (Host-J groups: no row; the payload is
+  // uploaded by upload_group_payload)
+  const EdgeTypeInfo* t = edge_type_info(es.type);
   const bool gicp_plpl = g.family == FAM_GICP && !es.params.empty();
-  // device parameter record: the BA intrinsics as given (a CameraParameters record expanded: ba_device_params);
-  // slam3d: the inverse offset as an isometry (12), the camera types' fx fy cx cy behind it (FamilySlam3d, device_types.hpp); the pose-only projections: the intrinsics (the
-  // point Xw ahead of them in the caller's record goes into the measurement payload); EdgeSE3Offset: the two offsets as
-  // isometries [R (9) | t (3)] (24); EdgeSE2Offset: the two offsets x y theta as given (6)
-  const int mpar = is_ba_family(g.family) ? ba_device_param_dim(es.type)
-                   : g.family == FAM_SE3_XYZ ? 12
-                   : is_slam3d_family(g.family) ? 16
-                   : is_pose_only_family(g.family) ? edge_param_dim(es.type) - 3
-                   : g.family == FAM_SE3_OFFSET ? 24
-                   : g.family == FAM_SE2_OFFSET ? 6
-                   : gicp_plpl ? 12               // Edge_V_V_GICP plane-to-plane: cov0 | cov1 packed upper, as given
-                   : g.family == FAM_VSC ? 5 : 0;  // Edge_XYZ_VSC: fx fy cx cy baseline, as given
+  const int mmeas = t ? t->dev_meas : 0;
+  const int mpar = !t || (g.family == FAM_GICP && !gicp_plpl) ? 0 : t->dev_par;
   std::vector<double> meas((size_t)std::max(gne, 1) * std::max(mmeas, 1)), info((size_t)std::max(gne, 1) * minfo),
       params(mpar ? (size_t)gne * mpar : 1);
   for (int k = 0; k < gne; ++k) {
@@ -2731,7 +2513,7 @@ void Engine::fill_group_device(EGroup& g) {
     };
     if (is_ba_family(g.family)) {
       for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
-      ba_device_params(es.type, es.params.data() + (size_t)e * edge_param_dim(es.type), params.data() + (size_t)k * mpar);
+      ba_device_params(*t, es.params.data() + (size_t)e * t->np, params.data() + (size_t)k * mpar);
     } else if (g.family == FAM_SE3) {
       iso_inverse_of(m, mo);
     } else if (g.family == FAM_U_SE3) {  // edge_se3_prior.cpp:55-63: Z^-1, then the offset P = fromVectorQT(params)
@@ -2787,14 +2569,14 @@ void Engine::fill_group_device(EGroup& g) {
     } else if (g.family == FAM_SIM3) {  // Sim3(q, t, s), sim3.h:53-57: normalizeRotation (w >= 0, unit)
       set_state_from_est(G2OHIP_V_SIM3, m, mo);
     } else if (is_pose_only_family(g.family)) {  // caller's record Xw fx fy cx cy (bf) -> payload obs | Xw, intrinsics
-      const int np = edge_param_dim(es.type);
+      const int np = t->np;
       const double* p = es.params.data() + (size_t)e * np;
       for (int j = 0; j < nm; ++j) mo[j] = m[j];
       for (int j = 0; j < 3; ++j) mo[nm + j] = p[j];
       for (int j = 3; j < np; ++j) params[(size_t)k * mpar + j - 3] = p[j];
     } else if (is_slam3d_family(g.family)) {  // the offset (x y z qx qy qz qw) -> its inverse [Rp^T | -Rp^T tp]
       for (int j = 0; j < 3; ++j) mo[j] = m[j];
-      const int np = edge_param_dim(es.type);
+      const int np = t->np;
       const double* p = es.params.data() + (size_t)e * np;
       double* po = params.data() + (size_t)k * mpar;
       iso_inverse_of(p, po);
@@ -2812,10 +2594,7 @@ void Engine::fill_group_device(EGroup& g) {
      // record instead of 24 + 32 bytes per edge (G2OHIP_UNIFORM_RECORDS=0 keeps per-edge records, A/B)
     const char* ev = getenv("G2OHIP_UNIFORM_RECORDS");
     g.ue = 0;
-    if ((is_ba_family(g.family) || is_slam3d_family(g.family) || is_pose_only_family(g.family) ||
-         is_sba_family(g.family) || is_offset_family(g.family) || g.family == FAM_SE2XY_BEARING ||
-         g.family == FAM_GICP || g.family == FAM_VSC || g.family == FAM_SIM3) && gne > 1 &&
-        !(ev && atoi(ev) == 0)) {
+    if (t && t->uniform && gne > 1 && !(ev && atoi(ev) == 0)) {
       auto uniform = [&](const std::vector<double>& v, int st) {
         for (int k = 1; k < gne; ++k)
           if (std::memcmp(v.data() + (size_t)k * st, v.data(), sizeof(double) * st) != 0) return false;
@@ -2849,8 +2628,7 @@ void Engine::form_groups(bool filtered, std::vector<EGroup>& out) const {
   out.clear();
   for (size_t si = 0; si < hg.esets.size(); ++si) {
     const HEdgeSet& es = hg.esets[si];
-    int vtA, vtB;
-    const int fam = family_of(es.type, vtA, vtB);
+    const int fam = edge_family(es.type);
     // groups: one per (endpoint vertex type pair) in first-seen order; device families have exactly one
     std::vector<std::pair<int, int>> keys;
     std::vector<std::vector<int>> lists;
@@ -2995,7 +2773,8 @@ void Engine::setup_edges_device() {
     std::vector<int> ptr(num_poses + 1, 0), cv0, cv1;
     std::vector<double> cmeas, cinfo, cpar;
     // per observation: D measurement doubles (2, stereo 3), the packed information, the intrinsics (4, stereo 5)
-    const int cD = g.D, cI = cD * (cD + 1) / 2, cP = ba_device_param_dim(es.type);
+    const EdgeTypeInfo& t = *edge_type_info(es.type);
+    const int cD = g.D, cI = cD * (cD + 1) / 2, cP = t.dev_par;
     cm_e_h.clear();
     for (int i = 0; i < num_poses; ++i) {
       ptr[i + 1] = ptr[i] + (int)lists[i].size();
@@ -3009,7 +2788,7 @@ void Engine::setup_edges_device() {
         for (int c = 0; c < cD; ++c)  // packed upper, column-major: (0,0) (0,1) (1,1) ...
           for (int r = 0; r <= c; ++r) cinfo.push_back(I[r * cD + c]);
         cpar.resize(cpar.size() + cP);
-        ba_device_params(es.type, es.params.data() + (size_t)e * edge_param_dim(es.type), cpar.data() + cpar.size() - cP);
+        ba_device_params(t, es.params.data() + (size_t)e * t.np, cpar.data() + cpar.size() - cP);
       }
     }
     auto nz_i = [](std::vector<int>& v) -> std::vector<int>& { if (v.empty()) v.push_back(0); return v; };
@@ -3292,44 +3071,14 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                       algorithm + ": the device PCG and the matrix-free CGLS take pose blocks of 3 or 6, a Sim3 graph has "
                                   "blocks of 7; use lm_hip_var or lm_hip_fix7_3");
-  if (use_cgls())
-    for (const HEdgeSet& es : hg.esets)
-      if (is_slam3d_type(es.type) && !es.ev0.empty())
-        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
-                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the slam3d "
-                          "landmark edges (edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
-  if (use_cgls())
-    for (const HEdgeSet& es : hg.esets)
-      if (is_sba_type(es.type) && !es.ev0.empty())
-        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
-                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the sba types on "
-                          "a VertexCam (edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
-  if (use_cgls())
-    for (const HEdgeSet& es : hg.esets)
-      if ((is_offset_type(es.type) || es.type == G2OHIP_E_SE2_XY_BEARING) && !es.ev0.empty())
-        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
-                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the offset and "
-                          "bearing edges (edge type " + std::to_string(es.type) + "); use lm_pcg or lm_hip_var");
-  if (use_cgls())
-    for (const HEdgeSet& es : hg.esets)
-      if (is_icp_type(es.type) && !es.ev0.empty())
-        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
-                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the types_icp "
-                          "edges Edge_V_V_GICP / Edge_XYZ_VSC (edge type " + std::to_string(es.type) +
-                          "); use lm_pcg, lm_pcg6_3 or lm_hip_var");
-  if (use_cgls())
-    for (const HEdgeSet& es : hg.esets)
-      if (is_camparams_type(es.type) && !es.ev0.empty())
-        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
-                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take the "
-                          "CameraParameters edges EdgeProjectXYZ2UV / XYZ2UVU (edge type " + std::to_string(es.type) +
-                          "); use lm_pcg6_3 or lm_hip_fix6_3");
-  if (use_cgls())
-    for (const HEdgeSet& es : hg.esets)
-      if (es.type == G2OHIP_E_SE3_EXPMAP && !es.ev0.empty())
-        throw StatusError(G2OHIP_ERR_UNSUPPORTED,
-                          "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take EdgeSE3Expmap "
-                          "(edge type " + std::to_string(es.type) + "); use lm_pcg6_3 or lm_hip_fix6_3");
+  if (use_cgls())  // (CGLS_REFUSALS' order first, the edge sets' second: which of two refused types the message names)
+    for (int c = 1; c < (int)(sizeof CGLS_REFUSALS / sizeof *CGLS_REFUSALS); ++c)
+      for (const HEdgeSet& es : hg.esets)
+        if (const EdgeTypeInfo* t = edge_type_info(es.type); t && t->cgls == c && !es.ev0.empty())
+          throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                            std::string("lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take ") +
+                                CGLS_REFUSALS[c].what + " (edge type " + std::to_string(es.type) + "); use " +
+                                CGLS_REFUSALS[c].instead);
   if (use_cgls() && has_unary_)
     throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                       "lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) does not take unary edges: the "
@@ -5305,18 +5054,23 @@ double Engine::kernel_bytes(const std::string& name) const {
   if (name == "schur_diag") return 2 * npl * pb + local_lm.size() * 9 * 8.0 + (double)num_poses * pd * pd * 8 * 2 +
                                    size_poses * 16.0;
   if (name == "schur_dinv") return local_lm.size() * ((9 + 3) * 8.0 + (9 + 6 + 3) * 8.0);
+  // a group's device parameter record (EDGE_TYPES; 0: none, and the host-J groups)
+  auto dev_par = [&](const EGroup& g) {
+    const EdgeTypeInfo* t = edge_type_info(hg.esets[g.set].type);
+    return t ? t->dev_par : 0;
+  };
   if (name == "linearize") {  // BA groups: edge data read, the Hpl block written (+ both slots, generic path)
     double by = 0;
     for (const EGroup& g : groups)
       // measurement + packed information + intrinsics streamed per edge: 2 + 3 + 4 doubles, stereo 3 + 6 + 5
       if (is_ba_family(g.family)) {
-        const int D = g.D, np = g.family == FAM_BA ? 4 : 5;  // (FAM_BA_UVU: f f cx cy b)
+        const int D = g.D, np = dev_par(g);  // (FAM_BA_UVU: f f cx cy b)
         by += g.ne * ((D + D * (D + 1) / 2 + np) * 8.0 + 8 + (ba_fused ? 0.0 : 9.0 + 27.0) * 8 + ob) +
               (ba_fused ? local_lm.size() * 12 * 8.0 : 0.0);
       } else if (is_slam3d_family(g.family)) {
         // slam3d landmark edges (slot path): measurement 3 + packed information 6 (one record when uniform), the
         // parameter record 12 / 16 (likewise), two vertex indices, the pose slot 27, the point slot 9, the Hpl block
-        const int np = g.family == FAM_SE3_XYZ ? 12 : 16;
+        const int np = dev_par(g);
         by += g.ne * ((3 + ((g.ue & 1) ? 0 : 6) + ((g.ue & 2) ? 0 : np)) * 8.0 + 8 + (27.0 + 9.0) * 8 + pb);
       } else if (is_sba_family(g.family)) {
         // sba types (slot path): measurement D + packed information (one record when uniform), two vertex indices, the
@@ -5333,9 +5087,7 @@ double Engine::kernel_bytes(const std::string& name) const {
     double by = (double)so_.nlm * (4 + 4 + 1 + 2.0 * so_.ld * 8);
     for (int gi : so_.group_of) {
       const EGroup& g = groups[gi];
-      const int np = g.family == FAM_BA ? 4 : g.family == FAM_BA_STEREO || g.family == FAM_BA_UVU ? 5
-                     : g.family == FAM_SE3_XYZ ? 12
-                     : is_slam3d_family(g.family) ? 16 : 0;
+      const int np = dev_par(g);
       by += g.ne * (8.0 + (g.vtB ? 4.0 : 0.0) + g.D * 8.0 + ((g.ue & 1) ? 0.0 : g.D * (g.D + 1) / 2 * 8.0) +
                     ((g.ue & 2) ? 0.0 : np * 8.0));
     }
@@ -5359,9 +5111,8 @@ double Engine::kernel_bytes(const std::string& name) const {
       if (is_unary_family(g.family)) {
         // (the pose-only projections: the point Xw behind the observation; their intrinsics are one shared record
         // in the usual graph and not counted)
-        const int mm = g.family == FAM_U_SE3 ? 24
-                       : g.family == FAM_U_HOSTJ ? g.payload_stride()
-                       : hg.esets[g.set].nm + (is_pose_only_family(g.family) ? 3 : 0);
+        const EdgeTypeInfo* t = edge_type_info(hg.esets[g.set].type);
+        const int mm = t ? t->dev_meas : g.payload_stride();
         by += g.ne * (8.0 + (mm + g.D * (g.D + 1) / 2 + vertex_state_stride(g.vtA) + g.DA * (g.DA + 1) / 2 + g.DA) * 8.0);
       }
     return by;

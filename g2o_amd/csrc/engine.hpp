@@ -22,11 +22,8 @@
 namespace g2ohip {
 
 constexpr int NVT = 8;  // vertex type codes 1..7 (G2OHIP_V_*)
-int vertex_dim(int vtype);
 int vertex_est_dim(int vtype);
 int vertex_state_stride(int vtype);
-int edge_dim(int etype);
-int edge_meas_dim(int etype);
 
 // OptimizableGraph mirror (host, authoritative for I/O; the device copy is authoritative
 // during optimize()).

@@ -27,6 +27,7 @@
 #include "common.hpp"
 #include "device_types.hpp"
 #include "device_util.hpp"
+#include "family_dispatch.hpp"
 #include "kernels.hpp"
 
 namespace g2ohip {
@@ -1976,102 +1977,6 @@ namespace launch {
 
 static EdgeData mk(const EdgeArgs& a) {
   return EdgeData{a.v0, a.v1, a.meas, a.info, a.params, a.s0, a.s1, a.rk, a.rk_delta, a.ue};
-}
-
-// host-Jacobian families: runtime (D, DA, DB) -> FamilyHostJ<D, DA, DB> (vertex dims 2, 3, 6 or 7, D = 1..7)
-template <int D, int DA, class Fn>
-static void hj_b(int DB, Fn& fn) {
-  if (DB == 2) fn(FamilyHostJ<D, DA, 2>{});
-  else if (DB == 3) fn(FamilyHostJ<D, DA, 3>{});
-  else if (DB == 6) fn(FamilyHostJ<D, DA, 6>{});
-  else if (DB == 7) fn(FamilyHostJ<D, DA, 7>{});
-  else throw std::runtime_error("host-Jacobian edge: vertex dimension must be 2, 3, 6 or 7");
-}
-template <int D, class Fn>
-static void hj_a(int DA, int DB, Fn& fn) {
-  if (DA == 2) hj_b<D, 2>(DB, fn);
-  else if (DA == 3) hj_b<D, 3>(DB, fn);
-  else if (DA == 6) hj_b<D, 6>(DB, fn);
-  else if (DA == 7) hj_b<D, 7>(DB, fn);
-  else throw std::runtime_error("host-Jacobian edge: vertex dimension must be 2, 3, 6 or 7");
-}
-// unary families; host-Jacobian ones: runtime (D, DA) -> FamilyHostJUnary<D, DA>
-template <int D, class Fn>
-static void hju_a(int DA, Fn& fn) {
-  if (DA == 2) fn(FamilyHostJUnary<D, 2>{});
-  else if (DA == 3) fn(FamilyHostJUnary<D, 3>{});
-  else if (DA == 6) fn(FamilyHostJUnary<D, 6>{});
-  else if (DA == 7) fn(FamilyHostJUnary<D, 7>{});
-  else throw std::runtime_error("host-Jacobian unary edge: vertex dimension must be 2, 3, 6 or 7");
-}
-template <class Fn>
-static void unary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
-  switch (family) {
-    case FAM_U_SE2: fn(FamilyUnarySE2{}); break;
-    case FAM_U_SE2XY: fn(FamilyUnarySE2XY{}); break;
-    case FAM_U_XY: fn(FamilyUnaryXY{}); break;
-    case FAM_U_SE3: fn(FamilyUnarySE3{}); break;
-    case FAM_U_XYZ: fn(FamilyUnaryXYZ{}); break;
-    case FAM_U_POSE_ONLY: fn(FamilyPoseOnly{}); break;
-    case FAM_U_STEREO_POSE_ONLY: fn(FamilyStereoPoseOnly{}); break;
-    case FAM_U_HOSTJ:
-      switch (a.D) {
-        case 1: hju_a<1>(a.DA, fn); break;
-        case 2: hju_a<2>(a.DA, fn); break;
-        case 3: hju_a<3>(a.DA, fn); break;
-        case 4: hju_a<4>(a.DA, fn); break;
-        case 5: hju_a<5>(a.DA, fn); break;
-        case 6: hju_a<6>(a.DA, fn); break;
-        case 7: hju_a<7>(a.DA, fn); break;
-        default: throw std::runtime_error("host-Jacobian unary edge: error dimension must be 1..7");
-      }
-      break;
-    default: throw std::runtime_error("unknown unary edge family");
-  }
-}
-template <class Fn>
-static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn);
-// every family, for the kernels that only need F::error (chi2): binary or unary
-template <class Fn>
-static void family_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
-  if (is_unary_family(family)) unary_dispatch(family, a, fn);
-  else binary_dispatch(family, a, fn);
-}
-template <class Fn>
-static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
-  switch (family) {
-    case FAM_BA: fn(FamilyBA{}); break;
-    case FAM_BA_STEREO: fn(FamilyStereo{}); break;
-    case FAM_BA_UVU: fn(FamilyUVU{}); break;
-    case FAM_SE3: fn(FamilySE3{}); break;
-    case FAM_SE2: fn(FamilySE2{}); break;
-    case FAM_SE2XY: fn(FamilySE2XY{}); break;
-    case FAM_SE3_XYZ: fn(FamilySE3XYZ{}); break;
-    case FAM_SE3_XYZ_DEPTH: fn(FamilySE3XYZDepth{}); break;
-    case FAM_SE3_XYZ_DISPARITY: fn(FamilySE3XYZDisparity{}); break;
-    case FAM_EXPMAP: fn(FamilyExpmap{}); break;
-    case FAM_SBA_MONO: fn(FamilySBAMono{}); break;
-    case FAM_SBA_STEREO: fn(FamilySBAStereo{}); break;
-    case FAM_SE3_OFFSET: fn(FamilySE3Offset{}); break;
-    case FAM_SE2_OFFSET: fn(FamilySE2Offset{}); break;
-    case FAM_SE2XY_BEARING: fn(FamilySE2XYBearing{}); break;
-    case FAM_GICP: fn(FamilyGICP{}); break;
-    case FAM_VSC: fn(FamilyVSC{}); break;
-    case FAM_SIM3: fn(FamilySim3{}); break;
-    case FAM_HOSTJ:
-      switch (a.D) {
-        case 1: hj_a<1>(a.DA, a.DB, fn); break;
-        case 2: hj_a<2>(a.DA, a.DB, fn); break;
-        case 3: hj_a<3>(a.DA, a.DB, fn); break;
-        case 4: hj_a<4>(a.DA, a.DB, fn); break;
-        case 5: hj_a<5>(a.DA, a.DB, fn); break;
-        case 6: hj_a<6>(a.DA, a.DB, fn); break;
-        case 7: hj_a<7>(a.DA, a.DB, fn); break;
-        default: throw std::runtime_error("host-Jacobian edge: error dimension must be 1..7");
-      }
-      break;
-    default: throw std::runtime_error("unknown edge family");
-  }
 }
 
 void error(int family, const EdgeArgs& a, int ne, double* chi, hipStream_t s) {

@@ -5,32 +5,10 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "edge_types.hpp"
+
 namespace g2ohip {
 
-enum Family {
-  FAM_NONE = 0, FAM_BA = 1, FAM_SE3 = 2, FAM_SE2 = 3, FAM_HOSTJ = 4, FAM_SE2XY = 5, FAM_BA_STEREO = 6,
-  // slam3d landmark edges (VertexSE3 pose, point): EdgeSE3PointXYZ, ...Depth, ...Disparity
-  FAM_SE3_XYZ = 7, FAM_SE3_XYZ_DEPTH = 8, FAM_SE3_XYZ_DISPARITY = 9,
-  // EdgeSE3Expmap between two VertexSE3Expmap cameras
-  FAM_EXPMAP = 10,
-  // sba types (point, VertexCam): EdgeProjectP2MC, EdgeProjectP2SC
-  FAM_SBA_MONO = 11, FAM_SBA_STEREO = 12,
-  // offset and bearing edges: EdgeSE3Offset, EdgeSE2Offset (two poses, two sensor offsets), EdgeSE2PointXYBearing
-  FAM_SE3_OFFSET = 13, FAM_SE2_OFFSET = 14, FAM_SE2XY_BEARING = 15,
-  // unary families (BaseUnaryEdge: one vertex, EdgeArgs::v1 / s1 null, DB = 0)
-  FAM_U_SE2 = 16, FAM_U_SE2XY = 17, FAM_U_XY = 18, FAM_U_SE3 = 19, FAM_U_XYZ = 20, FAM_U_HOSTJ = 21,
-  // pose-only projections on a VertexSE3Expmap camera: EdgeSE3ProjectXYZOnlyPose, EdgeStereoSE3ProjectXYZOnlyPose
-  FAM_U_POSE_ONLY = 22, FAM_U_STEREO_POSE_ONLY = 23,
-  // EdgeProjectXYZ2UVU (point, VertexSE3Expmap camera, a CameraParameters record): FamilyUVU. A binary family, as
-  // FAM_BA_STEREO; EdgeProjectXYZ2UV runs as FAM_BA with the record f f cx cy
-  FAM_BA_UVU = 24,
-  // Edge_V_V_GICP between two VertexSE3 (types_icp): FamilyGICP, point-to-plane or plane-to-plane per edge set
-  FAM_GICP = 25,
-  // Edge_XYZ_VSC (point, VertexSCam = a VertexSE3 camera): FamilyVSC, the landmark first as in the BA families
-  FAM_VSC = 26,
-  // EdgeSim3 between two VertexSim3Expmap (types/sim3): FamilySim3, linearized by k_linearize_sim3
-  FAM_SIM3 = 27
-};
 // the fused landmark-major assembly's families (point, VertexSE3Expmap camera)
 inline bool is_ba_family(int f) { return f == FAM_BA || f == FAM_BA_STEREO || f == FAM_BA_UVU; }
 inline bool is_unary_family(int f) { return f >= FAM_U_SE2 && f <= FAM_U_STEREO_POSE_ONLY; }
@@ -38,9 +16,6 @@ inline bool is_pose_only_family(int f) { return f == FAM_U_POSE_ONLY || f == FAM
 inline bool is_hostj_family(int f) { return f == FAM_HOSTJ || f == FAM_U_HOSTJ; }
 inline bool is_slam3d_family(int f) { return f >= FAM_SE3_XYZ && f <= FAM_SE3_XYZ_DISPARITY; }
 inline bool is_sba_family(int f) { return f == FAM_SBA_MONO || f == FAM_SBA_STEREO; }
-inline bool is_offset_family(int f) { return f == FAM_SE3_OFFSET || f == FAM_SE2_OFFSET; }
-// the families whose second vertex is the landmark (structure-only, the SE2 / SE3 landmark edges)
-inline bool is_lm_second_family(int f) { return is_slam3d_family(f) || f == FAM_SE2XY || f == FAM_SE2XY_BEARING; }
 
 struct EdgeArgs {
   const int* v0;
@@ -65,14 +40,13 @@ void error(int family, const EdgeArgs& a, int ne, double* chi, hipStream_t s);
 // depth test, bad edges, summed from the per-block partials in part (3 per block of classify_blocks(ne))
 struct ClassifyArgs {
   double* chi;
-  unsigned char* depth;  // nullptr: not wanted (only the projection families have it: family_has_depth)
+  unsigned char* depth;  // nullptr: not wanted (only the projection families have it: EdgeTypeInfo::depth)
   int* level;
   double chi_max;
   int check_depth, inlier, outlier;
   long long* part;
   long long* counts;
 };
-bool family_has_depth(int family);
 int classify_blocks(int ne);
 void classify(int family, const EdgeArgs& a, int ne, const ClassifyArgs& c, hipStream_t s);
 // off_dst: destination of each edge's off-diagonal block, an offset into off_base (the Hessian) or, with bit 62

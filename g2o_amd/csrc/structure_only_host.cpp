@@ -74,7 +74,12 @@ void Engine::so_build_list() {
     fixed.push_back(v.fixed ? 1 : 0);
   }
   L.nlm = (int)local.size();
-  // the landmark end of each group: v0 for the BA and sba families, Edge_XYZ_VSC and the point priors, v1 for slam3d, SE2-XY and the bearing edge
+  // the landmark end of each group (EdgeTypeInfo::lm): v0 for the BA and sba types, Edge_XYZ_VSC and the point priors, v1
+  // for slam3d, SE2-XY and the bearing edge; LM_NONE: the other types and the host-J ones
+  auto lm_side = [&](const EGroup& g) {
+    const EdgeTypeInfo* t = edge_type_info(hg.esets[g.set].type);
+    return t ? t->lm : LM_NONE;
+  };
   std::vector<int> cnt(L.nlm + 1, 0);
   std::vector<int> gslot(groups.size(), -1);
   auto lm_end = [&](const EGroup& g, int k) {  // vertex index of the edge's marginalised endpoint(s): (a, b), -1 none
@@ -85,9 +90,7 @@ void Engine::so_build_list() {
   };
   for (size_t gi = 0; gi < groups.size() && L.nlm; ++gi) {
     const EGroup& g = groups[gi];
-    const bool lm_first = is_ba_family(g.family) || g.family == FAM_U_XYZ ||
-                          g.family == FAM_U_XY || is_sba_family(g.family) || g.family == FAM_VSC;
-    const bool lm_second = is_lm_second_family(g.family);
+    const bool lm_first = lm_side(g) == LM_V0, lm_second = lm_side(g) == LM_V1;
     for (int k = 0; k < g.ne; ++k) {
       const auto [a, b] = lm_end(g, k);
       if (a < 0 && b < 0) continue;
@@ -112,7 +115,7 @@ void Engine::so_build_list() {
   std::vector<int> fill(cnt.begin(), cnt.end() - 1);
   for (int gi : L.group_of) {
     const EGroup& g = groups[gi];
-    const bool lm_first = !is_lm_second_family(g.family);
+    const bool lm_first = lm_side(g) == LM_V0;
     for (int k = 0; k < g.ne; ++k) {
       const auto [a, b] = lm_end(g, k);
       const int v = lm_first ? a : b;
@@ -168,7 +171,7 @@ int Engine::structure_only_calc(int n, const int* ids, int num_iters, int num_ma
   std::memset(sg.data(), 0, sizeof(launch::SoGroup) * sg.size());
   for (size_t k = 0; k < L.group_of.size(); ++k) {
     const EGroup& g = groups[L.group_of[k]];
-    const bool lm_first = !is_lm_second_family(g.family);
+    const bool lm_first = edge_type_info(hg.esets[g.set].type)->lm == LM_V0;  // (a listed group has a landmark end)
     launch::SoGroup& o = sg[k];
     o.vo = is_unary_family(g.family) ? nullptr : (lm_first ? g.v1.get() : g.v0.get());
     const int vto = lm_first ? g.vtB : g.vtA;
