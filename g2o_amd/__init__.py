@@ -88,6 +88,12 @@ ICP_EDGE_TAGS = {E_V_V_GICP: "EDGE_V_V_GICP"}
 V_SIM3 = 7
 E_SIM3 = 27
 SIM3_TAGS = {"vertex": "VERTEX_SIM3:EXPMAP", "edge": "EDGE_SIM3:EXPMAP"}
+# EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ (G2OHIP_E_SIM3_PROJECT_XYZ, ..._INVERSE_XYZ): v0 a fixed V_XYZ point, v1 a
+# V_SIM3; meas [n, 2] u v, info [n, 2, 2], params None: the intrinsics are camera 1 (inverse: camera 2) of v1,
+# SparseOptimizer.set_sim3_cameras. SIM3_PROJECT_TAGS: their .g2o tags (load(sim3=True, sim3_project=True))
+E_SIM3_PROJECT, E_SIM3_PROJECT_INVERSE = 28, 29
+SIM3_PROJECT_TAGS = {E_SIM3_PROJECT: "EDGE_PROJECT_SIM3_XYZ:EXPMAP",
+                     E_SIM3_PROJECT_INVERSE: "EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP"}
 
 
 # EdgeGICP::prec0 / cov0 in numpy, and the packed form of the covariances (ValueError on a normal parallel to (0,1,0))
@@ -122,6 +128,7 @@ LOAD_OFFSET = 16
 LOAD_CAMERAPARAMS = 32
 LOAD_ICP = 64
 LOAD_SIM3 = 128
+LOAD_SIM3_PROJECT = 256
 
 # robust kernels (G2OHIP_RK_*, robust_kernel_impl.cpp)
 RK = {"none": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "GemanMcClure": 4, "Welsch": 5, "Fair": 6, "Tukey": 7,
@@ -151,6 +158,7 @@ EXPORTS = [
     "g2ohip_dogleg_next_delta", "g2ohip_structure_only_calc",
     "g2ohip_set_edge_levels", "g2ohip_get_edge_levels", "g2ohip_initialize_level", "g2ohip_edge_chi2",
     "g2ohip_classify_edges", "g2ohip_set_pair_major", "g2ohip_pair_major_info", "g2ohip_set_sim3_fix_scale",
+    "g2ohip_set_sim3_cameras",
 ]
 
 # G2OHIP_LEVEL_KEEP: classify_edges leaves the level of the edges on that side as it is
@@ -248,6 +256,7 @@ def lib() -> C.CDLL:
         "g2ohip_set_pair_major": ([P, I], I),
         "g2ohip_pair_major_info": ([P, P], I),
         "g2ohip_set_sim3_fix_scale": ([P, I], I),
+        "g2ohip_set_sim3_cameras": ([P, I, P, P, P], I),
         "g2ohip_dogleg_state": ([P, P, I], I),
         "g2ohip_dogleg_blend": ([D, D, D, D, D, D, P], I),
         "g2ohip_dogleg_next_delta": ([D, D, D], D),
@@ -435,7 +444,7 @@ class SparseOptimizer:
         par = None if es.params is None else np.ascontiguousarray(es.params, np.float64)
         pd = synth.PARAM_DIM.get(es.etype)
         md, D = synth.MEAS_DIM.get(es.etype), synth.ERR_DIM.get(es.etype)
-        if es.etype in (E_V_V_GICP, E_XYZ_VSC, E_SIM3):  # the C side reads n * md and n * D * D doubles
+        if es.etype in (E_V_V_GICP, E_XYZ_VSC, E_SIM3, E_SIM3_PROJECT, E_SIM3_PROJECT_INVERSE):  # the C side reads n * md and n * D * D doubles
             if meas is None or meas.size != len(v0) * md:
                 raise G2OHipError(f"add_edges: edge type {es.etype} takes {md} measurement values per edge, got "
                                   f"{0 if meas is None else meas.size} for {len(v0)} edges")
@@ -497,7 +506,7 @@ class SparseOptimizer:
 
     def load(self, path: str, marginalize_xyz: bool = True, unary: bool = False, slam3d: bool = False,
              expmap: bool = False, sba: bool = False, offset: bool = False, camparams: bool = False,
-             icp: bool = False, sim3: bool = False):
+             icp: bool = False, sim3: bool = False, sim3_project: bool = False):
         """OptimizableGraph::load; unary=True also reads the prior tags (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY,
         EDGE_PRIOR_XY, EDGE_POINTXYZ_PRIOR, EDGE_SE3_PRIOR + PARAMS_SE3OFFSET), slam3d=True the 3D landmark tags
         (VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ, EDGE_PROJECT_DEPTH, EDGE_PROJECT_DISPARITY + PARAMS_SE3OFFSET,
@@ -506,10 +515,12 @@ class SparseOptimizer:
         EDGE_BEARING_SE2_XY + PARAMS_SE3OFFSET, PARAMS_SE2OFFSET), camparams=True g2o's own BA tags
         (EDGE_PROJECT_XYZ2UV:EXPMAP + PARAMS_CAMERAPARAMETERS), icp=True EDGE_V_V_GICP (point-to-plane, the information
         Edge_V_V_GICP::read builds; a normal0 parallel to (0,1,0) fails the load), sim3=True VERTEX_SIM3:EXPMAP and
-        EDGE_SIM3:EXPMAP; all are skipped otherwise."""
+        EDGE_SIM3:EXPMAP, sim3_project=True (with sim3) EDGE_PROJECT_SIM3_XYZ:EXPMAP and
+        EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP, whose points must end up fixed (marginalize_xyz=False and FIX lines); all
+        are skipped otherwise."""
         flags = ((LOAD_UNARY if unary else 0) | (LOAD_SLAM3D if slam3d else 0) | (LOAD_EXPMAP if expmap else 0) |
                  (LOAD_SBA if sba else 0) | (LOAD_OFFSET if offset else 0) | (LOAD_CAMERAPARAMS if camparams else 0) |
-                 (LOAD_ICP if icp else 0) | (LOAD_SIM3 if sim3 else 0))
+                 (LOAD_ICP if icp else 0) | (LOAD_SIM3 if sim3 else 0) | (LOAD_SIM3_PROJECT if sim3_project else 0))
         _check(lib().g2ohip_load_g2o_ex(self.h, path.encode(), int(marginalize_xyz), flags), "load")
 
     def num_vertices(self) -> int:
@@ -541,6 +552,21 @@ class SparseOptimizer:
         column 6, as the reference's numeric ones do. H(6, 6) then holds lambda alone: gn_* and dl_* on such a graph
         are not positive definite."""
         _check(lib().g2ohip_set_sim3_fix_scale(self.h, int(bool(on))), "set_sim3_fix_scale")
+
+    def set_sim3_cameras(self, ids, cam1=None, cam2=None):
+        """VertexSim3Expmap's two pinhole cameras for the V_SIM3 vertices ``ids``: cam1 / cam2 [n, 4] fx fy cx cy (one
+        row is taken for every id), None leaves that camera as it is. E_SIM3_PROJECT reads camera 1 of its Sim3 vertex,
+        E_SIM3_PROJECT_INVERSE camera 2; both default to 1 1 0 0 and camera 1 is what a VERTEX_SIM3:EXPMAP line holds."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), np.int32)
+
+        def rows(c):
+            if c is None:
+                return None
+            c = np.asarray(c, np.float64)
+            return np.ascontiguousarray(np.broadcast_to(c, (len(ids), 4)) if c.ndim == 1 else c.reshape(len(ids), 4))
+
+        c1, c2 = rows(cam1), rows(cam2)
+        _check(lib().g2ohip_set_sim3_cameras(self.h, len(ids), _p(ids), _p(c1), _p(c2)), "set_sim3_cameras")
 
     def pair_major_info(self) -> dict:
         """After a structure build: whether it is pair-major, and its pairs and chunks."""

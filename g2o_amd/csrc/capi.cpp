@@ -112,7 +112,7 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz) {
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags) {
   if (!g || !path || (flags & ~(G2OHIP_LOAD_UNARY | G2OHIP_LOAD_SLAM3D | G2OHIP_LOAD_EXPMAP | G2OHIP_LOAD_SBA |
                                     G2OHIP_LOAD_OFFSET | G2OHIP_LOAD_CAMERAPARAMS | G2OHIP_LOAD_ICP |
-                                    G2OHIP_LOAD_SIM3))) return G2OHIP_ERR_ARG;
+                                    G2OHIP_LOAD_SIM3 | G2OHIP_LOAD_SIM3_PROJECT))) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->load(path, marginalize_xyz, flags); });
 }
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
@@ -225,6 +225,10 @@ int g2ohip_set_pair_major(g2ohip_graph* g, int enable) {
 int g2ohip_set_sim3_fix_scale(g2ohip_graph* g, int on) {
   if (!g) return G2OHIP_ERR_ARG;
   return guarded([&] { return g->e->set_sim3_fix_scale(on); });
+}
+int g2ohip_set_sim3_cameras(g2ohip_graph* g, int n, const int* ids, const double* cam1, const double* cam2) {
+  if (!g) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->set_sim3_cameras(n, ids, cam1, cam2); });
 }
 int g2ohip_pair_major_info(g2ohip_graph* g, int* out) {
   if (!g) return G2OHIP_ERR_ARG;

@@ -12,6 +12,7 @@
 //   EdgeSE2Offset      types/slam2d/edge_se2_offset.cpp:102-106, parameter_se2_offset.cpp:76-86 (no analytic Jacobian)
 //   EdgeSE2PointXYBearing  types/slam2d/edge_se2_pointxy_bearing.h:43-50 (no analytic Jacobian)
 //   Edge_V_V_GICP      types/icp/types_icp.h:161-238, types_icp.cpp:49-57, 163-203
+//   EdgeSim3, EdgeSim3ProjectXYZ, EdgeInverseSim3ProjectXYZ  types/sim3/types_seven_dof_expmap.h:110-180, sim3.h
 //   unary priors       types/slam2d/edge_se2_prior.h:39-77, edge_se2_xyprior.h:39-71, edge_xy_prior.h,
 //                      types/slam3d/edge_se3_prior.cpp:89-102 (isometry3d_gradients.h:265-325), edge_xyz_prior.cpp:63-70
 //   oplus             types_six_dof_expmap.h:97-100 (SE3Quat::exp * T, se3quat.h:217-257),
@@ -1892,6 +1893,82 @@ struct FamilySim3 {
     double RE[9], tE[3], sE, sC;
     error_transform<false>(d, e, RE, tE, sE, nullptr, nullptr, sC);
     sim3_log<false>(RE, tE, sE, err, nullptr);
+  }
+};
+
+// ---- EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ (types_seven_dof_expmap.h:141-180): v0 = the point [3], v1 = S, a
+// Sim3 [8]; meas u v, info packed 3, params fx fy cx cy = camera 1 (INV: camera 2) of the edge's Sim3 vertex as the host
+// holds it (one shared record when EdgeData::ue bit 1 is set). With g = S (INV: S.inverse(), the constructor's
+// normalising inverse = sim3_inv) and x = g.map(p) = s (r p) + t: error = obs - (x.xy / x.z * f + c), rounded operation by
+// operation as the reference's. The family has no linearize(): the point is fixed in every graph that initialises, so
+// k_linearize_sim3_project (kernels.hip) takes jac_pose alone, the exact first derivatives under oplus exp(u) S with
+// P = [[fx/z, 0, -fx x/z^2], [0, fy/z, -fy y/z^2]] at x and R = toRotationMatrix(q_g):
+//   forward  Jj = -P [ -[x]x | I | x ]        inverse  Jj = -P s R [ [p]x | -I | -p ]
+// EdgeData::ue bit 3: the vertices' _fix_scale (column 6 of Jj is zero; applied by the kernel). ----
+template <bool INV>
+struct FamilySim3Project {
+  static constexpr int D = 2, DA = 3, DB = 7, MEAS = 2, INFO = 3, PAR = 4;
+  // g as (q, s) and the mapped point x; pv: the point
+  DI static void map(const EdgeData& d, int e, double* q, double& s, double* pv, double* x) {
+#pragma clang fp contract(off)
+    double t[3];
+    if (INV) {
+      double qs[4], ts[3], ss;
+      sim3_load(d.s1 + (size_t)d.v1[e] * 8, qs, ts, ss);
+      sim3_inv(qs, ts, ss, q, t, s);
+    } else {
+      sim3_load(d.s1 + (size_t)d.v1[e] * 8, q, t, s);
+    }
+    const double* p = d.s0 + (size_t)d.v0[e] * 3;
+    pv[0] = p[0]; pv[1] = p[1]; pv[2] = p[2];
+    double rp[3];
+    qrot(q, pv, rp);
+    x[0] = s * rp[0] + t[0]; x[1] = s * rp[1] + t[1]; x[2] = s * rp[2] + t[2];
+  }
+  DI static void residual(const double* K, const double* x, const double* m, double* err) {
+#pragma clang fp contract(off)
+    err[0] = m[0] - (x[0] / x[2] * K[0] + K[2]);
+    err[1] = m[1] - (x[1] / x[2] * K[1] + K[3]);
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double q[4], s, pv[3], x[3];
+    map(d, e, q, s, pv, x);
+    residual(param_rec(d, e, PAR), x, d.meas + (size_t)e * MEAS, err);
+  }
+  // the error and B = Jj, 2 x 7 row-major in (omega, upsilon, sigma) order
+  DI static void jac_pose(const EdgeData& d, int e, double* err, double* B) {
+    double q[4], s, pv[3], x[3];
+    map(d, e, q, s, pv, x);
+    const double* K = param_rec(d, e, PAR);
+    residual(K, x, d.meas + (size_t)e * MEAS, err);
+    const double iz = 1.0 / x[2];
+    // -P, rows (a0, 0, a2) and (0, b1, b2)
+    const double a0 = -K[0] * iz, a2 = K[0] * x[0] * iz * iz, b1 = -K[1] * iz, b2 = K[1] * x[1] * iz * iz;
+    double G[21];  // d x / d u, 3 x 7 row-major
+    if (INV) {
+      double R[9];
+      quat_to_R(q[0], q[1], q[2], q[3], R);
+      // [ [p]x | -I | -p ], then s R in front
+      const double C[21] = {0,      -pv[2], pv[1],  -1, 0,  0,  -pv[0],
+                            pv[2],  0,      -pv[0], 0,  -1, 0,  -pv[1],
+                            -pv[1], pv[0],  0,      0,  0,  -1, -pv[2]};
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 7; ++c)
+          G[r * 7 + c] = s * (R[r * 3] * C[c] + R[r * 3 + 1] * C[7 + c] + R[r * 3 + 2] * C[14 + c]);
+    } else {
+      const double C[21] = {0,     x[2],  -x[1], 1, 0, 0, x[0],
+                            -x[2], 0,     x[0],  0, 1, 0, x[1],
+                            x[1],  -x[0], 0,     0, 0, 1, x[2]};
+#pragma unroll
+      for (int i = 0; i < 21; ++i) G[i] = C[i];
+    }
+#pragma unroll
+    for (int c = 0; c < 7; ++c) {
+      B[c] = a0 * G[c] + a2 * G[14 + c];
+      B[7 + c] = b1 * G[7 + c] + b2 * G[14 + c];
+    }
   }
 };
 

@@ -1,5 +1,5 @@
 // What the host knows about each device edge type, in one table: EDGE_TYPES has one row per G2OHIP_E_* code the
-// device linearizes itself (1-3, 5-27). The host-Jacobian types (G2OHIP_E_HOSTJ*, any D and any endpoints) are no rows:
+// device linearizes itself (1-3, 5-29). The host-Jacobian types (G2OHIP_E_HOSTJ*, any D and any endpoints) are no rows:
 // their facts follow from the code (hostj_dim). The launchers check the rows against the device families at compile
 // time (family_dispatch.hpp), so a stride here cannot drift from the one a kernel indexes with.
 #pragma once
@@ -30,6 +30,9 @@ enum Family {
   FAM_VSC = 26,
   // EdgeSim3 between two VertexSim3Expmap (types/sim3): FamilySim3, linearized by k_linearize_sim3
   FAM_SIM3 = 27,
+  // EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ (point, VertexSim3Expmap): FamilySim3Project<false> / <true>,
+  // linearized by k_linearize_sim3_project (the Sim3 side alone: the point is fixed in every graph that initialises)
+  FAM_SIM3_PROJECT = 28, FAM_SIM3_PROJECT_INVERSE = 29,
   FAM_COUNT
 };
 
@@ -144,6 +147,12 @@ constexpr EdgeTypeInfo TABLE[] = {
      LM_V0, Y, N,    NOTAG, 0, 0, N,  CGLS_ICP},
     {G2OHIP_E_SIM3, FAM_SIM3, SIM3, SIM3,                 7, 8, 0, 8, 0,  // a Sim3: tx ty tz qx qy qz qw s
      LM_NONE, Y, N,  "EDGE_SIM3:EXPMAP", G2OHIP_LOAD_SIM3, 0, Y,  CGLS_OK},  // (the line: log of the inverse, 7 values)
+    // the Sim3 projections: no caller record; the device record is camera 1 (inverse: camera 2) of the edge's Sim3 vertex
+    // (CGLS: blocks of 7 are refused before the per-type check)
+    {G2OHIP_E_SIM3_PROJECT_XYZ, FAM_SIM3_PROJECT, XYZ, SIM3,  2, 2, 0, 2, 4,
+     LM_NONE, Y, N,  "EDGE_PROJECT_SIM3_XYZ:EXPMAP", G2OHIP_LOAD_SIM3_PROJECT, 0, Y,  CGLS_OK},
+    {G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ, FAM_SIM3_PROJECT_INVERSE, XYZ, SIM3,  2, 2, 0, 2, 4,
+     LM_NONE, Y, N,  "EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP", G2OHIP_LOAD_SIM3_PROJECT, 0, Y,  CGLS_OK},
 };
 constexpr bool sorted_and_complete() {
   bool seen[FAM_COUNT] = {};

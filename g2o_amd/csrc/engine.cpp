@@ -1266,7 +1266,10 @@ int Engine::add_vertices(int type, int n, const int* ids, const double* est, con
     hg.st[type].resize(o + sd, 0.0);
     set_state_from_est(type, est + (size_t)k * ed, hg.st[type].data() + o);
     if (type == G2OHIP_V_SE3_QUAT) hg.nopl.push_back(0);
-    if (type == G2OHIP_V_SIM3) hg.sim3_cam.insert(hg.sim3_cam.end(), {1.0, 1.0, 0.0, 0.0});  // (:43-57)
+    if (type == G2OHIP_V_SIM3) {  // both cameras' constructor defaults (:43-57)
+      hg.sim3_cam.insert(hg.sim3_cam.end(), {1.0, 1.0, 0.0, 0.0});
+      hg.sim3_cam2.insert(hg.sim3_cam2.end(), {1.0, 1.0, 0.0, 0.0});
+    }
   }
   initialized = false;
   device_state_dirty = true;
@@ -1287,9 +1290,10 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
       type != G2OHIP_E_SE2_OFFSET && !gicp)
     return G2OHIP_ERR_ARG;
   if (!info && n > 0 && !(gicp && params)) return G2OHIP_ERR_ARG;  // only a plane-to-plane set goes without one
-  // no parameter at all: the sba types (the intrinsics live in the VertexCam), EdgeSE2PointXYBearing, EdgeSim3
+  // no parameter at all: the sba types (the intrinsics live in the VertexCam), EdgeSE2PointXYBearing, EdgeSim3, the Sim3
+  // projections (the intrinsics live in the VertexSim3Expmap)
   if (params && (type == G2OHIP_E_PROJECT_P2MC || type == G2OHIP_E_PROJECT_P2SC || type == G2OHIP_E_SE2_XY_BEARING ||
-                 type == G2OHIP_E_SIM3))
+                 type == G2OHIP_E_SIM3 || type == G2OHIP_E_SIM3_PROJECT_XYZ || type == G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ))
     return G2OHIP_ERR_ARG;
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
@@ -1693,6 +1697,16 @@ int Engine::load(const char* path, int marginalize_xyz, unsigned flags) {
                                                   std::to_string(ed.b) + ": vertex " + std::to_string(id) +
                                                   " is missing or no VERTEX_SIM3:EXPMAP");
         }
+      if (is_sim3_project_family(t.family)) {  // v0 a VERTEX_XYZ point, v1 a VERTEX_SIM3:EXPMAP
+        const std::string where = std::string("g2o_hip load: ") + t.tag + " " + std::to_string(ed.a) + " -> " + std::to_string(ed.b);
+        const int want[2] = {G2OHIP_V_XYZ, G2OHIP_V_SIM3}, end[2] = {ed.a, ed.b};
+        const char* vname[2] = {"VERTEX_XYZ", "VERTEX_SIM3:EXPMAP"};
+        for (int h = 0; h < 2; ++h) {
+          auto it = hg.idmap.find(end[h]);
+          if (it == hg.idmap.end() || hg.verts[it->second].type != want[h])
+            throw StatusError(G2OHIP_ERR_ARG, where + ": vertex " + std::to_string(end[h]) + " is missing or no " + vname[h]);
+        }
+      }
       if (is_sba_family(t.family)) {  // v0 a VERTEX_XYZ point, v1 a VERTEX_CAM
         const std::string tg = std::string(t.tag) + " ";
         auto ia = hg.idmap.find(ed.a), ib = hg.idmap.find(ed.b);
@@ -2430,7 +2444,7 @@ EdgeArgs Engine::group_args(const EGroup& g) const {
   a.D = g.D;
   a.DA = g.DA;
   a.DB = g.DB;
-  a.ue = g.ue | (g.family == FAM_SIM3 && sim3_fix_scale_ ? 8 : 0);
+  a.ue = g.ue | ((g.family == FAM_SIM3 || is_sim3_project_family(g.family)) && sim3_fix_scale_ ? 8 : 0);
   return a;
 }
 
@@ -2486,8 +2500,9 @@ void Engine::fill_group_device(EGroup& g) {
   // inverse offset as an isometry (12), the camera types' fx fy cx cy behind it; the pose-only projections: the
   // intrinsics (the point Xw ahead of them in the caller's record goes into the measurement payload); EdgeSE3Offset: the
   // two offsets as isometries [R (9) | t (3)] (24); EdgeSE2Offset: the two offsets x y theta as given (6); Edge_V_V_GICP:
-  // cov0 | cov1 packed upper as given, no record at all in a point-to-plane set. (Host-J groups: no row; the payload is
-  // uploaded by upload_group_payload)
+  // cov0 | cov1 packed upper as given, no record at all in a point-to-plane set; the Sim3 projections: fx fy cx cy of
+  // the edge's Sim3 vertex, camera 1 or (the inverse edge) camera 2. (Host-J groups: no row; the payload is uploaded by
+  // upload_group_payload)
   const EdgeTypeInfo* t = edge_type_info(es.type);
   const bool gicp_plpl = g.family == FAM_GICP && !es.params.empty();
   const int mmeas = t ? t->dev_meas : 0;
@@ -2539,6 +2554,10 @@ void Engine::fill_group_device(EGroup& g) {
       mo[0] = m[0]; mo[1] = m[1];
     } else if (is_sba_family(g.family) || g.family == FAM_SE2XY_BEARING) {
       for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
+    } else if (is_sim3_project_family(g.family)) {  // cam_map1 / cam_map2 of v1 (types_seven_dof_expmap.h:84-99)
+      mo[0] = m[0]; mo[1] = m[1];
+      const std::vector<double>& cam = g.family == FAM_SIM3_PROJECT ? hg.sim3_cam : hg.sim3_cam2;
+      std::memcpy(params.data() + (size_t)k * 4, cam.data() + (size_t)v1[k] * 4, sizeof(double) * 4);
     } else if (g.family == FAM_VSC) {
       for (int j = 0; j < 3; ++j) mo[j] = m[j];
       for (int j = 0; j < 5; ++j) params[(size_t)k * 5 + j] = es.params[(size_t)e * 5 + j];
@@ -4517,6 +4536,32 @@ int Engine::set_sim3_fix_scale(int on) {
     sim3_fix_scale_ = on == 1;
     built_ver = 0;  // a system assembled ahead of time holds the other Jacobians
   }
+  return G2OHIP_OK;
+}
+// VertexSim3Expmap::_focal_length1/2, _principle_point1/2. The projection edges' parameter records are copies of them:
+// the groups and all-edges views of those sets that are on the device are filled again (the uniform bit may change
+// with them), and neither a cached chi2 nor a system assembled ahead of time survives
+int Engine::set_sim3_cameras(int n, const int* ids, const double* cam1, const double* cam2) {
+  if (n < 0 || (n > 0 && !ids)) return G2OHIP_ERR_ARG;
+  for (int k = 0; k < n; ++k) {
+    auto it = hg.idmap.find(ids[k]);
+    if (it == hg.idmap.end() || hg.verts[it->second].type != G2OHIP_V_SIM3) return G2OHIP_ERR_ARG;
+  }
+  for (int k = 0; k < n; ++k) {
+    const size_t o = (size_t)hg.verts[hg.idmap[ids[k]]].local * 4;
+    if (cam1) std::memcpy(hg.sim3_cam.data() + o, cam1 + (size_t)k * 4, sizeof(double) * 4);
+    if (cam2) std::memcpy(hg.sim3_cam2.data() + o, cam2 + (size_t)k * 4, sizeof(double) * 4);
+  }
+  if (n == 0 || (!cam1 && !cam2)) return G2OHIP_OK;
+  for (size_t si = 0; si < hg.esets.size(); ++si) {
+    if (!is_sim3_project_family(edge_family(hg.esets[si].type))) continue;
+    if (si < views_.size()) views_[si].reset();
+    if (initialized && edges_ready)
+      for (EGroup& g : groups)
+        if (g.set == (int)si) fill_group_device(g);
+  }
+  ++state_ver;
+  built_ver = 0;
   return G2OHIP_OK;
 }
 int Engine::pair_major_info(int* out) const {

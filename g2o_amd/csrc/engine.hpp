@@ -55,7 +55,9 @@ struct HostGraph {
   std::vector<double> st[NVT];            // per type, device layout
   std::vector<std::vector<int>> by_type = std::vector<std::vector<int>>(NVT);  // local -> vertex
   std::vector<int> nopl;                // VertexSE3 oplus counters (per local SE3QUAT vertex)
-  std::vector<double> sim3_cam;         // per local Sim3 vertex: fx fy cx cy of its VERTEX_SIM3:EXPMAP line (1 1 0 0)
+  std::vector<double> sim3_cam;         // per local Sim3 vertex: fx fy cx cy of camera 1, what its VERTEX_SIM3:EXPMAP line
+                                        // holds (1 1 0 0), and of camera 2 (no line carries it): g2ohip_set_sim3_cameras
+  std::vector<double> sim3_cam2;
   std::vector<HEdgeSet> esets;          // in first-seen type order
   long long num_edges() const {
     long long n = 0;
@@ -249,6 +251,7 @@ class Engine {
   int pair_major_info(int* out) const;  // out[0] path taken (1 pair-major), out[1] pairs, out[2] chunks
   // VertexSim3Expmap::_fix_scale of every Sim3 vertex: oplus zeroes update[6], EdgeSim3's Jacobians lose column 6
   int set_sim3_fix_scale(int on);
+  int set_sim3_cameras(int n, const int* ids, const double* cam1, const double* cam2);
   // [delta, lastStep, lastNumTries, currentLambda, wasPDInAllIterations] after the last dogleg iteration
   void dogleg_state(double* out) const;
 

@@ -33,6 +33,10 @@ template <class F> struct is_hostj_type : std::false_type {};
 template <int D, int DA, int DB> struct is_hostj_type<FamilyHostJ<D, DA, DB>> : std::true_type {};
 template <int D, int DA> struct is_hostj_type<FamilyHostJUnary<D, DA>> : std::true_type {};
 
+// the Sim3 projection families: no F::linearize (k_linearize_sim3_project takes F::jac_pose)
+template <class F> struct is_sim3_project_type : std::false_type {};
+template <bool INV> struct is_sim3_project_type<FamilySim3Project<INV>> : std::true_type {};
+
 // host-Jacobian families: runtime (D, DA, DB) -> FamilyHostJ<D, DA, DB> (vertex dims 2, 3, 6 or 7, D = 1..7)
 template <int D, int DA, class Fn>
 static void hj_b(int DB, Fn& fn) {
@@ -113,6 +117,8 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_GICP: fn(checked<FAM_GICP, FamilyGICP>()); break;
     case FAM_VSC: fn(checked<FAM_VSC, FamilyVSC>()); break;
     case FAM_SIM3: fn(checked<FAM_SIM3, FamilySim3>()); break;
+    case FAM_SIM3_PROJECT: fn(checked<FAM_SIM3_PROJECT, FamilySim3Project<false>>()); break;
+    case FAM_SIM3_PROJECT_INVERSE: fn(checked<FAM_SIM3_PROJECT_INVERSE, FamilySim3Project<true>>()); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;

@@ -478,6 +478,86 @@ __global__ void __launch_bounds__(256)
   wave_copy_out(slot1 + (size_t)ebase * SA, sw, nw * SA, lane);
 }
 
+// EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ (FamilySim3Project<INV>, D = 2, DA = 3, DB = 7): constructQuadraticForm of
+// the Sim3 side alone. v0, the point, is fixed in every graph that initialises (a free marginalised point is refused by
+// the 7/3 rule, a free non-marginalised one by the one-pose-block-size rule), so neither A (2 x 3), the side-A slot nor
+// an off-diagonal block exists: one lane per edge forms B = Jj (2 x 7), B^T Omega B packed upper 28 and -B^T Omega e (7),
+// Omega scaled by rho' under a robust kernel, in k_linearize's side-B operation order. fix_scale (EdgeData::ue bit 3)
+// zeroes column 6 of B. Slot contract of k_linearize: the same slot layout (packed upper 28 + 7), one wave-staged
+// coalesced copy-out of 35 doubles per lane (70 KB of LDS per workgroup, k_linearize_sim3's image), a fixed summation
+// order; a lane whose Sim3 vertex is fixed writes nothing to the image (its slot is never read).
+template <class F>
+__global__ void __launch_bounds__(256)
+    k_linearize_sim3_project(EdgeData d, int ne, const int* __restrict__ h1, double* __restrict__ slot1) {
+  constexpr int D = F::D, DB = F::DB;
+  constexpr int SB = DB * (DB + 1) / 2 + DB;
+  static_assert(D == 2 && DB == 7 && SB == 35, "the Sim3 projection families");
+  __shared__ __attribute__((aligned(16))) double stage[4][64 * SB];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int e = blockIdx.x * blockDim.x + tid;
+  const int ebase = e - lane, nw = min(64, ne - ebase);  // the wave's edges [ebase, ebase + nw)
+  if (nw <= 0) return;                                  // wave-uniform
+  double* sw = stage[tid >> 6];
+  if (e < ne && h1[d.v1[e]] >= 0) {
+    double err[D], B[D * DB], Om[D * D];
+    F::jac_pose(d, e, err, B);
+    if (d.ue & 8) B[6] = B[DB + 6] = 0;
+    family_info<F>(d, e, Om);
+    if (d.rk) {  // robust branch of constructQuadraticForm (base_binary_edge.hpp:104-135): Omega, omega_r scaled by rho'
+      double chi = 0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        double r = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) r += Om[i * D + j] * err[j];
+        chi += err[i] * r;
+      }
+      double r0, r1;
+      robustify(d.rk, d.rk_delta, chi, r0, r1);
+#pragma unroll
+      for (int i = 0; i < D * D; ++i) Om[i] *= r1;
+    }
+    double wr[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      double s = 0;
+#pragma unroll
+      for (int c = 0; c < D; ++c) s += Om[r * D + c] * err[c];
+      wr[r] = -s;
+    }
+    double BtO[DB * D];
+#pragma unroll
+    for (int j = 0; j < DB; ++j)
+#pragma unroll
+      for (int c = 0; c < D; ++c) {
+        double s = 0;
+#pragma unroll
+        for (int r = 0; r < D; ++r) s += B[r * DB + j] * Om[r * D + c];
+        BtO[j * D + c] = s;
+      }
+    double* o = sw + lane * SB;
+    int k = 0;
+#pragma unroll
+    for (int c = 0; c < DB; ++c)
+#pragma unroll
+      for (int r = 0; r <= c; ++r) {
+        double s = 0;
+#pragma unroll
+        for (int t = 0; t < D; ++t) s += BtO[r * D + t] * B[t * DB + c];
+        o[k++] = s;
+      }
+#pragma unroll
+    for (int j = 0; j < DB; ++j) {
+      double s = 0;
+#pragma unroll
+      for (int r = 0; r < D; ++r) s += B[r * DB + j] * wr[r];
+      o[k++] = s;
+    }
+  }
+  wave_sync();
+  wave_copy_out(slot1 + (size_t)ebase * SB, sw, nw * SB, lane);
+}
+
 // ------------------------------------------------------------------------------ vertex reduction
 // One group of LANES lanes per vertex; lane l sums slots l, l+LANES, ... in order; butterfly
 // reduction in a fixed pattern keeps the result bitwise reproducible.
@@ -1998,6 +2078,8 @@ void linearize(int family, const EdgeArgs& a, int ne, const int* h0, const int* 
     if constexpr (std::is_same_v<F, FamilySim3>)  // never the generic kernel at D = DA = DB = 7 (k_linearize_sim3)
       hipLaunchKernelGGL(k_linearize_sim3, g, 256, 0, s, mk(a), ne, h0, h1, slot0, slot1, off_dst, off_tr, off_base,
                          off_slot);
+    else if constexpr (is_sim3_project_type<F>::value)  // the Sim3 side alone: no side-A slot, no off-diagonal block
+      hipLaunchKernelGGL(k_linearize_sim3_project<F>, g, 256, 0, s, mk(a), ne, h1, slot1);
     else
       hipLaunchKernelGGL(k_linearize<F>, g, 256, 0, s, mk(a), ne, h0, h1, slot0, slot1, off_dst, off_tr, off_base,
                          off_slot);

@@ -16,6 +16,7 @@ inline bool is_pose_only_family(int f) { return f == FAM_U_POSE_ONLY || f == FAM
 inline bool is_hostj_family(int f) { return f == FAM_HOSTJ || f == FAM_U_HOSTJ; }
 inline bool is_slam3d_family(int f) { return f >= FAM_SE3_XYZ && f <= FAM_SE3_XYZ_DISPARITY; }
 inline bool is_sba_family(int f) { return f == FAM_SBA_MONO || f == FAM_SBA_STEREO; }
+inline bool is_sim3_project_family(int f) { return f == FAM_SIM3_PROJECT || f == FAM_SIM3_PROJECT_INVERSE; }
 
 struct EdgeArgs {
   const int* v0;
@@ -29,7 +30,7 @@ struct EdgeArgs {
   double rk_delta = 1.0;
   int D = 0, DA = 0, DB = 0;  // host-J family dimensions
   int ue = 0;                 // uniform records (EdgeData::ue): bit 0 information, bit 1 intrinsics; bit 2 GICP plane-to-plane;
-                              // bit 3: the Sim3 vertices' _fix_scale (FamilySim3)
+                              // bit 3: the Sim3 vertices' _fix_scale (FamilySim3, FamilySim3Project)
 };
 
 namespace launch {

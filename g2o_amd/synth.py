@@ -77,19 +77,24 @@ E_V_V_GICP, E_XYZ_VSC = 25, 26
 # Sim3 in the same layout, info 7x7 in (omega, upsilon, sigma) order
 V_SIM3 = 7
 E_SIM3 = 27
+# EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ from a fixed V_XYZ point to a V_SIM3 (meas u v, info 2x2, no params: the
+# intrinsics are camera 1 / camera 2 of the Sim3 vertex)
+E_SIM3_PROJECT, E_SIM3_PROJECT_INVERSE = 28, 29
 EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12, V_SIM3: 8}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
             E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
             E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
             E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 7, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
-            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 12, E_XYZ_VSC: 3, E_SIM3: 8}
+            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 12, E_XYZ_VSC: 3, E_SIM3: 8,
+            E_SIM3_PROJECT: 2, E_SIM3_PROJECT_INVERSE: 2}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
            E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 6, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
-           E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 3, E_XYZ_VSC: 3, E_SIM3: 7}
+           E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 3, E_XYZ_VSC: 3, E_SIM3: 7,
+           E_SIM3_PROJECT: 2, E_SIM3_PROJECT_INVERSE: 2}
 # parameter values per edge of the types that take a record (EdgeSet.params; where None is allowed it is the identity)
 PARAM_DIM = {E_SE3_PROJECT_XYZ: 4, E_STEREO_SE3_PROJECT_XYZ: 5, E_SE3_PRIOR: 7, E_SE3_XYZ: 7, E_SE3_XYZ_DEPTH: 11,
              E_SE3_XYZ_DISPARITY: 11, E_SE3_PROJECT_XYZ_ONLYPOSE: 7, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 8,

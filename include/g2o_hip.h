@@ -202,9 +202,9 @@ extern "C" {
  * Sim3 poses is BlockSolver_7_3 without marginalised vertices: {lm,gn,dl}_hip_fix7_3 or *_hip_var. A free marginalised
  * point beside Sim3 poses is refused by the structure build (G2OHIP_ERR_UNSUPPORTED: the 7/3 Schur kernels do not
  * exist), a free non-marginalised one by the one-pose-block-size rule; lm_pcg*, gn_pcg* and lm_pcg6_3_eigen refuse a
- * Sim3 graph (pose blocks of 3 or 6 only). EdgeSim3ProjectXYZ and EdgeInverseSim3ProjectXYZ, numerically differentiated
- * in the reference, enter as G2OHIP_E_HOSTJ(2) between a fixed G2OHIP_V_XYZ point and a Sim3 vertex (ORB-SLAM's
- * OptimizeSim3, where the points are fixed). ---- */
+ * Sim3 graph (pose blocks of 3 or 6 only). EdgeSim3ProjectXYZ and EdgeInverseSim3ProjectXYZ (ORB-SLAM's OptimizeSim3,
+ * where the points are fixed) are the device types G2OHIP_E_SIM3_PROJECT_XYZ and G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ
+ * below; as G2OHIP_E_HOSTJ(2) between a fixed G2OHIP_V_XYZ point and a Sim3 vertex they still enter too. ---- */
 #define G2OHIP_E_SIM3 27 /* EdgeSim3 (EDGE_SIM3:EXPMAP), types_seven_dof_expmap.h:110-137: v0, v1 both G2OHIP_V_SIM3; meas
                             the Sim3 C, 8 doubles in the vertex layout, normalised on entry as a vertex estimate is; info
                             7x7 in (omega, upsilon, sigma) order; params must be NULL (non-NULL is G2OHIP_ERR_ARG).
@@ -214,6 +214,26 @@ extern "C" {
                             Ji = M Ad(C), Jj = -M Ad(E), E = C S0 S1^-1, M = d log(exp(d) E) / d d. No isDepthPositive
                             (depth_positive != NULL or check_depth is G2OHIP_ERR_ARG); robust kernels, edge levels,
                             g2ohip_edge_chi2 and g2ohip_classify_edges take it like any device type */
+#define G2OHIP_E_SIM3_PROJECT_XYZ 28 /* EdgeSim3ProjectXYZ (EDGE_PROJECT_SIM3_XYZ:EXPMAP), types_seven_dof_expmap.h:141-160:
+                            v0 a G2OHIP_V_XYZ point, v1 a G2OHIP_V_SIM3, in g2o's vertex order; meas u v; info 2x2;
+                            params must be NULL (non-NULL is G2OHIP_ERR_ARG): the intrinsics are camera 1 of v1
+                            (g2ohip_set_sim3_cameras, or the VERTEX_SIM3:EXPMAP line). error = obs -
+                            cam_map1(project(S.map(p))), S.map(p) = s (r p) + t in that order. The reference
+                            differentiates numerically (its linearizeOplus is commented out); the device uses the exact
+                            first derivatives under the vertex's oplus exp(u) S: with x = S.map(p) and
+                            P = [[fx/z, 0, -fx x/z^2], [0, fy/z, -fy y/z^2]] at x, Jj = -P [ -[x]x | I | x ] and
+                            Ji = -P s R; under g2ohip_set_sim3_fix_scale(1) column 6 of Jj is zero. The point is fixed
+                            in every graph that initialises (a free marginalised one needs the 7/3 Schur kernels, a free
+                            non-marginalised one breaks the one-pose-block-size rule), so the device forms Jj alone:
+                            k_linearize_sim3_project writes the Sim3 vertex's slot and nothing else. No isDepthPositive
+                            in the reference (depth_positive != NULL or check_depth is G2OHIP_ERR_ARG); robust kernels,
+                            edge levels, g2ohip_edge_chi2, g2ohip_classify_edges, marginals and
+                            g2ohip_update_initialization take it like any device type */
+#define G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ 29 /* EdgeInverseSim3ProjectXYZ (EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP), :163-180:
+                            the same endpoints, measurement and information; the intrinsics are camera 2 of v1. error =
+                            obs - cam_map2(project(S.inverse().map(p))), S.inverse() as the reference's constructor
+                            builds it (conjugate, conj * (-t / s), 1 / s, then normalizeRotation). With (R', t', s') =
+                            S^-1 and y = s' R' p + t': Jj = -P(y) s' R' [ [p]x | -I | -p ], Ji = -P(y) s' R' */
 /* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3, 6 or 7 (an edge type of the application's own, say): the
  * host supplies the error and the Jacobian as for G2OHIP_E_HOSTJ, payload [e (D) | Ji (D x dim(v0))] row-major per
  * edge. meas unused (may be NULL); info D*D. */
@@ -347,10 +367,19 @@ int g2ohip_load_g2o(g2ohip_graph* g, const char* path, int marginalize_xyz);
  * g2ohip_save_g2o. A line with exactly 7 values takes the constructor's defaults 1 1 0 0; any other length fails the
  * load, g2ohip_last_error naming the tag. EDGE_SIM3:EXPMAP v0 v1 m0..m6 and the 28 upper-triangle information values
  * loads as G2OHIP_E_SIM3 with the measurement Sim3(m).inverse() (:104-122); a short line or an endpoint that is no
- * VERTEX_SIM3:EXPMAP fails the load. Without the flag both tags are skipped like any unknown one. EDGE_PROJECT_SIM3_XYZ:EXPMAP
- * and EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP are always skipped: their lines carry no intrinsics. g2ohip_save_g2o writes both
- * tags the reference's way (:89-102, 124-137): the log of the inverse, the intrinsics, the upper triangle. */
+ * VERTEX_SIM3:EXPMAP fails the load. Without the flag both tags are skipped like any unknown one. g2ohip_save_g2o writes both
+ * tags the reference's way (:89-102, 124-137): the log of the inverse, the intrinsics, the upper triangle.
+ * EDGE_PROJECT_SIM3_XYZ:EXPMAP and EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP are read under G2OHIP_LOAD_SIM3_PROJECT alone. */
 #define G2OHIP_LOAD_SIM3 128u
+/* G2OHIP_LOAD_SIM3_PROJECT (with G2OHIP_LOAD_SIM3, which reads the vertices): EDGE_PROJECT_SIM3_XYZ:EXPMAP v0 v1 u v i00 i01
+ * i11 loads as G2OHIP_E_SIM3_PROJECT_XYZ and EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP, the same line, as
+ * G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ (types_seven_dof_expmap.cpp:146-203). A short line, a v0 that is no VERTEX_XYZ or a v1
+ * that is no VERTEX_SIM3:EXPMAP fails the load, g2ohip_last_error naming the tag. Camera 1 of a vertex is what its
+ * VERTEX_SIM3:EXPMAP line holds; no line carries camera 2, in the reference either: it keeps its default 1 1 0 0 until
+ * g2ohip_set_sim3_cameras. The points must end up fixed (FIX lines, marginalize_xyz = 0) or initialisation refuses the
+ * graph (see types/sim3 above). Without the flag both tags are skipped like any unknown one. g2ohip_save_g2o writes
+ * both tags the reference's way: u v and the upper triangle. */
+#define G2OHIP_LOAD_SIM3_PROJECT 256u
 int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, unsigned flags);
 /* Unary edges are written under the reference's tags and formats (edge_se2_prior.cpp:57-65, edge_se2_xyprior.cpp:50-58,
  * edge_xy_prior.cpp, edge_xyz_prior.cpp:54-61, edge_se3_prior.cpp:77-86), with one PARAMS_SE3OFFSET id x y z qx qy qz qw
@@ -424,11 +453,19 @@ int g2ohip_set_algorithm(g2ohip_graph* g, const char* name);
 int g2ohip_set_pair_major(g2ohip_graph* g, int enable);
 /* VertexSim3Expmap::_fix_scale (types_seven_dof_expmap.h:77-78, 101), for every G2OHIP_V_SIM3 vertex of the handle: on = 1
  * makes oplus zero update[6], so the scale of no vertex moves. The reference differentiates EdgeSim3 numerically
- * through oplusImpl, so under _fix_scale column 6 of both of its Jacobians is zero; the device zeroes that column too.
+ * through oplusImpl, so under _fix_scale column 6 of both of its Jacobians is zero; the device zeroes that column too,
+ * and column 6 of the Sim3 projection edges' Jj.
  * H(6, 6) of every vertex block then holds lambda alone: Levenberg-Marquardt works, Gauss-Newton and the undamped
  * dogleg solve on such a graph are not positive definite. That is the reference's behaviour. Host-Jacobian edges on Sim3
  * vertices must supply such Jacobians themselves. on other than 0 or 1: G2OHIP_ERR_ARG. */
 int g2ohip_set_sim3_fix_scale(g2ohip_graph* g, int on);
+/* VertexSim3Expmap::_focal_length1 / _principle_point1 and _focal_length2 / _principle_point2
+ * (types_seven_dof_expmap.h:84-99) of n G2OHIP_V_SIM3 vertices: cam1 and cam2 are n * 4 doubles fx fy cx cy, NULL
+ * leaves that camera as it is. Both default to 1 1 0 0; camera 1 is also what a VERTEX_SIM3:EXPMAP line sets and
+ * g2ohip_save_g2o writes. G2OHIP_E_SIM3_PROJECT_XYZ reads camera 1 of its v1, G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ camera 2.
+ * A change after the edges are on the device reaches it before the next evaluation. An id that is no G2OHIP_V_SIM3
+ * vertex: G2OHIP_ERR_ARG, and nothing changes. */
+int g2ohip_set_sim3_cameras(g2ohip_graph* g, int n, const int* ids, const double* cam1, const double* cam2);
 int g2ohip_pair_major_info(g2ohip_graph* g, int out[3]);
 int g2ohip_set_dogleg_params(g2ohip_graph* g, double initial_delta, int max_trials_after_failure,
                              double initial_lambda, double lambda_factor);
