@@ -94,6 +94,11 @@ SIM3_TAGS = {"vertex": "VERTEX_SIM3:EXPMAP", "edge": "EDGE_SIM3:EXPMAP"}
 E_SIM3_PROJECT, E_SIM3_PROJECT_INVERSE = 28, 29
 SIM3_PROJECT_TAGS = {E_SIM3_PROJECT: "EDGE_PROJECT_SIM3_XYZ:EXPMAP",
                      E_SIM3_PROJECT_INVERSE: "EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP"}
+# examples/bal (G2OHIP_V_CAM_BAL, G2OHIP_E_OBSERVATION_BAL): VertexCameraBAL, estimate [n, 9] rx ry rz tx ty tz f k1 k2,
+# dimension 9; EdgeObservationBAL from it (v0) to a V_XYZ point (v1), meas [n, 2] u v, info [n, 2, 2], params None. No
+# .g2o tag: SparseOptimizer.load_bal / save_bal read and write the BAL text format
+V_CAM_BAL = synth.V_CAM_BAL
+E_OBSERVATION_BAL = synth.E_OBSERVATION_BAL
 
 
 # EdgeGICP::prec0 / cov0 in numpy, and the packed form of the covariances (ValueError on a normal parallel to (0,1,0))
@@ -158,7 +163,7 @@ EXPORTS = [
     "g2ohip_dogleg_next_delta", "g2ohip_structure_only_calc",
     "g2ohip_set_edge_levels", "g2ohip_get_edge_levels", "g2ohip_initialize_level", "g2ohip_edge_chi2",
     "g2ohip_classify_edges", "g2ohip_set_pair_major", "g2ohip_pair_major_info", "g2ohip_set_sim3_fix_scale",
-    "g2ohip_set_sim3_cameras",
+    "g2ohip_set_sim3_cameras", "g2ohip_load_bal", "g2ohip_save_bal",
 ]
 
 # G2OHIP_LEVEL_KEEP: classify_edges leaves the level of the edges on that side as it is
@@ -189,6 +194,8 @@ def lib() -> C.CDLL:
         "g2ohip_load_g2o": ([P, C.c_char_p, I], I),
         "g2ohip_load_g2o_ex": ([P, C.c_char_p, I, C.c_uint], I),
         "g2ohip_save_g2o": ([P, C.c_char_p], I),
+        "g2ohip_load_bal": ([P, C.c_char_p, I], I),
+        "g2ohip_save_bal": ([P, C.c_char_p], I),
         "g2ohip_num_vertices": ([P], I),
         "g2ohip_num_edges": ([P], I),
         "g2ohip_set_robust_kernel": ([P, I, I, D], I),
@@ -444,7 +451,8 @@ class SparseOptimizer:
         par = None if es.params is None else np.ascontiguousarray(es.params, np.float64)
         pd = synth.PARAM_DIM.get(es.etype)
         md, D = synth.MEAS_DIM.get(es.etype), synth.ERR_DIM.get(es.etype)
-        if es.etype in (E_V_V_GICP, E_XYZ_VSC, E_SIM3, E_SIM3_PROJECT, E_SIM3_PROJECT_INVERSE):  # the C side reads n * md and n * D * D doubles
+        if es.etype in (E_V_V_GICP, E_XYZ_VSC, E_SIM3, E_SIM3_PROJECT, E_SIM3_PROJECT_INVERSE,
+                        E_OBSERVATION_BAL):  # the C side reads n * md and n * D * D doubles
             if meas is None or meas.size != len(v0) * md:
                 raise G2OHipError(f"add_edges: edge type {es.etype} takes {md} measurement values per edge, got "
                                   f"{0 if meas is None else meas.size} for {len(v0)} edges")
@@ -531,6 +539,16 @@ class SparseOptimizer:
 
     def save(self, path: str):
         _check(lib().g2ohip_save_g2o(self.h, path.encode()), "save")
+
+    def load_bal(self, path: str, marginalize: bool = True):
+        """g2ohip_load_bal: a "Bundle Adjustment in the Large" text file (bal_example.cpp:336-406). Cameras become
+        V_CAM_BAL vertices with ids 0 .. ncams-1, points V_XYZ vertices behind them (marginalised by default),
+        observations E_OBSERVATION_BAL edges with identity information."""
+        _check(lib().g2ohip_load_bal(self.h, path.encode(), int(marginalize)), "load_bal")
+
+    def save_bal(self, path: str):
+        """g2ohip_save_bal: the same format from the current estimates, 17 significant digits."""
+        _check(lib().g2ohip_save_bal(self.h, path.encode()), "save_bal")
 
     def save_hessian(self, path: str) -> bool:
         """Solver::saveHessian (block_solver.hpp:589-593): Hpp in Octave sparse-matrix text."""

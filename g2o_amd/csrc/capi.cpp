@@ -36,13 +36,14 @@ int guarded(F&& f) {
 int algorithm_known(const std::string& n) {
   // StructureOnlySolver<3> / <2> (solvers/structure_only/structure_only.cpp:64-65)
   if (n == "structure_only_3" || n == "structure_only_2") return 1;
-  // {gn,lm}_hip_{var,fix6_3,fix3_2,fix3_3,fix6_6,fix7_3} (cf. solver_csparse.cpp:51-84 name parsing; fix7_3 is
-  // BlockSolver_7_3, block_solver.h:196-197, here for Sim3 pose graphs without marginalised points)
+  // {gn,lm}_hip_{var,fix6_3,fix3_2,fix3_3,fix6_6,fix7_3,fix9_3} (cf. solver_csparse.cpp:51-84 name parsing; fix7_3 is
+  // BlockSolver_7_3, block_solver.h:196-197, here for Sim3 pose graphs without marginalised points; fix9_3 is
+  // bal_example.cpp:301's BalBlockSolver)
   if (n.size() < 6) return 0;
   const std::string m = n.substr(0, 3), rest = n.substr(3);
   if (m != "lm_" && m != "gn_" && m != "dl_") return 0;
   if (rest == "hip_var" || rest == "hip_fix6_3" || rest == "hip_fix3_2" || rest == "hip_fix3_3" ||
-      rest == "hip_fix6_6" || rest == "hip_fix7_3")
+      rest == "hip_fix6_6" || rest == "hip_fix7_3" || rest == "hip_fix9_3")
     return 1;
   // Powell's dogleg needs an exact Gauss-Newton solve: the reference registers dl_* over the Cholesky solvers only
   // (solver_csparse.cpp), never over PCG
@@ -140,6 +141,15 @@ int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
             "return false)";
     return G2OHIP_ERR_UNSUPPORTED;
   }
+  // EdgeObservationBAL and VertexCameraBAL likewise (bal_example.cpp:69-83, 163-172): the BAL text format carries them
+  if (const auto* es = g->e->hg.set_of(G2OHIP_E_OBSERVATION_BAL);
+      (es && !es->ev0.empty()) || !g->e->hg.by_type[G2OHIP_V_CAM_BAL].empty()) {
+    g_err = "g2ohip_save_g2o: the graph holds " + std::to_string(es ? es->ev0.size() : 0) + " EdgeObservationBAL edges and " +
+            std::to_string(g->e->hg.by_type[G2OHIP_V_CAM_BAL].size()) +
+            " VertexCameraBAL vertices, which the .g2o format cannot carry (the reference's read and write return "
+            "false); use g2ohip_save_bal";
+    return G2OHIP_ERR_UNSUPPORTED;
+  }
   // the pose-only projections likewise: their tags carry neither the point Xw nor the intrinsics
   // (types_six_dof_expmap.cpp:543-567, 610-634)
   for (int type : {G2OHIP_E_SE3_PROJECT_XYZ_ONLYPOSE, G2OHIP_E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE})
@@ -165,6 +175,14 @@ int g2ohip_save_g2o(g2ohip_graph* g, const char* path) {
             }
     }
   return guarded([&] { return g->e->save(path); });
+}
+int g2ohip_load_bal(g2ohip_graph* g, const char* path, int marginalize_points) {
+  if (!g || !path) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->load_bal(path, marginalize_points); });
+}
+int g2ohip_save_bal(g2ohip_graph* g, const char* path) {
+  if (!g || !path) return G2OHIP_ERR_ARG;
+  return guarded([&] { return g->e->save_bal(path); });
 }
 int g2ohip_num_vertices(g2ohip_graph* g) { return g ? (int)g->e->hg.verts.size() : G2OHIP_ERR_ARG; }
 int g2ohip_num_edges(g2ohip_graph* g) { return g ? (int)g->e->hg.num_edges() : G2OHIP_ERR_ARG; }

@@ -1972,6 +1972,120 @@ struct FamilySim3Project {
   }
 };
 
+// ---- EdgeObservationBAL (examples/bal/bal_example.cpp:156-281): v0 = VertexCameraBAL [9] rx ry rz tx ty tz f k1 k2 (an
+// angle-axis rotation, world to camera), v1 = point (3); meas u v, info packed 3, no parameter record, no depth test.
+// With w = est[0:3], th = |w|: P = X cos th + (v x X) sin th + v (v.X)(1 - cos th), v = w / th (th == 0: P = X + w x X),
+// P += t, p = -P.xy / P.z, r2 = p.p, rp = 1 + k1 r2 + k2 r2 r2, e = f rp p - z, in the reference's operation order. The
+// reference differentiates this with ceres autodiff, which gives the exact first derivatives of the expression as
+// written, branch by branch; so does this:
+//   dE = f (rp I + (2 k1 + 4 k2 r2) p p^T), dp/dP = [[-1/Pz, 0, Px/Pz^2], [0, -1/Pz, Py/Pz^2]], M = dE dp/dP (2 x 3),
+//   Ji = [ M dP/dw | M | rp p | f r2 p | f r2^2 p ],  Jj = M dP/dX (the Rodrigues matrix of the branch).
+// dP/dw_k for th > 0 goes term by term through th, v, sin and cos, with dth/dw_k = v_k, dv/dw_k = (e_k - v v_k) / th:
+//   -X sin th v_k + (dv x X) sin th + (v x X) cos th v_k + dv (v.X)(1 - cos th) + v (dv.X)(1 - cos th) + v (v.X) sin th v_k
+// (no closed form that divides differences by th^2: such a form loses digits for small th, where autodiff does not);
+// th == 0: dP/dw = -[X]x, dP/dX = I + [w]x. ----
+struct FamilyBAL {
+  static constexpr int D = 2, DA = 9, DB = 3, MEAS = 2, INFO = 3, PAR = 0;
+  // P (before the translation), and with JAC the 3 x 3 row-major dP/dw and dP/dX
+  template <bool JAC>
+  DI static void rotate(const double* w, const double* X, double* P, double* dPw, double* dPX) {
+    const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    if (th > 0) {
+      const double v[3] = {w[0] / th, w[1] / th, w[2] / th};
+      const double c = cos(th), s = sin(th);
+      const double vX[3] = {v[1] * X[2] - v[2] * X[1], v[2] * X[0] - v[0] * X[2], v[0] * X[1] - v[1] * X[0]};
+      const double vd = v[0] * X[0] + v[1] * X[1] + v[2] * X[2];
+      const double omc = 1.0 - c;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) P[i] = X[i] * c + vX[i] * s + v[i] * vd * omc;
+      if (JAC) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          double dv[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) dv[i] = ((i == k ? 1.0 : 0.0) - v[i] * v[k]) / th;
+          const double dvX[3] = {dv[1] * X[2] - dv[2] * X[1], dv[2] * X[0] - dv[0] * X[2], dv[0] * X[1] - dv[1] * X[0]};
+          const double dvd = dv[0] * X[0] + dv[1] * X[1] + dv[2] * X[2];
+          const double dc = -s * v[k], ds = c * v[k];  // d cos th, d sin th
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+            dPw[i * 3 + k] = X[i] * dc + dvX[i] * s + vX[i] * ds + dv[i] * vd * omc + v[i] * dvd * omc - v[i] * vd * dc;
+        }
+        // dP/dX = c I + s [v]x + (1 - c) v v^T
+        const double R[9] = {c + omc * v[0] * v[0],        -s * v[2] + omc * v[0] * v[1], s * v[1] + omc * v[0] * v[2],
+                             s * v[2] + omc * v[1] * v[0], c + omc * v[1] * v[1],         -s * v[0] + omc * v[1] * v[2],
+                             -s * v[1] + omc * v[2] * v[0], s * v[0] + omc * v[2] * v[1], c + omc * v[2] * v[2]};
+#pragma unroll
+        for (int i = 0; i < 9; ++i) dPX[i] = R[i];
+      }
+    } else {  // the reference's Taylor branch, taken at th == 0 exactly
+      P[0] = X[0] + (w[1] * X[2] - w[2] * X[1]);
+      P[1] = X[1] + (w[2] * X[0] - w[0] * X[2]);
+      P[2] = X[2] + (w[0] * X[1] - w[1] * X[0]);
+      if (JAC) {
+        const double A[9] = {0, X[2], -X[1], -X[2], 0, X[0], X[1], -X[0], 0};       // -[X]x
+        const double R[9] = {1, -w[2], w[1], w[2], 1, -w[0], -w[1], w[0], 1};       // I + [w]x
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { dPw[i] = A[i]; dPX[i] = R[i]; }
+      }
+    }
+  }
+  DI static void load(const EdgeData& d, int e, double* cam, double* X) {
+    const double* c = d.s0 + (size_t)d.v0[e] * 9;
+    const double* x = d.s1 + (size_t)d.v1[e] * 3;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cam[k] = c[k];
+    X[0] = x[0]; X[1] = x[1]; X[2] = x[2];
+  }
+  DI static void error(const EdgeData& d, int e, double* err) {
+    double cam[9], X[3], P[3];
+    load(d, e, cam, X);
+    rotate<false>(cam, X, P, nullptr, nullptr);
+    P[0] += cam[3]; P[1] += cam[4]; P[2] += cam[5];
+    const double* m = d.meas + (size_t)e * 2;
+    const double p0 = -P[0] / P[2], p1 = -P[1] / P[2];
+    const double r2 = p0 * p0 + p1 * p1;
+    const double rp = 1.0 + cam[7] * r2 + cam[8] * r2 * r2;
+    err[0] = cam[6] * rp * p0 - m[0];
+    err[1] = cam[6] * rp * p1 - m[1];
+  }
+  DI static void linearize(const EdgeData& d, int e, double* err, double* Ji, double* Jj) {
+    double cam[9], X[3], P[3], dPw[9], dPX[9];
+    load(d, e, cam, X);
+    rotate<true>(cam, X, P, dPw, dPX);
+    P[0] += cam[3]; P[1] += cam[4]; P[2] += cam[5];
+    const double* m = d.meas + (size_t)e * 2;
+    const double p0 = -P[0] / P[2], p1 = -P[1] / P[2];
+    const double r2 = p0 * p0 + p1 * p1;
+    const double f = cam[6], k1 = cam[7], k2 = cam[8];
+    const double rp = 1.0 + k1 * r2 + k2 * r2 * r2;
+    err[0] = f * rp * p0 - m[0];
+    err[1] = f * rp * p1 - m[1];
+    const double g = 2 * k1 + 4 * k2 * r2;
+    const double dE[4] = {f * (rp + g * p0 * p0), f * (g * p0 * p1), f * (g * p0 * p1), f * (rp + g * p1 * p1)};
+    const double iz = 1.0 / P[2];
+    const double dp[6] = {-iz, 0, P[0] * iz * iz, 0, -iz, P[1] * iz * iz};
+    double M[6];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) M[r * 3 + c] = dE[r * 2] * dp[c] + dE[r * 2 + 1] * dp[3 + c];
+    const double pr[2] = {p0, p1};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        Ji[r * 9 + c] = M[r * 3] * dPw[c] + M[r * 3 + 1] * dPw[3 + c] + M[r * 3 + 2] * dPw[6 + c];
+        Ji[r * 9 + 3 + c] = M[r * 3 + c];
+        Jj[r * 3 + c] = M[r * 3] * dPX[c] + M[r * 3 + 1] * dPX[3 + c] + M[r * 3 + 2] * dPX[6 + c];
+      }
+      Ji[r * 9 + 6] = rp * pr[r];
+      Ji[r * 9 + 7] = f * r2 * pr[r];
+      Ji[r * 9 + 8] = f * r2 * r2 * pr[r];
+    }
+  }
+};
+
 // ---- EdgeSE3ProjectXYZOnlyPose (types_six_dof_expmap.h:242-246, .cpp:569-599), unary: v0 = camera SE3Quat [8];
 // meas payload u v | Xw (5), info packed 3, params fx fy cx cy (one shared record when EdgeData::ue bit 1 is set).
 // error = obs - cam_project(T.map(Xw)); the Jacobian in the reference's invz / invz_2 products ----

@@ -1,5 +1,5 @@
 // What the host knows about each device edge type, in one table: EDGE_TYPES has one row per G2OHIP_E_* code the
-// device linearizes itself (1-3, 5-29). The host-Jacobian types (G2OHIP_E_HOSTJ*, any D and any endpoints) are no rows:
+// device linearizes itself (1-3, 5-30). The host-Jacobian types (G2OHIP_E_HOSTJ*, any D and any endpoints) are no rows:
 // their facts follow from the code (hostj_dim). The launchers check the rows against the device families at compile
 // time (family_dispatch.hpp), so a stride here cannot drift from the one a kernel indexes with.
 #pragma once
@@ -33,16 +33,20 @@ enum Family {
   // EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ (point, VertexSim3Expmap): FamilySim3Project<false> / <true>,
   // linearized by k_linearize_sim3_project (the Sim3 side alone: the point is fixed in every graph that initialises)
   FAM_SIM3_PROJECT = 28, FAM_SIM3_PROJECT_INVERSE = 29,
+  // EdgeObservationBAL (VertexCameraBAL, point; examples/bal): FamilyBAL, a 2 x 9 camera Jacobian
+  FAM_BAL = 30,
   FAM_COUNT
 };
 
 constexpr int vertex_dim(int t) {
   if (t == G2OHIP_V_SIM3) return 7;
+  if (t == G2OHIP_V_CAM_BAL) return 9;
   return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT || t == G2OHIP_V_CAM ? 6
          : (t == G2OHIP_V_XYZ || t == G2OHIP_V_SE2 ? 3 : (t == G2OHIP_V_XY ? 2 : -1));
 }
 
-// which endpoint a marginalised landmark may be (structure-only, the Schur path's landmark edges)
+// which endpoint a marginalised landmark may be (the Schur path's landmark edges; structure-only reads it for the
+// families has_structure_only_form names)
 enum LmSide { LM_NONE, LM_V0, LM_V1 };
 
 // lm_pcg6_3_eigen (matrix-free CGLS on the Jacobian of BA edges) refuses a graph that holds one of these; in the order
@@ -83,7 +87,7 @@ struct EdgeTypeInfo {
 
 namespace edge_types_detail {
 constexpr int EXPMAP = G2OHIP_V_SE3_EXPMAP, XYZ = G2OHIP_V_XYZ, SE3 = G2OHIP_V_SE3_QUAT, SE2 = G2OHIP_V_SE2,
-              XY = G2OHIP_V_XY, CAM = G2OHIP_V_CAM, SIM3 = G2OHIP_V_SIM3;
+              XY = G2OHIP_V_XY, CAM = G2OHIP_V_CAM, SIM3 = G2OHIP_V_SIM3, CAM_BAL = G2OHIP_V_CAM_BAL;
 constexpr bool Y = true, N = false;
 constexpr const char* NOTAG = nullptr;
 // per row:  type, family, vtA, vtB,                      D, nm, np, dev_meas, dev_par,
@@ -153,6 +157,9 @@ constexpr EdgeTypeInfo TABLE[] = {
      LM_NONE, Y, N,  "EDGE_PROJECT_SIM3_XYZ:EXPMAP", G2OHIP_LOAD_SIM3_PROJECT, 0, Y,  CGLS_OK},
     {G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ, FAM_SIM3_PROJECT_INVERSE, XYZ, SIM3,  2, 2, 0, 2, 4,
      LM_NONE, Y, N,  "EDGE_PROJECT_INVERSE_SIM3_XYZ:EXPMAP", G2OHIP_LOAD_SIM3_PROJECT, 0, Y,  CGLS_OK},
+    // EdgeObservationBAL: the camera first (CGLS: blocks of 9 are refused before the per-type check)
+    {G2OHIP_E_OBSERVATION_BAL, FAM_BAL, CAM_BAL, XYZ,     2, 2, 0, 2, 0,
+     LM_V1, Y, N,    NOTAG, 0, 0, N,  CGLS_OK},
 };
 constexpr bool sorted_and_complete() {
   bool seen[FAM_COUNT] = {};
@@ -175,6 +182,14 @@ constexpr const EdgeTypeInfo* edge_type_info(int type) {
   for (const EdgeTypeInfo& t : EDGE_TYPES)
     if (t.type == type) return &t;
   return nullptr;
+}
+
+// the families k_structure_only (structure_only.hip) has a point term for: a landmark edge of any other family on a
+// marginalised vertex is refused by structure_only_* (EdgeObservationBAL: its point takes the Schur path only)
+constexpr bool has_structure_only_form(int f) {
+  return f == FAM_BA || f == FAM_BA_STEREO || f == FAM_BA_UVU || f == FAM_SE3_XYZ || f == FAM_SE3_XYZ_DEPTH ||
+         f == FAM_SE3_XYZ_DISPARITY || f == FAM_SBA_MONO || f == FAM_SBA_STEREO || f == FAM_VSC || f == FAM_SE2XY ||
+         f == FAM_SE2XY_BEARING || f == FAM_U_XYZ || f == FAM_U_XY;
 }
 
 // host-Jacobian types: the error dimension is the code's offset, the endpoints are any registered vertices

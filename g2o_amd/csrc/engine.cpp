@@ -35,6 +35,7 @@ static double wall() {
 int vertex_est_dim(int t) {
   if (t == G2OHIP_V_CAM) return 12;  // the VERTEX_CAM line: x y z qx qy qz qw fx fy cx cy baseline
   if (t == G2OHIP_V_SIM3) return 8;  // tx ty tz qx qy qz qw s
+  if (t == G2OHIP_V_CAM_BAL) return 9;  // rx ry rz tx ty tz f k1 k2
   return t == G2OHIP_V_SE3_EXPMAP || t == G2OHIP_V_SE3_QUAT ? 7 : (t == G2OHIP_V_XY ? 2 : 3);
 }
 int vertex_state_stride(int t) {
@@ -46,6 +47,7 @@ int vertex_state_stride(int t) {
     case G2OHIP_V_XY: return 2;
     case G2OHIP_V_CAM: return 12;
     case G2OHIP_V_SIM3: return 8;
+    case G2OHIP_V_CAM_BAL: return 9;
   }
   return 0;
 }
@@ -248,6 +250,9 @@ void set_state_from_est(int vt, const double* est, double* st) {
       st[7] = est[7];
       break;
     }
+    case G2OHIP_V_CAM_BAL:  // VertexCameraBAL: the 9 values as given
+      for (int k = 0; k < 9; ++k) st[k] = est[k];
+      break;
   }
 }
 void est_from_state(int vt, const double* st, double* est) {
@@ -1291,10 +1296,12 @@ int Engine::add_edges(int type, int n, const int* v0, const int* v1, const doubl
     return G2OHIP_ERR_ARG;
   if (!info && n > 0 && !(gicp && params)) return G2OHIP_ERR_ARG;  // only a plane-to-plane set goes without one
   // no parameter at all: the sba types (the intrinsics live in the VertexCam), EdgeSE2PointXYBearing, EdgeSim3, the Sim3
-  // projections (the intrinsics live in the VertexSim3Expmap)
+  // projections (the intrinsics live in the VertexSim3Expmap), EdgeObservationBAL (they live in the VertexCameraBAL)
   if (params && (type == G2OHIP_E_PROJECT_P2MC || type == G2OHIP_E_PROJECT_P2SC || type == G2OHIP_E_SE2_XY_BEARING ||
-                 type == G2OHIP_E_SIM3 || type == G2OHIP_E_SIM3_PROJECT_XYZ || type == G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ))
-    return G2OHIP_ERR_ARG;
+                 type == G2OHIP_E_SIM3 || type == G2OHIP_E_SIM3_PROJECT_XYZ || type == G2OHIP_E_SIM3_PROJECT_INVERSE_XYZ ||
+                 type == G2OHIP_E_OBSERVATION_BAL))
+    throw StatusError(G2OHIP_ERR_ARG, "g2ohip_add_edges: edge type " + std::to_string(type) +
+                                          " takes no parameter record: params must be NULL");
   if (nm > 0 && !meas && n > 0) return G2OHIP_ERR_ARG;
   for (int k = 0; k < n; ++k)
     if (!hg.idmap.count(v0[k]) || (!unary && !hg.idmap.count(v1[k]))) return G2OHIP_ERR_ARG;
@@ -2139,6 +2146,14 @@ static int mark_edge_vertices(const HostGraph& hg, const std::vector<std::vector
     const EdgeTypeInfo* t = edge_type_info(es.type);  // (nullptr: a host-J type, on any endpoint vertex types)
     if (!t && !is_hostj(es.type)) return G2OHIP_ERR_UNSUPPORTED;
     hostj |= !t;
+    if (!t)  // FamilyHostJ is instantiated for vertex dimensions 2, 3, 6 and 7
+      for (size_t k = 0; k < es.ev0.size(); ++k)
+        for (int vi : {es.ev0[k], es.unary ? es.ev0[k] : es.ev1[k]})
+          if (hg.verts[vi].dim == 9)
+            throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                              "host-Jacobian edge type " + std::to_string(es.type) + " on vertex " +
+                                  std::to_string(hg.verts[vi].id) + " of dimension 9: the vertex dimension must be "
+                                  "2, 3, 6 or 7 (a VertexCameraBAL takes G2OHIP_E_OBSERVATION_BAL)");
     const std::vector<char>* on = si < act.size() && !act[si].empty() ? &act[si] : nullptr;
     for (size_t k = 0; k < es.ev0.size(); ++k) {
       const HVertex& a = hg.verts[es.ev0[k]];
@@ -2228,12 +2243,13 @@ int Engine::initialize_level(int level) {  // sparse_optimizer.cpp:201-279 + bui
   size_poses = num_poses * pd;
   size_landmarks = num_landmarks * ld;
   do_schur = num_landmarks > 0;  // optimization_algorithm_with_hessian.cpp:48-73
-  // the Schur kernels are instantiated for BlockSolver_6_3 and BlockSolver_3_2 (block_solver.h:188-201)
+  // the Schur kernels are instantiated for BlockSolver_6_3 and BlockSolver_3_2 (block_solver.h:188-201) and for
+  // BlockSolver<BlockSolverTraits<9, 3>> (bal_example.cpp:301)
   if (do_schur && pd == 7 && ld == 3)
     throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                       "marginalised points under Sim3 poses need BlockSolver_7_3, whose 7/3 Schur kernels do not "
                       "exist; fix the points (EdgeSim3ProjectXYZ enters as G2OHIP_E_HOSTJ(2) from a fixed point)");
-  if (do_schur && !((pd == 6 && ld == 3) || (pd == 3 && ld == 2))) return G2OHIP_ERR_UNSUPPORTED;
+  if (do_schur && !((pd == 6 && ld == 3) || (pd == 3 && ld == 2) || (pd == 9 && ld == 3))) return G2OHIP_ERR_UNSUPPORTED;
   // landmark-landmark edges have no place in BlockSolver's Schur layout here (a prior on a landmark is no such edge:
   // it lands in the landmark's own Hll block)
   for (size_t si = 0; si < hg.esets.size(); ++si) {
@@ -2552,7 +2568,7 @@ void Engine::fill_group_device(EGroup& g) {
       mo[2] = th;
     } else if (g.family == FAM_SE2XY) {
       mo[0] = m[0]; mo[1] = m[1];
-    } else if (is_sba_family(g.family) || g.family == FAM_SE2XY_BEARING) {
+    } else if (is_sba_family(g.family) || g.family == FAM_SE2XY_BEARING || g.family == FAM_BAL) {
       for (int j = 0; j < mmeas; ++j) mo[j] = m[j];
     } else if (is_sim3_project_family(g.family)) {  // cam_map1 / cam_map2 of v1 (types_seven_dof_expmap.h:84-99)
       mo[0] = m[0]; mo[1] = m[1];
@@ -3086,6 +3102,15 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
                       algorithm + ": Powell's dogleg is not supported on a sharded graph (" + std::to_string(nranks) +
                           " ranks): it multiplies by Hpp (multiplyHessian), and a landmark shard's Hpp diagonal "
                           "blocks are partial sums; use lm_hip_* or gn_hip_* there");
+  if ((use_pcg() || use_cgls()) && pd == 9)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                      algorithm + ": the device PCG and the matrix-free CGLS take pose blocks of 3 or 6, a BAL graph has "
+                                  "camera blocks of 9; use lm_hip_var or lm_hip_fix9_3");
+  if (nranks > 1 && pd == 9)
+    throw StatusError(G2OHIP_ERR_UNSUPPORTED,
+                      "a sharded graph (" + std::to_string(nranks) + " ranks) with camera blocks of 9 is not supported: "
+                      "the landmark shards' exchange is built for BlockSolver_6_3 and BlockSolver_3_2; run BAL problems "
+                      "on one rank");
   if ((use_pcg() || use_cgls()) && pd == 7)
     throw StatusError(G2OHIP_ERR_UNSUPPORTED,
                       algorithm + ": the device PCG and the matrix-free CGLS take pose blocks of 3 or 6, a Sim3 graph has "
@@ -3318,7 +3343,7 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
   db.zero(stream);
   dx.resize(std::max<long long>(n, 1));
   dx.zero(stream);
-  for (int d : {2, 3, 6, 7})  // the fused BA path needs no slots
+  for (int d : {2, 3, 6, 7, 9})  // the fused BA path needs no slots
     dslot[d].resize((size_t)std::max<long long>(ba_fused ? 1 : nslot[d], 1) * (d * (d + 1) / 2 + d));
   // vertex incidence lists (hessian order): code = slot index in the arena of the vertex's dimension, in
   // group / edge order (a fixed summation order)
@@ -3756,8 +3781,10 @@ int Engine::build_structure() {  // block_solver.hpp:102-256
     ds_hpp.upload(shpp, stream);
     dDinv.resize(std::max(nLloc * ld * ld, 1));
     dUfac.resize(std::max(nLloc * launch::schur_ufac_stride(ld), 1));
-    // G = Hpl U^-T per observation (pd x ld), or the split's 10-double Kt records (+ the fixed-landmark ones)
-    dG.resize(std::max<long long>(std::max((long long)nHpl * pd * ld, ((long long)nHpl + n_kx_extra) * 10), 1));
+    // G = Hpl U^-T per observation (pd x ld, blocks launch::schur_g_stride apart: 28 doubles for 9 x 3), or the split's
+    // 10-double Kt records (+ the fixed-landmark ones)
+    dG.resize(std::max<long long>(std::max((long long)nHpl * launch::schur_g_stride(pd, ld),
+                                           ((long long)nHpl + n_kx_extra) * 10), 1));
     dCl.resize(std::max<long long>((long long)num_landmarks * ld, 1));  // c = U^-1 b_l (global landmark index)
     dS.resize((size_t)nS * pd * pd + size_poses);  // [S blocks | bschur] contiguous for one all-reduce
     // blocks and rhs rows the per-rank task lists never write (sch_skip) must read as zeros in the whole-dS all-reduce of
@@ -5136,7 +5163,7 @@ double Engine::kernel_bytes(const std::string& name) const {
       by += g.ne * (8.0 + (g.vtB ? 4.0 : 0.0) + g.D * 8.0 + ((g.ue & 1) ? 0.0 : g.D * (g.D + 1) / 2 * 8.0) +
                     ((g.ue & 2) ? 0.0 : np * 8.0));
     }
-    for (int t : {G2OHIP_V_SE3_EXPMAP, G2OHIP_V_SE3_QUAT, G2OHIP_V_SE2, G2OHIP_V_CAM, G2OHIP_V_SIM3})
+    for (int t : {G2OHIP_V_SE3_EXPMAP, G2OHIP_V_SE3_QUAT, G2OHIP_V_SE2, G2OHIP_V_CAM, G2OHIP_V_SIM3, G2OHIP_V_CAM_BAL})
       by += dstate[t].bytes();
     return by;
   }

@@ -21,7 +21,7 @@
 
 namespace g2ohip {
 
-constexpr int NVT = 8;  // vertex type codes 1..7 (G2OHIP_V_*)
+constexpr int NVT = 9;  // vertex type codes 1..8 (G2OHIP_V_*)
 int vertex_est_dim(int vtype);
 int vertex_state_stride(int vtype);
 
@@ -274,6 +274,9 @@ class Engine {
   int diag_absmax(double* out);
   int load(const char* path, int marginalize_xyz, unsigned flags = 0);  // flags: G2OHIP_LOAD_*
   int save(const char* path);
+  // the BAL text format (bal_io.cpp; bal_example.cpp:336-406): cameras 0 .. ncams-1, then the points, identity information
+  int load_bal(const char* path, int marginalize_points);
+  int save_bal(const char* path);
   // doubles of the host payload of a host-J edge type ([e | Ji | Jj] per edge, insertion order)
   long long host_payload_len(int type);
   // Solver::saveHessian (block_solver.hpp:589-593 -> SparseBlockMatrix::writeOctave, sparse_block_matrix.hpp:579-617)
@@ -408,9 +411,9 @@ class Engine {
   bool ev_valid_ = false;
   DevBuf<int> d_xoff[NVT];         // per type local -> x offset or -1
   DevBuf<int> d_hidx[NVT];         // per type local -> hessian index (-1 fixed)
-  // per-vertex-side slot arenas by vertex dimension (2, 3, 6, 7): packed upper H + b, one slot per (edge, side)
-  DevBuf<double> dslot[8];
-  long long nslot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // per-vertex-side slot arenas by vertex dimension (2, 3, 6, 7, 9): packed upper H + b, one slot per (edge, side)
+  DevBuf<double> dslot[10];
+  long long nslot[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   double* slot_arena(int dim) { return dslot[dim].get(); }
   // off-diagonal blocks several local edges share: per-edge slots reduced in edge order, one launch per block size
   DevBuf<double> doffslot;

@@ -119,6 +119,7 @@ static void binary_dispatch(int family, const EdgeArgs& a, Fn&& fn) {
     case FAM_SIM3: fn(checked<FAM_SIM3, FamilySim3>()); break;
     case FAM_SIM3_PROJECT: fn(checked<FAM_SIM3_PROJECT, FamilySim3Project<false>>()); break;
     case FAM_SIM3_PROJECT_INVERSE: fn(checked<FAM_SIM3_PROJECT_INVERSE, FamilySim3Project<true>>()); break;
+    case FAM_BAL: fn(checked<FAM_BAL, FamilyBAL>()); break;
     case FAM_HOSTJ:
       switch (a.D) {
         case 1: hj_a<1>(a.DA, a.DB, fn); break;

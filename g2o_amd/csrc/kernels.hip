@@ -91,7 +91,12 @@ __global__ void __launch_bounds__(256)
                 double* __restrict__ off_base, double* __restrict__ off_slot) {
   constexpr int D = F::D, DA = F::DA, DB = F::DB;
   constexpr int SA = DA * (DA + 1) / 2 + DA, SB = DB * (DB + 1) / 2 + DB, SH = DA * DB;
-  constexpr int SM = SA > SB ? (SA > SH ? SA : SH) : (SB > SH ? SB : SH);
+  // A side A slot beyond 36 doubles (DA = 9: 54, EdgeObservationBAL's camera) leaves in PA = 2 passes of LW = 32 lanes, as
+  // k_linearize_sim3's 49-double block does: the image stays at 64 * 27 doubles per wave (55296 B per workgroup, under
+  // the 72 KB of D = 6) instead of 64 * 54 (108 KB, one workgroup per CU)
+  constexpr int PA = SA > 36 ? 2 : 1, LW = 64 / PA;
+  constexpr int SAW = (SA * LW + 63) / 64;  // the side A image in doubles per lane of the wave
+  constexpr int SM = SAW > SB ? (SAW > SH ? SAW : SH) : (SB > SH ? SB : SH);
   __shared__ __attribute__((aligned(16))) double stage[4][64 * SM];
   const int tid = threadIdx.x, lane = tid & 63;
   const int e = blockIdx.x * blockDim.x + tid;
@@ -138,29 +143,33 @@ __global__ void __launch_bounds__(256)
       AtO[i * D + c] = s;
     }
   // side A slot (edges whose side A is fixed leave garbage in their slot: never read)
-  if (nfA) {
-    double* o = sw + lane * SA;
-    int k = 0;
 #pragma unroll
-    for (int c = 0; c < DA; ++c)
+  for (int pass = 0; pass < PA; ++pass) {  // lanes [LW pass, LW pass + LW)
+    if (nfA && (PA == 1 || lane / LW == pass)) {
+      double* o = sw + (lane % LW) * SA;
+      int k = 0;
 #pragma unroll
-      for (int r = 0; r <= c; ++r) {
+      for (int c = 0; c < DA; ++c)
+#pragma unroll
+        for (int r = 0; r <= c; ++r) {
+          double s = 0;
+#pragma unroll
+          for (int t = 0; t < D; ++t) s += AtO[r * D + t] * A[t * DA + c];
+          o[k++] = s;
+        }
+#pragma unroll
+      for (int i = 0; i < DA; ++i) {
         double s = 0;
 #pragma unroll
-        for (int t = 0; t < D; ++t) s += AtO[r * D + t] * A[t * DA + c];
+        for (int r = 0; r < D; ++r) s += A[r * DA + i] * wr[r];
         o[k++] = s;
       }
-#pragma unroll
-    for (int i = 0; i < DA; ++i) {
-      double s = 0;
-#pragma unroll
-      for (int r = 0; r < D; ++r) s += A[r * DA + i] * wr[r];
-      o[k++] = s;
     }
+    wave_sync();
+    const int l0 = LW * pass, cnt = min(LW, nw - l0);
+    if (cnt > 0) wave_copy_out(slot0 + (size_t)(ebase + l0) * SA, sw, cnt * SA, lane);
+    wave_sync();
   }
-  wave_sync();
-  wave_copy_out(slot0 + (size_t)ebase * SA, sw, nw * SA, lane);
-  wave_sync();
   // off-diagonal block: staged when the wave's blocks are consecutive with one orientation. Destinations with
   // bit 62 set are per-edge slots of a block several edges share (summed in order by k_offblock_reduce)
   constexpr long long SLOT_BIT = 1LL << 62;
@@ -692,7 +701,11 @@ __global__ void __launch_bounds__(256)
 // so that Hpl Dinv Hpl^T = G G^T and Hpl Dinv b_l = G c_l. k_schur_diag forms G once per observation
 // (for its own sums and, stored, for k_schur_rows). Ufac per landmark (UF doubles, r = reciprocal pivots of U):
 // LD = 3: r0 r1 r2 u10 u20 u21, LD = 2: r0 r1 u10 0. The Schur kernels are instantiated for the reference's
-// BlockSolver_6_3 (PD = 6, LD = 3) and BlockSolver_3_2 (PD = 3, LD = 2) (block_solver.h:188-201).
+// BlockSolver_6_3 (PD = 6, LD = 3) and BlockSolver_3_2 (PD = 3, LD = 2) (block_solver.h:188-201), and for BAL's
+// BlockSolver<BlockSolverTraits<9, 3>> (PD = 9, LD = 3; examples/bal/bal_example.cpp:301).
+// G blocks (PD x LD col-major) sit GS = schur_g_stride(PD, LD) doubles apart: PD * LD rounded up to whole 16-byte
+// pieces, so that every block starts on a 16-byte boundary for the double2 moves and the LDS-DMA of k_schur_rows and
+// k_backsub_g. (6, 3) and (3, 2): GS = PD * LD, the layout unchanged; (9, 3): 27 -> 28, one zero double behind each block.
 template <int LD>
 struct LmTraits;
 template <>
@@ -764,10 +777,11 @@ __global__ void __launch_bounds__(256)
                  const double* __restrict__ lam, const unsigned char* __restrict__ lam_own,
                  const double* __restrict__ lam_full, double* __restrict__ S, double* __restrict__ bschur,
                  double* __restrict__ G) {
-  constexpr int GB = PD * LD, UF = LmTraits<LD>::UF, NPK = PD * (PD + 1) / 2, NA = NPK + PD;
-  static_assert(GB % 2 == 0 && UF % 2 == 0, "16-byte block loads");
+  constexpr int GB = PD * LD, GS = launch::schur_g_stride(PD, LD), UF = LmTraits<LD>::UF, NPK = PD * (PD + 1) / 2,
+                NA = NPK + PD;
+  static_assert(GS % 2 == 0 && UF % 2 == 0, "16-byte block stores");
   __shared__ double red[4][NA];
-  __shared__ __attribute__((aligned(16))) double gst[4][64 * GB];  // per-wave image of 64 G blocks
+  __shared__ __attribute__((aligned(16))) double gst[4][64 * GS];  // per-wave image of 64 G blocks
   // XCD-contiguous camera rows: the observations of one landmark (neighbours in Hpl) are read by
   // rows of nearby cameras, i.e. mostly behind one L2
   const int row = xcd_item(blockIdx.x, nrows), tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -779,11 +793,18 @@ __global__ void __launch_bounds__(256)
     const int p = pb + lane, nw = min(64, p1 - pb);
     if (p < p1) {
       const int a = robs[p], l = obs_lm[a];
-      const double2* h2 = reinterpret_cast<const double2*>(Hpl + (size_t)a * GB);
       const double2* u2 = reinterpret_cast<const double2*>(Ufac + (size_t)l * UF);
-      double g[GB], U[UF], c[LD];
+      double g[GS], U[UF], c[LD];
+      if constexpr (GB % 2 == 0) {
+        const double2* h2 = reinterpret_cast<const double2*>(Hpl + (size_t)a * GB);
 #pragma unroll
-      for (int k = 0; k < GB / 2; ++k) { const double2 v = h2[k]; g[2 * k] = v.x; g[2 * k + 1] = v.y; }
+        for (int k = 0; k < GB / 2; ++k) { const double2 v = h2[k]; g[2 * k] = v.x; g[2 * k + 1] = v.y; }
+      } else {  // Hpl blocks are GB doubles apart: an odd block starts on 8 bytes only
+        const double* h = Hpl + (size_t)a * GB;
+#pragma unroll
+        for (int k = 0; k < GB; ++k) g[k] = h[k];
+        g[GB] = 0.0;  // the pad of the stored G block
+      }
 #pragma unroll
       for (int k = 0; k < UF / 2; ++k) { const double2 v = u2[k]; U[2 * k] = v.x; U[2 * k + 1] = v.y; }
       const double* cp = cl_all + (size_t)(lm0 + l) * LD;
@@ -792,9 +813,9 @@ __global__ void __launch_bounds__(256)
       form_G<PD, LD>(g, U);
       {  // every observation lies in exactly one camera row: G is written once, in camera-row order,
          // for k_schur_rows; the wave's blocks leave as one contiguous coalesced run (below)
-        double2* go = reinterpret_cast<double2*>(gst[w] + lane * GB);
+        double2* go = reinterpret_cast<double2*>(gst[w] + lane * GS);
 #pragma unroll
-        for (int k = 0; k < GB / 2; ++k) go[k] = double2{g[2 * k], g[2 * k + 1]};
+        for (int k = 0; k < GS / 2; ++k) go[k] = double2{g[2 * k], g[2 * k + 1]};
       }
       int k = 0;
 #pragma unroll
@@ -815,7 +836,7 @@ __global__ void __launch_bounds__(256)
       }
     }
     wave_sync();  // converged: the whole wave copies the image out
-    wave_copy_out(G + (size_t)pb * GB, gst[w], nw * GB, lane);
+    wave_copy_out(G + (size_t)pb * GS, gst[w], nw * GS, lane);
     wave_sync();
   }
 #pragma unroll
@@ -854,14 +875,14 @@ __global__ void __launch_bounds__(256)
 template <int PD, int LD>
 __device__ __forceinline__ void schur_pairs(const double* Gs, const int* sp, const int* spp, int noff, int ls, int q,
                                             double (&acc)[((PD + 1) / 2) * PD]) {
-  constexpr int GB = PD * LD, CW = (PD + 1) / 2;
+  constexpr int GS = launch::schur_g_stride(PD, LD), CW = (PD + 1) / 2;
   const int c0 = (q & 1) * CW, par = q >> 1;
   if (ls >= noff) return;
   const int p1 = spp[ls + 1];
   for (int p = spp[ls] + par; p < p1; p += 2) {
     const int pr = sp[p];
-    const double* ga = &Gs[(pr & 0xffff) * GB];
-    const double* gb = &Gs[(pr >> 16) * GB + c0];
+    const double* ga = &Gs[(pr & 0xffff) * GS];
+    const double* gb = &Gs[(pr >> 16) * GS + c0];
 #pragma unroll
     for (int kk = 0; kk < LD; ++kk) {  // one column of G_a and CW entries of G_b at a time
       double A[PD], Bm[CW];
@@ -1116,7 +1137,8 @@ __global__ void __launch_bounds__(256, OCC)
                  double* __restrict__ fronts, double* __restrict__ part, const int* __restrict__ gmap) {
   static_assert(!KX || (PD == 6 && LD == 3), "Kt records: BA blocks");
   constexpr int SCH_NI = (SCH_SB + 255) / 256;
-  constexpr int GB = KX ? 10 : PD * LD;              // doubles per staged block: G, PD x LD col-major (or a Kt record)
+  constexpr int GB = KX ? 10 : launch::schur_g_stride(PD, LD);  // doubles per staged block: G, PD x LD col-major and
+                                                                 // its pad (or a Kt record)
   constexpr int NPC = GB / 2;                        // 16-B pieces per block
   constexpr int NC = (SCH_SB * NPC + 255) / 256;     // 16-B pieces per thread per batch
   constexpr int CW = (PD + 1) / 2;                   // output columns (and rows) per half
@@ -1360,7 +1382,7 @@ __global__ void __launch_bounds__(256)
                 const double* __restrict__ Ufac, const double* __restrict__ cl_all, int size_poses, int lm0,
                 double* __restrict__ x) {
   constexpr int UF = LmTraits<LD>::UF;
-  constexpr int GB = PD * LD, GP = GB / 2;  // doubles / 16-B pieces per block
+  constexpr int GB = launch::schur_g_stride(PD, LD), GP = GB / 2;  // doubles (with the pad) / 16-B pieces per block
   constexpr int CH = 32;                    // blocks per staged chunk (per wave)
   static_assert(GB % 2 == 0, "blocks are whole 16-B pieces");
   // A wave's landmarks own one contiguous run of G blocks (Hpl order is landmark-major). The run is staged through
@@ -1565,6 +1587,16 @@ __device__ __forceinline__ void d_oplus_sim3(int v, const int* __restrict__ xoff
   s[7] = sn;
 }
 
+// VertexCameraBAL::oplusImpl (bal_example.cpp:90-94): estimate += update, all 9 values
+__device__ __forceinline__ void d_oplus_cam_bal(int v, const int* __restrict__ xoff, const double* __restrict__ x,
+                                                double* __restrict__ st) {
+  if (xoff[v] < 0) return;
+  const double* u = x + xoff[v];
+  double* s = st + (size_t)v * 9;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s[k] += u[k];
+}
+
 // SparseOptimizer::update (sparse_optimizer.cpp:441-454) over every vertex type in one launch: block ranges per type
 __global__ void __launch_bounds__(256) k_oplus_multi(launch::OplusList L, const double* __restrict__ x) {
   int t = 0;
@@ -1579,6 +1611,7 @@ __global__ void __launch_bounds__(256) k_oplus_multi(launch::OplusList L, const 
     case 5: d_oplus_xy(v, L.xoff[t], x, L.st[t], L.nopl); break;
     case 6: d_oplus_cam(v, L.xoff[t], x, L.st[t], L.nopl); break;
     case 7: d_oplus_sim3(v, L.xoff[t], x, L.st[t], L.sim3_fix_scale); break;
+    case 8: d_oplus_cam_bal(v, L.xoff[t], x, L.st[t]); break;
   }
 }
 
@@ -2110,7 +2143,8 @@ static void vreduce_dim(int nv, int lanes, const int* ptr, const int* code, cons
     case 4: hipLaunchKernelGGL((k_vertex_reduce<DIM, 4>), g, 256, 0, s, nv, ptr, code, slots, H, b, boff); break;
     case 8: hipLaunchKernelGGL((k_vertex_reduce<DIM, 8>), g, 256, 0, s, nv, ptr, code, slots, H, b, boff); break;
     case 64:
-      // (the wide kernel reads one slot per half-wave: dimension 7's 35 doubles do not fit and take the 64-lane one)
+      // (the wide kernel reads one slot per half-wave: dimension 7's 35 and dimension 9's 54 doubles do not fit and take
+      // the 64-lane one)
       if constexpr (DIM * (DIM + 1) / 2 + DIM <= 32) {
         if (vr_wide()) {
           hipLaunchKernelGGL((k_vertex_reduce_wide<DIM>), nv, 256, 0, s, nv, ptr, code, slots, H, b, boff);
@@ -2131,6 +2165,7 @@ void vertex_reduce(int dim, int nv, int lanes, const int* ptr, const int* code, 
   else if (dim == 3) vreduce_dim<3>(nv, lanes, ptr, code, slots, H, b, boff, s);
   else if (dim == 6) vreduce_dim<6>(nv, lanes, ptr, code, slots, H, b, boff, s);
   else if (dim == 7) vreduce_dim<7>(nv, lanes, ptr, code, slots, H, b, boff, s);
+  else if (dim == 9) vreduce_dim<9>(nv, lanes, ptr, code, slots, H, b, boff, s);
   else throw std::runtime_error("vertex_reduce: unsupported dim");
 }
 
@@ -2141,12 +2176,13 @@ void offblock_reduce(int nb, int bsz, const int* ptr, const long long* soff, con
   KERNEL_CHECK();
 }
 
-// (pose, landmark) block sizes with Schur kernels: BlockSolver_6_3 and BlockSolver_3_2
+// (pose, landmark) block sizes with Schur kernels: BlockSolver_6_3, BlockSolver_3_2 and BAL's BlockSolver<9, 3>
 template <class Fn>
 static void pl_dispatch(int pd, int ld, Fn&& fn) {
   if (pd == 6 && ld == 3) fn(std::integral_constant<int, 6>{}, std::integral_constant<int, 3>{});
   else if (pd == 3 && ld == 2) fn(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
-  else throw std::runtime_error("Schur complement: (pose, landmark) dimensions must be (6, 3) or (3, 2)");
+  else if (pd == 9 && ld == 3) fn(std::integral_constant<int, 9>{}, std::integral_constant<int, 3>{});
+  else throw std::runtime_error("Schur complement: (pose, landmark) dimensions must be (6, 3), (3, 2) or (9, 3)");
 }
 void schur_prep(int ld, int nl, int lm0, const double* Hll, const double* bl_all, const double* lam, double* Dinv,
                 double* Ufac, double* cl_all, int* fail, hipStream_t s) {
@@ -2191,7 +2227,8 @@ void schur_part_sum(int pd, int ngroups, const SchurPartGroup* groups, const dou
   if (ngroups <= 0) return;
   if (pd == 6) hipLaunchKernelGGL(k_schur_part_sum<6>, ngroups, 256, 0, s, groups, part, s_hpp, Hpp, S);
   else if (pd == 3) hipLaunchKernelGGL(k_schur_part_sum<3>, ngroups, 256, 0, s, groups, part, s_hpp, Hpp, S);
-  else throw DeviceError("schur_part_sum: pose blocks of 3 or 6");
+  else if (pd == 9) hipLaunchKernelGGL(k_schur_part_sum<9>, ngroups, 256, 0, s, groups, part, s_hpp, Hpp, S);
+  else throw DeviceError("schur_part_sum: pose blocks of 3, 6 or 9");
   KERNEL_CHECK();
 }
 void schur_rows(int pd, int ld, int ntasks, const SchurTask* tasks, const SchurBatch* batches, const int* st_obs,
@@ -2229,12 +2266,16 @@ void schur_rows(int pd, int ld, int ntasks, const SchurTask* tasks, const SchurB
   }
   pl_dispatch(pd, ld, [&](auto P, auto L) {
     constexpr int pv = decltype(P)::value, lv = decltype(L)::value;
+    // (9, 3): 45 accumulators per thread and 2 x 128 x 28 doubles of staged blocks (57344 B + 3856 B of indices): LDS
+    // admits two workgroups per CU, so the register budget is set for two (OCC 2: 256 VGPRs) and the batch stays at the
+    // host's SCHUR_SB = 128 blocks
+    constexpr int occ = pv == 9 ? SCHUR_OCC_9_3 : 4;
     if (pipe == 0)
-      hipLaunchKernelGGL((k_schur_rows<pv, lv, 0>), ntasks + nz, 256, 0, s, tasks, batches, st_obs, pairs, pp, G, s_hpp,
-                         Hpp, S, mode, ntasks, zr, fronts, part, gmap);
+      hipLaunchKernelGGL((k_schur_rows<pv, lv, 0, false, SCHUR_SB, occ>), ntasks + nz, 256, 0, s, tasks, batches, st_obs,
+                         pairs, pp, G, s_hpp, Hpp, S, mode, ntasks, zr, fronts, part, gmap);
     else
-      hipLaunchKernelGGL((k_schur_rows<pv, lv, 1>), ntasks + nz, 256, 0, s, tasks, batches, st_obs, pairs, pp, G, s_hpp,
-                         Hpp, S, mode, ntasks, zr, fronts, part, gmap);
+      hipLaunchKernelGGL((k_schur_rows<pv, lv, 1, false, SCHUR_SB, occ>), ntasks + nz, 256, 0, s, tasks, batches, st_obs,
+                         pairs, pp, G, s_hpp, Hpp, S, mode, ntasks, zr, fronts, part, gmap);
   });
   KERNEL_CHECK();
 }
@@ -2329,7 +2370,8 @@ void block_symv(int pd, int n, const int* rptr, const int2* ent, const int* diag
   if (pd == 6) hipLaunchKernelGGL(k_block_symv<6>, g, 256, 0, s, n, rptr, ent, diag, vals, lam, x, y, b, r2, b2);
   else if (pd == 3) hipLaunchKernelGGL(k_block_symv<3>, g, 256, 0, s, n, rptr, ent, diag, vals, lam, x, y, b, r2, b2);
   else if (pd == 7) hipLaunchKernelGGL(k_block_symv<7>, g, 256, 0, s, n, rptr, ent, diag, vals, lam, x, y, b, r2, b2);
-  else throw std::runtime_error("block_symv: block dimension must be 3, 6 or 7");
+  else if (pd == 9) hipLaunchKernelGGL(k_block_symv<9>, g, 256, 0, s, n, rptr, ent, diag, vals, lam, x, y, b, r2, b2);
+  else throw std::runtime_error("block_symv: block dimension must be 3, 6, 7 or 9");
   KERNEL_CHECK();
 }
 void scale_terms(long long n, const double* x, const double* b, const double* lam, double* out, hipStream_t s) {
@@ -2353,7 +2395,10 @@ static void dl_symv_dots(const DoglegSymv& H, long long n, const double* v, cons
   else if (H.pd == 7)
     hipLaunchKernelGGL(k_dl_symv_dots<7>, nsb + nps, RED_BLOCK, 0, s, H.npose, n, nsb, nps, H.rptr, H.ent, H.diag,
                        H.vals, v, w, partial);
-  else throw std::runtime_error("dogleg: block dimension must be 3, 6 or 7");
+  else if (H.pd == 9)
+    hipLaunchKernelGGL(k_dl_symv_dots<9>, nsb + nps, RED_BLOCK, 0, s, H.npose, n, nsb, nps, H.rptr, H.ent, H.diag,
+                       H.vals, v, w, partial);
+  else throw std::runtime_error("dogleg: block dimension must be 3, 6, 7 or 9");
   KERNEL_CHECK();
 }
 void dl_alpha(const DoglegSymv& H, long long n, const double* b, double* partial, double* p, hipStream_t s) {

@@ -121,6 +121,11 @@ void schur_diag(int pd, int ld, int nrows, const int* rptr, const int* robs, con
 // row-stationary off-diagonal Schur pass (k_schur_rows): task = (camera row, <= SCHUR_SL off-diagonal
 // slots), batch = <= SCHUR_SB staged observation blocks of the row's landmarks
 constexpr int SCHUR_SB = 128, SCHUR_SL = 64;  // 128: 4 workgroups per CU (LDS), 150 vs 172 us at C4
+// doubles between two G blocks (k_schur_diag writes, k_schur_rows and k_backsub_g read, Engine allocates): pd * ld rounded
+// up to whole 16-byte pieces. (6, 3): 18 and (3, 2): 6, as ever; (9, 3): 28
+constexpr int schur_g_stride(int pd, int ld) { return (pd * ld + 1) & ~1; }
+// k_schur_rows<9, 3>: workgroups per CU its register budget is set for (LDS admits two at SCHUR_SB = 128)
+constexpr int SCHUR_OCC_9_3 = 2;
 // batches of the BA split's 80-byte Kt records (assembly.hip KXB): 192 blocks are 30 KB of staging, still 4 workgroups
 // per CU, and a third fewer batches per row task than 128
 #ifndef G2OHIP_SCHUR_SB_KX

@@ -75,10 +75,11 @@ void Engine::so_build_list() {
   }
   L.nlm = (int)local.size();
   // the landmark end of each group (EdgeTypeInfo::lm): v0 for the BA and sba types, Edge_XYZ_VSC and the point priors, v1
-  // for slam3d, SE2-XY and the bearing edge; LM_NONE: the other types and the host-J ones
+  // for slam3d, SE2-XY and the bearing edge; LM_NONE: the other types, the host-J ones, and the landmark edges whose
+  // family k_structure_only has no term for (has_structure_only_form: EdgeObservationBAL)
   auto lm_side = [&](const EGroup& g) {
     const EdgeTypeInfo* t = edge_type_info(hg.esets[g.set].type);
-    return t ? t->lm : LM_NONE;
+    return t && has_structure_only_form(t->family) ? t->lm : LM_NONE;
   };
   std::vector<int> cnt(L.nlm + 1, 0);
   std::vector<int> gslot(groups.size(), -1);

@@ -80,21 +80,25 @@ E_SIM3 = 27
 # EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ from a fixed V_XYZ point to a V_SIM3 (meas u v, info 2x2, no params: the
 # intrinsics are camera 1 / camera 2 of the Sim3 vertex)
 E_SIM3_PROJECT, E_SIM3_PROJECT_INVERSE = 28, 29
-EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12, V_SIM3: 8}
+# examples/bal: VertexCameraBAL, estimate rx ry rz tx ty tz f k1 k2 (angle-axis, world->camera), dimension 9;
+# EdgeObservationBAL from it (v0) to a V_XYZ point (v1), meas u v, info 2x2, no params
+V_CAM_BAL = 8
+E_OBSERVATION_BAL = 30
+EST_DIM = {V_SE3_EXPMAP: 7, V_XYZ: 3, V_SE3_QUAT: 7, V_SE2: 3, V_XY: 2, V_CAM: 12, V_SIM3: 8, V_CAM_BAL: 9}
 MEAS_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 7, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
             E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 7, E_XYZ_PRIOR: 3,
             E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
             E_SE3_EXPMAP: 7, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
             E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 7, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
             E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 12, E_XYZ_VSC: 3, E_SIM3: 8,
-            E_SIM3_PROJECT: 2, E_SIM3_PROJECT_INVERSE: 2}
+            E_SIM3_PROJECT: 2, E_SIM3_PROJECT_INVERSE: 2, E_OBSERVATION_BAL: 2}
 ERR_DIM = {E_SE3_PROJECT_XYZ: 2, E_SE3_QUAT: 6, E_SE2: 3, E_SE2_XY: 2, E_STEREO_SE3_PROJECT_XYZ: 3,
            E_SE2_PRIOR: 3, E_SE2_XY_PRIOR: 2, E_XY_PRIOR: 2, E_SE3_PRIOR: 6, E_XYZ_PRIOR: 3,
            E_SE3_XYZ: 3, E_SE3_XYZ_DEPTH: 3, E_SE3_XYZ_DISPARITY: 3,
            E_SE3_EXPMAP: 6, E_SE3_PROJECT_XYZ_ONLYPOSE: 2, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 3,
            E_PROJECT_P2MC: 2, E_PROJECT_P2SC: 3, E_SE3_OFFSET: 6, E_SE2_OFFSET: 3, E_SE2_XY_BEARING: 1,
            E_PROJECT_XYZ2UV: 2, E_PROJECT_XYZ2UVU: 3, E_V_V_GICP: 3, E_XYZ_VSC: 3, E_SIM3: 7,
-           E_SIM3_PROJECT: 2, E_SIM3_PROJECT_INVERSE: 2}
+           E_SIM3_PROJECT: 2, E_SIM3_PROJECT_INVERSE: 2, E_OBSERVATION_BAL: 2}
 # parameter values per edge of the types that take a record (EdgeSet.params; where None is allowed it is the identity)
 PARAM_DIM = {E_SE3_PROJECT_XYZ: 4, E_STEREO_SE3_PROJECT_XYZ: 5, E_SE3_PRIOR: 7, E_SE3_XYZ: 7, E_SE3_XYZ_DEPTH: 11,
              E_SE3_XYZ_DISPARITY: 11, E_SE3_PROJECT_XYZ_ONLYPOSE: 7, E_STEREO_SE3_PROJECT_XYZ_ONLYPOSE: 8,
@@ -1419,3 +1423,53 @@ def sim3_twin(prob: Problem) -> Problem:
     edges = [EdgeSet(32 + 7, es.v0.copy(), es.v1.copy(), None, es.info.copy(), None) if es.etype == E_SIM3 else es
              for es in prob.edges]
     return Problem(prob.name + "/hostj", list(prob.vertices), edges, prob.pose_dim, prob.landmark_dim)
+
+
+# ---------------------------------------------------------------- examples/bal
+def bal_project(cam: np.ndarray, X: np.ndarray) -> np.ndarray:
+    """EdgeObservationBAL's prediction (bal_example.cpp:191-238) for cameras [n, 9] rx ry rz tx ty tz f k1 k2 and points
+    [n, 3]: P = R(w) X + t by Rodrigues' formula (theta == 0: X + w x X), p = -P.xy / P.z, f (1 + k1 r2 + k2 r2^2) p."""
+    w, t = cam[:, :3], cam[:, 3:6]
+    th = np.sqrt(np.sum(w * w, 1))[:, None]
+    v = w / np.where(th > 0, th, 1.0)
+    c, s = np.cos(th), np.sin(th)
+    P = np.where(th > 0, X * c + np.cross(v, X) * s + v * np.sum(v * X, 1)[:, None] * (1 - c), X + np.cross(w, X)) + t
+    p = -P[:, :2] / P[:, 2:3]
+    r2 = np.sum(p * p, 1)
+    return (cam[:, 6] * (1 + cam[:, 7] * r2 + cam[:, 8] * r2 * r2))[:, None] * p
+
+
+def bal(num_cameras: int = 49, num_points: int = 7776, num_observations: int = 31843, pixel_noise: float = 0.5,
+        point_noise: float = 0.01, seed: int = SEED) -> Problem:
+    """A synthetic "Bundle Adjustment in the Large" problem; the defaults are the shape of Ladybug's
+    problem-49-7776-pre.txt. Cameras (V_CAM_BAL, ids 0 .. num_cameras-1) drive along x looking down -z with small
+    attitudes, f 400 - 600, |k1| <= 0.05, |k2| <= 0.01; points (V_XYZ, marginalised, ids behind the cameras') lie 4 - 7
+    in front of the track. Every point is seen by at least two cameras of a window of consecutive ones, the remaining
+    observations are spread at random; Omega = I2, nothing is fixed (as bal_example leaves the gauge to LM)."""
+    rng = _rng(seed, 90)
+    nc, npt, no = num_cameras, num_points, num_observations
+    assert nc >= 2 and no >= 2 * npt and no <= nc * npt
+    x0 = 0.25 * np.arange(nc)
+    w = 0.05 * rng.standard_normal((nc, 3))
+    cams = np.concatenate([w, np.stack([-x0, np.zeros(nc), np.zeros(nc)], 1) + 0.02 * rng.standard_normal((nc, 3)),
+                           rng.uniform(400, 600, (nc, 1)), rng.uniform(-0.05, 0.05, (nc, 1)), rng.uniform(-0.01, 0.01, (nc, 1))], 1)
+    cnt = 2 + rng.multinomial(no - 2 * npt, np.full(npt, 1.0 / npt))
+    cnt = np.minimum(cnt, nc)
+    short = no - int(cnt.sum())  # counts cut at num_cameras: hand the rest to the points with room, in order
+    for k in range(npt):
+        if short <= 0:
+            break
+        add = min(short, nc - int(cnt[k]))
+        cnt[k] += add
+        short -= add
+    first = np.array([rng.integers(0, nc - c + 1) for c in cnt])
+    ci = np.concatenate([f + np.arange(c) for f, c in zip(first, cnt)])
+    pi = np.repeat(np.arange(npt), cnt)
+    centre = x0[first] + 0.25 * (cnt - 1) / 2.0  # in front of the middle of the point's window
+    pts = np.stack([centre + rng.uniform(-1.5, 1.5, npt), rng.uniform(-1.5, 1.5, npt), -rng.uniform(4.0, 7.0, npt)], 1)
+    obs = bal_project(cams[ci], pts[pi]) + pixel_noise * rng.standard_normal((len(ci), 2))
+    info = np.broadcast_to(np.eye(2), (len(ci), 2, 2)).copy()
+    start = pts + point_noise * rng.standard_normal((npt, 3))
+    verts = [VertexSet(V_CAM_BAL, np.arange(nc, dtype=np.int32), cams, np.zeros(nc, np.int32), np.zeros(nc, np.int32)),
+             VertexSet(V_XYZ, (nc + np.arange(npt)).astype(np.int32), start, np.zeros(npt, np.int32), np.ones(npt, np.int32))]
+    return Problem(f"bal_{nc}_{npt}", verts, [EdgeSet(E_OBSERVATION_BAL, ci.astype(np.int32), (nc + pi).astype(np.int32), obs, info)], 9, 3)

@@ -11,7 +11,7 @@
  *        + SparseOptimizer::optimize (core/sparse_optimizer.cpp:374-439) ... g2ohip_optimize
  *   OptimizableGraph::load / save (core/optimizable_graph.cpp:397-679) .. g2ohip_load_g2o / g2ohip_save_g2o
  *   OptimizationAlgorithmFactory::construct (core/optimization_algorithm_factory.cpp:84-93)
- *        .. g2ohip_set_algorithm("lm_hip_fix6_3" | "lm_hip_fix3_3" | "lm_hip_fix6_6" | "lm_hip_fix7_3" | "lm_hip_var" | "gn_hip_*"
+ *        .. g2ohip_set_algorithm("lm_hip_fix6_3" | "lm_hip_fix3_3" | "lm_hip_fix6_6" | "lm_hip_fix7_3" | "lm_hip_fix9_3" | "lm_hip_var" | "gn_hip_*"
  *           | "dl_hip_*" (Powell's dogleg, core/optimization_algorithm_dogleg.cpp:57-208; the same suffixes)
  *           | "structure_only_3" | "structure_only_2" (StructureOnlySolver<PointDoF>, solvers/structure_only/
  *             structure_only.cpp:64-65, structure_only_solver.h:60-229; g2ohip_structure_only_calc is its calc())
@@ -54,6 +54,11 @@ extern "C" {
                                  (sim3.h:66-135, 255-261) with all four branches of the exponential, and nothing is
                                  normalised afterwards: neither the 7-vector constructor nor operator* does in the
                                  reference. See g2ohip_set_sim3_fix_scale */
+#define G2OHIP_V_CAM_BAL 8    /* VertexCameraBAL, examples/bal/bal_example.cpp:59-95, dimension 9. The estimate is 9
+                                 doubles: rx ry rz tx ty tz f k1 k2, an angle-axis rotation (world to camera), the
+                                 translation, the focal length and two radial distortion coefficients. Nothing is
+                                 normalised on entry. oplus is estimate += update (:90-94); g2ohip_minimal_state gives
+                                 the 9 values. VertexPointBAL is G2OHIP_V_XYZ as it stands (the same estimate and +=) */
 /* ---- edge types ---- */
 #define G2OHIP_E_SE3_PROJECT_XYZ 1 /* EdgeSE3ProjectXYZ, types_six_dof_expmap.h:201-229: v0 point, v1 camera;
                                       meas u v; info 2x2; params fx fy cx cy */
@@ -234,6 +239,24 @@ extern "C" {
                             obs - cam_map2(project(S.inverse().map(p))), S.inverse() as the reference's constructor
                             builds it (conjugate, conj * (-t / s), 1 / s, then normalizeRotation). With (R', t', s') =
                             S^-1 and y = s' R' p + t': Jj = -P(y) s' R' [ [p]x | -I | -p ], Ji = -P(y) s' R' */
+/* ---- examples/bal: "Bundle Adjustment in the Large" problems. Cameras of 9 parameters and marginalised points are
+ * BlockSolver<BlockSolverTraits<9, 3>> (bal_example.cpp:301): {lm,gn,dl}_hip_fix9_3 or *_hip_var, with the 9/3 Schur
+ * kernels. lm_pcg*, gn_pcg* and lm_pcg6_3_eigen refuse such a graph (pose blocks of 3 or 6 only), as do a sharded
+ * structure build (g2ohip_set_comm* with nranks > 1) and structure_only_* on a point that carries the edge; a free
+ * non-marginalised point beside the cameras breaks the one-pose-block-size rule. Host-Jacobian edges on a dimension-9
+ * vertex are not supported. See g2ohip_load_bal / g2ohip_save_bal. ---- */
+#define G2OHIP_E_OBSERVATION_BAL 30 /* EdgeObservationBAL, bal_example.cpp:156-281: v0 the camera (G2OHIP_V_CAM_BAL), v1
+                            the point (G2OHIP_V_XYZ), in the reference's vertex order; meas u v; info 2x2 (equal records
+                            are shared); params must be NULL (non-NULL is G2OHIP_ERR_ARG). With w = est[0:3] and
+                            th = sqrt(w.w): P = X cos th + (v x X) sin th + v (v.X)(1 - cos th), v = w / th (th == 0:
+                            P = X + w x X), P += t, p = -P.xy / P.z, r2 = p.p, rp = 1 + k1 r2 + k2 r2 r2,
+                            e = f rp p - z, in the reference's operation order (:191-244). The reference differentiates
+                            with ceres autodiff (:254-280); the device forms the same exact first derivatives of the
+                            expression as written, branch by branch, term by term through th, v, sin and cos. No
+                            isDepthPositive in the reference (depth_positive != NULL or check_depth is G2OHIP_ERR_ARG);
+                            robust kernels, edge levels, g2ohip_edge_chi2 and g2ohip_classify_edges take it like any
+                            device type. No .g2o file carries it (the reference's read / write return false):
+                            g2ohip_save_g2o refuses a graph that holds it */
 /* Any other BaseUnaryEdge<D, E, V> on a registered vertex of dimension 2, 3, 6 or 7 (an edge type of the application's own, say): the
  * host supplies the error and the Jacobian as for G2OHIP_E_HOSTJ, payload [e (D) | Ji (D x dim(v0))] row-major per
  * edge. meas unused (may be NULL); info D*D. */
@@ -402,8 +425,21 @@ int g2ohip_load_g2o_ex(g2ohip_graph* g, const char* path, int marginalize_xyz, u
  * line per distinct record in the same id space. G2OHIP_E_V_V_GICP edges are written as EDGE_V_V_GICP v0 v1 and the 12
  * values pos0 normal0 pos1 normal1 (types_icp.cpp:206-222): as in the reference the line carries neither the
  * information nor the covariances, a reader rebuilds the point-to-plane information from normal0. A graph holding
- * G2OHIP_E_XYZ_VSC edges is not written (G2OHIP_ERR_UNSUPPORTED, nothing written). */
+ * G2OHIP_E_XYZ_VSC or G2OHIP_E_OBSERVATION_BAL edges is not written (G2OHIP_ERR_UNSUPPORTED, nothing written). */
 int g2ohip_save_g2o(g2ohip_graph* g, const char* path);
+/* The BAL text format as bal_example.cpp:336-406 reads it: "ncams npts nobs", nobs records "cam pt x y", 9 * ncams
+ * camera values, 3 * npts point values, with whitespace of any kind between the tokens. Cameras become G2OHIP_V_CAM_BAL
+ * vertices with ids 0 .. ncams-1, points G2OHIP_V_XYZ vertices with ids ncams .. ncams+npts-1 (marginalised according to
+ * the flag), observations G2OHIP_E_OBSERVATION_BAL edges whose information is the identity, held as one shared record.
+ * A short file, counts the file is too short for, a token that is no finite decimal number ("nan", "inf" and
+ * hexadecimal floats among them) or an index out of range is G2OHIP_ERR_ARG, g2ohip_last_error names the record, and
+ * the graph is left as it was: the file is parsed and checked as a whole before a vertex is added. */
+int g2ohip_load_bal(g2ohip_graph* g, const char* path, int marginalize_points);
+/* Writes the same format from the current estimates, with 17 significant digits: load -> save -> load is bitwise. The
+ * graph must hold only G2OHIP_V_CAM_BAL, G2OHIP_V_XYZ and G2OHIP_E_OBSERVATION_BAL, ids of the shape g2ohip_load_bal
+ * gives (cameras 0 .. ncams-1, then the points) and identity information; otherwise G2OHIP_ERR_UNSUPPORTED and nothing
+ * is written. */
+int g2ohip_save_bal(g2ohip_graph* g, const char* path);
 int g2ohip_num_vertices(g2ohip_graph* g);
 int g2ohip_num_edges(g2ohip_graph* g);
 /* estimates of one vertex type in insertion order (syncs device state to host first) */
